@@ -9,7 +9,8 @@ K-marg), then K Levenberg-Marquardt trials, each = linearise ALL factors of the 
 J^T J (K3) -> banded Cholesky solve (K4) -> retract + cost + accept/reject (K5).
 value = (windows on all ranks) * steps / max-over-ranks time: one new keyframe per window per step.
 
-Contract: python bench.py --gpus N --steps K --warmup W ; rank 0 prints ONE JSON line.
+Contract: python bench.py --gpus N --steps K --warmup W ; rank 0 prints ONE JSON line.  --dump-outputs DIR: rank 0 also
+writes what the last timed step computed as DIR/*.npy (dump_outputs); the inputs depend on the arguments alone.
 N > 1: one rank per GPU -- launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the
 environment), or, when bench.py is started directly with --gpus N and no WORLD_SIZE, by bench.py itself, which
 starts N fresh child ranks BEFORE anything touches the GPU and exits with their status.  Windows are independent,
@@ -50,6 +51,7 @@ IMU_BYTES = 1776 + 8 * (15 + 450 - 159)
 IMU_BYTES_DENSE = 5496
 EXIT_SHARDED_SECTION_HUNG = 75   # the headline line was printed, the time-sharded (collective) section did not finish
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
 
 
 def _make_seq(job):
@@ -678,6 +680,29 @@ def compact_line(full, detail_name="bench_detail.json"):
     return line
 
 
+def dump_sample(windows, n):
+    """Windows whose n states --dump-outputs writes: all of them when they fit in DUMP_BYTES beside the per-window LM
+    summary (1 MB left for the .npy headers), else a seeded sample.  Empty when not even one window fits."""
+    room = DUMP_BYTES - (1 << 20) - windows * 6 * 8
+    k = max(0, min(windows, room // (n * 16 * 8)))
+    if k == windows:
+        return np.arange(windows)
+    return np.sort(np.random.default_rng(20241015).choice(windows, size=k, replace=False))
+
+
+def dump_outputs(out_dir, eng, windows, first_slot, n):
+    """What the timed step hands its caller after the last timed update, for comparing two builds output for output:
+    lm.npy       (windows, 5)     every window's cost, lambda, accepted trials, rejected trials, solve failures
+    states.npy   (S, n, 16)       the n keyframe states of the windows in states_windows.npy (dump_sample)"""
+    lm = np.array([[d["cost"], d["lam"], d["accepted"], d["rejected"], d["solve_failures"]]
+                   for d in (eng.read_lm(w) for w in range(windows))], dtype=np.float64)
+    sample = dump_sample(windows, n)
+    states = np.stack([eng.get_states(int(w), first_slot, n) for w in sample])
+    np.save(os.path.join(out_dir, "lm.npy"), lm)
+    np.save(os.path.join(out_dir, "states_windows.npy"), sample.astype(np.float64))
+    np.save(os.path.join(out_dir, "states.npy"), states)
+
+
 def write_detail(full, path=None):
     path = path or os.path.join(os.environ.get("VF_BENCH_DETAIL_DIR", ROOT), "bench_detail.json")
     try:
@@ -727,9 +752,16 @@ def main():
                     help="vf_engine_opts.solve_assemble_min of the headline engine (default: the library's)")
     ap.add_argument("--solve-assemble-waves", type=int, default=None,
                     help="vf_engine_opts.solve_assemble_waves of the headline engine (default: the library's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0's windows) as DIR/<name>.npy, float64, at "
+                         "most 64 MB: every window's LM summary and the states of a seeded sample of the windows")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs:
+        if not len(dump_sample(args.windows, args.window)):
+            ap.error(f"--dump-outputs: one window of {args.window} keyframes does not fit in {DUMP_BYTES} bytes")
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -798,6 +830,8 @@ def main():
     summaries = D.gather_summaries(dist, dict(rank=info.rank, keyframes=args.windows * args.steps))
     ingest_ms = eng.ingest_status()        # raises if any ingest of the run failed on the device; (h2d, K0 + staging) of the last one
     lm_after_timed = eng.read_lm(0)
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, eng, args.windows, args.steps + args.warmup, args.window)
     accuracy = None
     if reference is not None and reference["states"] is not None:
         done = args.steps + args.warmup

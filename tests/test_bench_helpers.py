@@ -104,3 +104,27 @@ def test_detail_file_is_written_where_asked(tmp_path, monkeypatch):
     monkeypatch.setenv("VF_BENCH_DETAIL_DIR", str(tmp_path))
     p = bench.write_detail({"a": [1, 2, 3]})
     assert json.load(open(p)) == {"a": [1, 2, 3]}
+
+
+def test_dumped_outputs_fit_the_budget_and_are_the_same_sample_every_time(tmp_path):
+    """--dump-outputs: every window's LM summary and the states of a fixed sample of windows, float64, at most 64 MB"""
+    full = bench.dump_sample(1024, 1000)                     # the default shape does not fit whole: a seeded sample
+    assert 0 < len(full) < 1024 and np.array_equal(full, bench.dump_sample(1024, 1000))
+    assert np.array_equal(full, np.unique(full)) and full.max() < 1024
+    assert np.array_equal(bench.dump_sample(8, 1000), np.arange(8)) and len(bench.dump_sample(1, 10**7)) == 0
+
+    class Eng:                                               # the two read calls of the engine dump_outputs makes
+        def read_lm(self, w):
+            return dict(cost=0.5 * w, lam=1e-3, accepted=5 + w, rejected=1, solve_failures=0)
+
+        def get_states(self, w, k0, n):
+            return np.full((n, 16), 100.0 * w + k0)
+
+    windows, n = 600, 1000
+    bench.dump_outputs(str(tmp_path), Eng(), windows, 12, n)
+    lm, states, idx = (np.load(tmp_path / f"{k}.npy") for k in ("lm", "states", "states_windows"))
+    assert sum(os.path.getsize(p) for p in tmp_path.iterdir()) <= bench.DUMP_BYTES
+    assert lm.dtype == states.dtype == idx.dtype == np.float64 and lm.shape == (windows, 5) and states.shape == (len(idx), n, 16)
+    np.testing.assert_array_equal(lm[:, 0], 0.5 * np.arange(windows))
+    np.testing.assert_array_equal(states[:, 0, 0], 100.0 * idx + 12)
+    np.testing.assert_array_equal(idx, bench.dump_sample(windows, n))
