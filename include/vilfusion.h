@@ -496,9 +496,15 @@ int vf_engine_counts(vf_engine* e, int64_t* n_imu, int64_t* n_between, int64_t* 
  * (apply_degen_function, vil_fusion/python/make_prettier_graphs.py:547-576).
  * mats: (count,6,6) row-major; pose: (count,6) [x y z roll pitch yaw] or NULL; dtype 0 = f64,
  * 1 = f32 (mats/pose/out all of that type); subset 0 = all 6x6, 1 = trans [0:3,0:3],
- * 2 = rot [3:6,3:6].  metric ids follow degen_funcs
+ * 2 = rot [3:6,3:6], 3 .. 8 = the 1x1 diagonal entry (and pose component) of x, y, z, roll, pitch,
+ * yaw (make_prettier_graphs.py:555-558).  metric ids follow degen_funcs
  * (vil_fusion/python/degeneracy_detection_functions.py:283-303) then condition_number,
- * differential_entropy.  reps/kernel_ms: optional HIP-event timing of the kernel alone. */
+ * differential_entropy, then the variants jensen_bregman_0, kullback_leibler_0pose,
+ * kullback_leibler_0cov (:184-193) and condition_cov (:247-251).  kullback_leibler needs pose;
+ * kullback_leibler_0pose ignores it (pose may be NULL).  kullback_leibler_0cov inverts the zero
+ * matrix in the reference, which raises and is caught: it is NaN for every message (y[0] = 0) and
+ * computes nothing.  condition_cov is the exact negation of condition_number.
+ * reps/kernel_ms: optional HIP-event timing of the kernel alone. */
 #define VF_METRIC_D_OPT 0
 #define VF_METRIC_D_OPT_RATIO 1
 #define VF_METRIC_A_OPT 2
@@ -520,15 +526,36 @@ int vf_engine_counts(vf_engine* e, int64_t* n_imu, int64_t* n_between, int64_t* 
 #define VF_METRIC_NORM_2_RATIO 18
 #define VF_METRIC_CONDITION_NUMBER 19
 #define VF_METRIC_DIFFERENTIAL_ENTROPY 20
+#define VF_METRIC_JENSEN_BREGMAN_0 21
+#define VF_METRIC_KULLBACK_LEIBLER_0POSE 22
+#define VF_METRIC_KULLBACK_LEIBLER_0COV 23
+#define VF_METRIC_CONDITION_COV 24
+#define VF_SUBSET_ALL 0
+#define VF_SUBSET_TRANS 1
+#define VF_SUBSET_ROT 2
+#define VF_SUBSET_X 3
+#define VF_SUBSET_Y 4
+#define VF_SUBSET_Z 5
+#define VF_SUBSET_ROLL 6
+#define VF_SUBSET_PITCH 7
+#define VF_SUBSET_YAW 8
 int vf_degeneracy_batch(const void* mats, const void* pose, int count, int dtype, int subset, int metric,
                         void* out, int reps, float* kernel_ms);
 /* extra: the three metrics that read the ends of the spectrum -- e_opt, max_eigen, condition_number
  * (degeneracy_detection_functions.py:74-82, 98-106, 239-243) -- of ONE eigen-solve per matrix, one launch, three outputs (each `count`
  * values, [0] = 0): bit for bit what three vf_degeneracy_batch calls return, at a third of the work.  condition_number is NaN for a
  * matrix that is not symmetric to rounding (its singular values are then not the moduli of its eigenvalues: ask
- * vf_degeneracy_batch, which falls back to an SVD). */
+ * vf_degeneracy_batch, which falls back to an SVD).  Subsets 3 .. 8 (1x1): e_opt = max_eigen = the entry,
+ * condition_number = -1 (-inf for a zero entry). */
 int vf_degeneracy_spectrum_batch(const void* mats, int count, int dtype, int subset, void* e_opt, void* max_eigen,
                                  void* condition_number, int reps, float* kernel_ms);
+/* Several subsets of one metric in one launch (the online node's score_all / score_trans / score_rot,
+ * vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130): every matrix is read from memory once.
+ * subset_mask: bit s = subset s (VF_SUBSET_*), bits 0 .. 8 only, at least one.  out holds
+ * popcount(subset_mask) rows of `count` values, in ascending subset id, each row bit for bit what
+ * vf_degeneracy_batch returns for that subset (row[0] = 0).  Other arguments as vf_degeneracy_batch. */
+int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, int dtype, int metric, unsigned subset_mask,
+                               void* out, int reps, float* kernel_ms);
 /* The shipped gate (gtsam_fusion/src/degerate_odometry_filter.cpp:29-47): float32 log det of the
  * rotation (3,3) and translation (0,0) 3x3 blocks of the 36-float LOAM Hessian; keep[i] = 0 when
  * either is below its threshold (fusion_params.yaml:35-36: 11.5 / 28.9). */

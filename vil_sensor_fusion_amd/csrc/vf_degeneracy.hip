@@ -1,5 +1,6 @@
-// vf_degeneracy.hip -- K6: batched degeneracy metrics on 6x6 information / covariance matrices
-// and their 3x3 translation / rotation blocks, one lane per message, everything in registers.
+// vf_degeneracy.hip -- K6: batched degeneracy metrics on 6x6 information / covariance matrices,
+// their 3x3 translation / rotation blocks and the 1x1 entry of each axis, one lane per message,
+// everything in registers; several of those subsets of one metric in one launch (k_degeneracy_scores).
 //
 // Replaces the per-message numpy/LAPACK calls of the reference's metric library
 // (vil_fusion/python/degeneracy_detection_functions.py:38-251) as driven by
@@ -432,8 +433,59 @@ DI void ratio_eig(const T (&now)[N * N], const T (&prev)[N * N], T (&ev)[N], boo
 
 enum Metric { D_OPT, D_OPT_RATIO, A_OPT, A_OPT_RATIO, E_OPT, E_OPT_RATIO, MAX_EIGEN, MAX_EIGEN_RATIO, JENSEN_BREGMAN,
               CORR_DIST, KULLBACK_LEIBLER, NORM_FRO, NORM_FRO_RATIO, NORM_NUC, NORM_NUC_RATIO, NORM_1, NORM_1_RATIO,
-              NORM_2, NORM_2_RATIO, COND_NUMBER, DIFF_ENTROPY, N_METRICS,
+              NORM_2, NORM_2_RATIO, COND_NUMBER, DIFF_ENTROPY,
+              // the variants of degeneracy_detection_functions.py:184-193, 247-251
+              JENSEN_BREGMAN_0, KL_0POSE, KL_0COV, CONDITION_COV, N_METRICS,
               SPECTRUM = N_METRICS };     // (not a metric of the reference: e_opt, max_eigen and condition_number of one eigen-solve, vf_degeneracy_spectrum_batch)
+
+// subset id -> (N, offset of the block on the diagonal): 0 all (6, 0), 1 trans (3, 0), 2 rot (3, 3), 3 + a the 1x1 entry of
+// axis a = x y z roll pitch yaw (1, a)
+constexpr int N_SUBSETS = 9;
+__host__ __device__ constexpr int subset_off(int s) { return s == 2 ? 3 : (s < 3 ? 0 : s - 3); }
+
+// numpy.linalg.cond of a 1x1: s / s = 1, and 0 / 0 -> inf (numpy turns the NaN of a singular matrix into inf)
+template <typename T>
+DI T cond_1x1(T a) { return a != a ? a : (t_abs(a) > T(0) ? T(1) : T(INFINITY)); }
+
+// numpy.linalg.det of a 1x1: numpy takes every determinant as sign * exp(log|det|) of its LU factors (slogdet), so det([[x]])
+// is x to within an ulp or two -- and the kullback_leibler of two close entries cancels down to exactly those ulps
+template <typename T>
+DI T det_1x1(T x) { return x == T(0) ? T(0) : copysign(exp(log(t_abs(x))), x); }
+
+// The reference's numpy calls on a 1x1 [[a]] (prev [[b]], pose difference du = prev - now), in closed form.  inv() of a zero
+// raises LinAlgError there: NaN here, also for the norm_*_ratio functions, which do not catch it (the reference raises).
+template <typename T, int METRIC>
+DI T metric_1x1(T a, T b, T du) {
+    const T nan = T(NAN);
+    const T r = a * (T(1) / b);          // now @ inv(prev)
+    switch (METRIC) {
+        case D_OPT: return exp(log(t_abs(a)));
+        case D_OPT_RATIO: return b != T(0) ? exp(log(t_abs(r))) : nan;
+        case A_OPT: case E_OPT: case MAX_EIGEN: case SPECTRUM: return a;
+        case A_OPT_RATIO: case E_OPT_RATIO: case MAX_EIGEN_RATIO: return b != T(0) ? r : nan;
+        case JENSEN_BREGMAN: return log(t_abs((a + b) / T(2))) - T(0.5) * det_1x1(a * b);
+        case JENSEN_BREGMAN_0: return log(t_abs(a / T(2)));
+        case CORR_DIST: return (a > T(0) && b > T(0)) ? T(0) : nan;    // both "correlations" are [[1]]
+        case KULLBACK_LEIBLER: case KL_0POSE: {
+            if (!(a != T(0) && b != T(0))) return nan;
+            const T ai = T(1) / a;
+            const T d = METRIC == KL_0POSE ? T(0) : du;
+            return T(0.5) * ((ai * b - T(1)) + d * (ai * d) + log(t_abs(det_1x1(a)) / t_abs(det_1x1(b))));
+        }
+        case KL_0COV: return nan;
+        case NORM_FRO: return t_sqrt(a * a);
+        case NORM_NUC: case NORM_1: case NORM_2: return t_abs(a);
+        case NORM_FRO_RATIO: return b != T(0) ? t_sqrt(r * r) : nan;
+        case NORM_NUC_RATIO: case NORM_1_RATIO: case NORM_2_RATIO: return b != T(0) ? t_abs(r) : nan;
+        case COND_NUMBER: return -cond_1x1(a);
+        case CONDITION_COV: return cond_1x1(a);
+        case DIFF_ENTROPY: {
+            const T d = T(2.0 * 3.141592653589793 * 2.718281828459045) * det_1x1(a);
+            return d > T(0) ? T(0.5) * log(d) : nan;
+        }
+        default: return nan;
+    }
+}
 
 template <typename T, int N>
 DI T norm1(const T (&a)[N * N]) {
@@ -458,60 +510,17 @@ DI T normfro(const T (&a)[N * N]) {
 // Which metrics read the previous message's matrix (the ratio / divergence family, make_prettier_graphs.py:565-574)
 __host__ __device__ constexpr bool metric_needs_prev(int m) {
     return m == D_OPT_RATIO || m == A_OPT_RATIO || m == E_OPT_RATIO || m == MAX_EIGEN_RATIO || m == JENSEN_BREGMAN || m == CORR_DIST ||
-           m == KULLBACK_LEIBLER || m == NORM_FRO_RATIO || m == NORM_NUC_RATIO || m == NORM_1_RATIO || m == NORM_2_RATIO;
+           m == KULLBACK_LEIBLER || m == NORM_FRO_RATIO || m == NORM_NUC_RATIO || m == NORM_1_RATIO || m == NORM_2_RATIO ||
+           m == KL_0POSE;
 }
 constexpr int MSTRIDE = 37;   // LDS stride of one 6x6 (36 + 1 pad: 64 lanes reading entry e of their own matrix hit 32 / 64 distinct banks)
 
-// mats: (T,6,6) row-major, pose (T,6) or null; off = 0 (all / trans) or 3 (rot); out[0] = 0.
-// One wave per 64 consecutive messages.  The wave's matrices (and the one in front of them, for the metrics that compare
-// with the previous message) are ONE contiguous stretch of HBM: it is copied to LDS with 16-byte loads, fully
-// coalesced, and every lane then picks its own matrix out of LDS (lane = message reads of 288-byte records straight
-// from HBM touch 64 cache lines per load instruction).  METRIC is a template parameter: a metric's kernel contains
-// only its own arithmetic and loads the previous matrix only if it uses it.
+// One metric of message i on its N x N block, N = 6 or 3 (`now`, `prev`: the block of message i and of message i - 1, the
+// identity on lanes that are not `active`); off = the block's first row / column, for the pose.  SPECTRUM also writes
+// out2 / out3.
 template <typename T, int N, int METRIC>
-__global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, const T* __restrict__ pose, int count, int off,
-                                                   T* __restrict__ out, T* __restrict__ out2 = nullptr, T* __restrict__ out3 = nullptr) {
-    // staged in two halves of 32 messages (lanes 0-31 pick theirs up after the first, 32-63 after the second): 9.8 KB of LDS
-    // per wave instead of 19.2, i.e. four waves per SIMD instead of two for the Jacobi kernels
-    __shared__ T lds[33 * MSTRIDE];
-    const int lane = threadIdx.x, base = blockIdx.x * 64;
-    const int i = base + lane;
-    constexpr bool PREV = metric_needs_prev(METRIC);
-    const bool active = i > 0 && i < count;
-    T now[N * N], prev[N * N];
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-        const int hb = base + 32 * half;                                  // first message of this half
-        if (half) __syncthreads();
-        if (hb < count) {
-            const int first = (PREV && hb > 0) ? hb - 1 : hb;            // first matrix staged, local index first - hb + 1
-            const int last = hb + 32 < count ? hb + 32 : count;
-            constexpr int V = 16 / (int)sizeof(T);                        // elements per 16-byte load (36 is a multiple of both)
-            const int nvec = (last - first) * 36 / V;
-            using vec_t = T __attribute__((ext_vector_type(V)));
-            const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
-            for (int v = lane; v < nvec; v += 64) {
-                const vec_t x = __builtin_nontemporal_load(src + v);
-                const int e = v * V, m = e / 36, r = e - m * 36;
-                T* dst = lds + (m + first - hb + 1) * MSTRIDE + r;
-#pragma unroll
-                for (int k = 0; k < V; k++) dst[k] = x[k];
-            }
-        }
-        __syncthreads();
-        if ((lane >> 5) == half) {
-            const int l = lane & 31;
-            const T* mn = lds + (l + 1) * MSTRIDE + off * 7;
-            const T* mp = lds + l * MSTRIDE + off * 7;
-#pragma unroll
-            for (int r = 0; r < N; r++)
-#pragma unroll
-                for (int c = 0; c < N; c++) {
-                    now[r * N + c] = active ? mn[r * 6 + c] : T(r == c);
-                    prev[r * N + c] = (PREV && active) ? mp[r * 6 + c] : T(r == c);
-                }
-        }
-    }
+DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __restrict__ pose, int i, int count, int off,
+                  bool active, T* __restrict__ out2, T* __restrict__ out3) {
     const T nan = T(NAN);
     T y = nan;
     constexpr bool is_ratio = METRIC == D_OPT_RATIO || METRIC == A_OPT_RATIO || METRIC == NORM_FRO_RATIO ||
@@ -585,6 +594,14 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
             matmul<T, N>(now, prev, prod);
             y = lu_logabsdet<T, N>(avg) - T(0.5) * lu_det<T, N>(prod);
         } break;
+        case JENSEN_BREGMAN_0: {   // jensen_bregman(now, 0): slogdet(now / 2)[1] - 0.5 det(now @ 0), and numpy's det of the zero
+                                   // matrix is 0 (lu_det's would be 0 * (1 / 0) = NaN: not the JENSEN_BREGMAN path with prev = 0)
+            T half[N * N];
+#pragma unroll
+            for (int k = 0; k < N * N; k++) half[k] = now[k] / T(2);
+            y = lu_logabsdet<T, N>(half);
+        } break;
+        case KL_0COV: break;       // kullback_leibler(now, 0, ...) inverts the zero matrix: LinAlgError, NaN for every message
         case CORR_DIST: {   // elementwise-product quirk: only the diagonal of the "correlation" survives
             T tr = 0, fx = 0, fy = 0;
             bool ok = true;
@@ -599,7 +616,7 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
             }
             y = ok ? T(1) - tr / (t_sqrt(fx) * t_sqrt(fy)) : nan;
         } break;
-        case KULLBACK_LEIBLER: {   // E1 = prev, E2 = now
+        case KULLBACK_LEIBLER: case KL_0POSE: {   // E1 = prev, E2 = now; KL_0POSE: pose difference 0
             T e2i[N * N], m[N * N];
             gj_inverse<T, N>(now, e2i);
             matmul<T, N>(e2i, prev, m);
@@ -608,7 +625,7 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
             for (int k = 0; k < N; k++) a += m[k * N + k] - T(1);
             T du[N], b = 0;
 #pragma unroll
-            for (int k = 0; k < N; k++) du[k] = (pose && active) ? pose[(size_t)(i - 1) * 6 + off + k] - pose[(size_t)i * 6 + off + k] : T(0);
+            for (int k = 0; k < N; k++) du[k] = (METRIC == KULLBACK_LEIBLER && pose && active) ? pose[(size_t)(i - 1) * 6 + off + k] - pose[(size_t)i * 6 + off + k] : T(0);
 #pragma unroll
             for (int r = 0; r < N; r++) {
                 T s = 0;
@@ -623,10 +640,11 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
         case NORM_FRO_RATIO: y = normfro<T, N>(ratio); break;
         case NORM_1: y = norm1<T, N>(now); break;
         case NORM_1_RATIO: y = norm1<T, N>(ratio); break;
-        case NORM_NUC: case NORM_2: case COND_NUMBER: case NORM_NUC_RATIO: case NORM_2_RATIO: {
+        case NORM_NUC: case NORM_2: case COND_NUMBER: case CONDITION_COV: case NORM_NUC_RATIO: case NORM_2_RATIO: {
             T w[N * N], sv[N];
             constexpr bool r = METRIC == NORM_NUC_RATIO || METRIC == NORM_2_RATIO;
-            if (METRIC == NORM_NUC || METRIC == NORM_2 || METRIC == COND_NUMBER) {
+            constexpr bool cond = METRIC == COND_NUMBER || METRIC == CONDITION_COV;    // CONDITION_COV = +cond, the same bits negated
+            if (METRIC == NORM_NUC || METRIC == NORM_2 || cond) {
                 // An information matrix is symmetric, and the singular values of a symmetric matrix are the moduli of its
                 // eigenvalues: sigma_max / sigma_min, the sum and the maximum come from the eigen-solve e_opt / max_eigen use, at a
                 // seventh of the cost of a Jacobi SVD.  "Symmetric" = to within rounding of the entries (an asymmetry of that
@@ -650,7 +668,7 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
                     T lo = t_abs(ev[0]), hi = t_abs(ev[0]), sum = T(0);
 #pragma unroll
                     for (int k = 0; k < N; k++) { const T x = t_abs(ev[k]); lo = x < lo ? x : lo; hi = x > hi ? x : hi; sum += x; }
-                    y = METRIC == NORM_NUC ? sum : (METRIC == COND_NUMBER ? -(hi / lo) : hi);
+                    y = METRIC == NORM_NUC ? sum : (cond ? (METRIC == COND_NUMBER ? -(hi / lo) : hi / lo) : hi);
                     break;
                 }
             }
@@ -660,7 +678,7 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
             T lo = sv[0], hi = sv[0], sum = 0;
 #pragma unroll
             for (int k = 0; k < N; k++) { lo = sv[k] < lo ? sv[k] : lo; hi = sv[k] > hi ? sv[k] : hi; sum += sv[k]; }
-            y = (METRIC == NORM_NUC || METRIC == NORM_NUC_RATIO) ? sum : ((METRIC == COND_NUMBER) ? -(hi / lo) : hi);
+            y = (METRIC == NORM_NUC || METRIC == NORM_NUC_RATIO) ? sum : (cond ? (METRIC == COND_NUMBER ? -(hi / lo) : hi / lo) : hi);
         } break;
         case DIFF_ENTROPY: {
             const T x = pow(T(2.0 * 3.141592653589793 * 2.718281828459045), T(N));
@@ -669,8 +687,155 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
         } break;
         default: break;
     }
+    return y;
+}
+
+// One metric on the N x N block of any subset: N = 1 (the per-axis subsets) takes the closed forms of metric_1x1.  Both
+// kernels below call this, so a subset computed by the fused launch is the arithmetic of the launch of that subset alone,
+// and the wave-uniform decisions inside (__all / __any of the eigen-solver and the SVD, the symmetric fast path) are taken
+// over the same 64 consecutive messages in both.
+template <typename T, int N, int METRIC>
+DI T degeneracy_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __restrict__ pose, int i, int count, int off,
+                       bool active, T* __restrict__ out2, T* __restrict__ out3) {
+    if constexpr (N == 1) {
+        const bool kl = METRIC == KULLBACK_LEIBLER && pose && active;
+        const T du = kl ? pose[(size_t)(i - 1) * 6 + off] - pose[(size_t)i * 6 + off] : T(0);
+        const T y = metric_1x1<T, METRIC>(now[0], prev[0], du);
+        if (METRIC == SPECTRUM) {     // e_opt = max_eigen = a, condition_number = -cond
+            if (i == 0) { out2[0] = T(0); out3[0] = T(0); }
+            else if (i < count) { out2[i] = y; out3[i] = -cond_1x1(y); }
+        }
+        return y;
+    } else {
+        return block_metric<T, N, METRIC>(now, prev, pose, i, count, off, active, out2, out3);
+    }
+}
+
+// the N x N block at (off, off) of the 6 x 6 staged at `m` (LDS), or the identity on a lane that is not active
+template <typename T, int N>
+DI void pick_block(const T* m, int off, bool active, T (&a)[N * N]) {
+#pragma unroll
+    for (int r = 0; r < N; r++)
+#pragma unroll
+        for (int c = 0; c < N; c++) a[r * N + c] = active ? m[off * 7 + r * 6 + c] : T(r == c);
+}
+
+// mats: (T,6,6) row-major, pose (T,6) or null; N and off from the subset (6 / 3 / 1, subset_off); out[0] = 0.
+// One wave per 64 consecutive messages.  The wave's matrices (and the one in front of them, for the metrics that compare
+// with the previous message) are ONE contiguous stretch of HBM: it is copied to LDS with 16-byte loads, fully
+// coalesced, and every lane then picks its own matrix out of LDS (lane = message reads of 288-byte records straight
+// from HBM touch 64 cache lines per load instruction).  METRIC is a template parameter: a metric's kernel contains
+// only its own arithmetic and loads the previous matrix only if it uses it.
+template <typename T, int N, int METRIC>
+__global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, const T* __restrict__ pose, int count, int off,
+                                                   T* __restrict__ out, T* __restrict__ out2 = nullptr, T* __restrict__ out3 = nullptr) {
+    // staged in two halves of 32 messages (lanes 0-31 pick theirs up after the first, 32-63 after the second): 9.8 KB of LDS
+    // per wave instead of 19.2, i.e. four waves per SIMD instead of two for the Jacobi kernels
+    __shared__ T lds[33 * MSTRIDE];
+    const int lane = threadIdx.x, base = blockIdx.x * 64;
+    const int i = base + lane;
+    constexpr bool PREV = metric_needs_prev(METRIC);
+    const bool active = i > 0 && i < count;
+    T now[N * N], prev[N * N];
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const int hb = base + 32 * half;                                  // first message of this half
+        if (half) __syncthreads();
+        if (hb < count) {
+            const int first = (PREV && hb > 0) ? hb - 1 : hb;            // first matrix staged, local index first - hb + 1
+            const int last = hb + 32 < count ? hb + 32 : count;
+            constexpr int V = 16 / (int)sizeof(T);                        // elements per 16-byte load (36 is a multiple of both)
+            const int nvec = (last - first) * 36 / V;
+            using vec_t = T __attribute__((ext_vector_type(V)));
+            const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
+            for (int v = lane; v < nvec; v += 64) {
+                const vec_t x = __builtin_nontemporal_load(src + v);
+                const int e = v * V, m = e / 36, r = e - m * 36;
+                T* dst = lds + (m + first - hb + 1) * MSTRIDE + r;
+#pragma unroll
+                for (int k = 0; k < V; k++) dst[k] = x[k];
+            }
+        }
+        __syncthreads();
+        if ((lane >> 5) == half) {
+            const int l = lane & 31;
+            pick_block<T, N>(lds + (l + 1) * MSTRIDE, off, active, now);
+            pick_block<T, N>(lds + l * MSTRIDE, off, PREV && active, prev);
+        }
+    }
+    const T y = degeneracy_metric<T, N, METRIC>(now, prev, pose, i, count, off, active, out2, out3);
     if (i == 0) out[0] = T(0);            // make_prettier_graphs.py:562-563
     else if (i < count) out[i] = y;
+}
+
+// Several subsets of one metric in one launch (the online node's score_all / score_trans / score_rot of one message,
+// vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130): the wave's 64 matrices (and the one before them) are staged
+// into LDS ONCE, as k_degeneracy stages them, and every subset set in `mask` is then evaluated from that image, one
+// after another (subsets in sequence, not interleaved: the registers are those of the largest one).  out: one row of
+// `count` values per subset in the mask, in ascending subset id.  All 65 matrices stay in LDS for the whole launch
+// (19.2 KB per wave in float64), so all the loads are issued before the first is waited for.
+template <typename T, int METRIC>
+__global__ void __launch_bounds__(64) k_degeneracy_scores(const T* __restrict__ mats, const T* __restrict__ pose, int count,
+                                                          unsigned mask, T* __restrict__ out) {
+    __shared__ T lds[65 * MSTRIDE];
+    const int lane = threadIdx.x, base = blockIdx.x * 64;
+    const int i = base + lane;
+    constexpr bool PREV = metric_needs_prev(METRIC);
+    const bool active = i > 0 && i < count;
+    {
+        const int first = (PREV && base > 0) ? base - 1 : base;           // first matrix staged, local index first - base + 1
+        const int last = base + 64 < count ? base + 64 : count;
+        constexpr int V = 16 / (int)sizeof(T);
+        constexpr int PER = (65 * 36 / V + 63) / 64;                       // 16-byte loads per lane at most
+        const int nvec = (last - first) * 36 / V;
+        using vec_t = T __attribute__((ext_vector_type(V)));
+        const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
+        vec_t x[PER];
+#pragma unroll
+        for (int k = 0; k < PER; k++)
+            if (lane + 64 * k < nvec) x[k] = __builtin_nontemporal_load(src + lane + 64 * k);
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int v = lane + 64 * k;
+            if (v < nvec) {
+                const int e = v * V, m = e / 36, r = e - m * 36;
+                T* dst = lds + (m + first - base + 1) * MSTRIDE + r;
+#pragma unroll
+                for (int j = 0; j < V; j++) dst[j] = x[k][j];
+            }
+        }
+    }
+    __syncthreads();
+    const T* mn = lds + (lane + 1) * MSTRIDE;
+    const T* mp = lds + lane * MSTRIDE;
+    T* o = out;
+    auto put = [&](T y) {
+        if (i == 0) o[0] = T(0);
+        else if (i < count) o[i] = y;
+        o += count;
+    };
+    if (mask & 1u) {
+        T now[36], prev[36];
+        pick_block<T, 6>(mn, 0, active, now);
+        pick_block<T, 6>(mp, 0, PREV && active, prev);
+        put(degeneracy_metric<T, 6, METRIC>(now, prev, pose, i, count, 0, active, nullptr, nullptr));
+    }
+#pragma unroll 1
+    for (int s = 1; s < 3; s++)
+        if (mask >> s & 1u) {
+            T now[9], prev[9];
+            pick_block<T, 3>(mn, subset_off(s), active, now);
+            pick_block<T, 3>(mp, subset_off(s), PREV && active, prev);
+            put(degeneracy_metric<T, 3, METRIC>(now, prev, pose, i, count, subset_off(s), active, nullptr, nullptr));
+        }
+#pragma unroll 1
+    for (int s = 3; s < N_SUBSETS; s++)
+        if (mask >> s & 1u) {
+            T now[1], prev[1];
+            pick_block<T, 1>(mn, subset_off(s), active, now);
+            pick_block<T, 1>(mp, subset_off(s), PREV && active, prev);
+            put(degeneracy_metric<T, 1, METRIC>(now, prev, pose, i, count, subset_off(s), active, nullptr, nullptr));
+        }
 }
 
 template <typename T, int N>
@@ -679,12 +844,26 @@ void launch_degeneracy(int metric, dim3 grid, const T* m, const T* p, int count,
     switch (metric) {
         VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
         VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
-        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20)
+        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
+        VF_K6_CASE(24)
         default: break;
     }
 #undef VF_K6_CASE
 }
-static_assert(N_METRICS == 21, "launch_degeneracy lists every metric");
+
+template <typename T>
+void launch_degeneracy_scores(int metric, dim3 grid, const T* m, const T* p, int count, unsigned mask, T* o) {
+#define VF_K6_CASE(M) case M: hipLaunchKernelGGL((k_degeneracy_scores<T, M>), grid, dim3(64), 0, 0, m, p, count, mask, o); break;
+    switch (metric) {
+        VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
+        VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
+        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
+        VF_K6_CASE(24)
+        default: break;
+    }
+#undef VF_K6_CASE
+}
+static_assert(N_METRICS == 25, "launch_degeneracy and launch_degeneracy_scores list every metric");
 
 template <typename T>
 int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_max, void* o_cond, int reps, float* kernel_ms);
@@ -733,14 +912,15 @@ int run_batch(const void* mats, const void* pose, int count, int subset, int met
         HIPCHK(hipMalloc((void**)&d_p, pb));
         HIPCHK(hipMemcpy(d_p, pose, pb, hipMemcpyHostToDevice));
     }
-    const int off = subset == 2 ? 3 : 0;
+    const int off = subset_off(subset);
     const dim3 grid((count + 63) / 64);
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     auto launch = [&]() {
         if (subset == 0) launch_degeneracy<T, 6>(metric, grid, d_m, d_p, count, off, d_o);
-        else launch_degeneracy<T, 3>(metric, grid, d_m, d_p, count, off, d_o);
+        else if (subset < 3) launch_degeneracy<T, 3>(metric, grid, d_m, d_p, count, off, d_o);
+        else launch_degeneracy<T, 1>(metric, grid, d_m, d_p, count, off, d_o);
     };
     launch();
     HIPCHK(hipDeviceSynchronize());
@@ -768,11 +948,12 @@ int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_m
     HIPCHK(hipMalloc((void**)&d_m, mb));
     HIPCHK(hipMalloc((void**)&d_o, 3 * ob));
     HIPCHK(hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice));
-    const int off = subset == 2 ? 3 : 0;
+    const int off = subset_off(subset);
     const dim3 grid((count + 63) / 64);
     auto launch = [&]() {
         if (subset == 0) hipLaunchKernelGGL((k_degeneracy<T, 6, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
-        else hipLaunchKernelGGL((k_degeneracy<T, 3, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
+        else if (subset < 3) hipLaunchKernelGGL((k_degeneracy<T, 3, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
+        else hipLaunchKernelGGL((k_degeneracy<T, 1, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
     };
     launch();
     HIPCHK(hipDeviceSynchronize());
@@ -797,6 +978,42 @@ int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_m
     return VF_OK;
 }
 
+template <typename T>
+int run_scores(const void* mats, const void* pose, int count, int metric, unsigned mask, void* out, int reps, float* kernel_ms) {
+    T *d_m = nullptr, *d_p = nullptr, *d_o = nullptr;
+    const int rows = __builtin_popcount(mask);
+    const size_t mb = (size_t)count * 36 * sizeof(T), pb = (size_t)count * 6 * sizeof(T), ob = (size_t)rows * count * sizeof(T);
+    HIPCHK(hipMalloc((void**)&d_m, mb));
+    HIPCHK(hipMalloc((void**)&d_o, ob));
+    HIPCHK(hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice));
+    if (pose) {
+        HIPCHK(hipMalloc((void**)&d_p, pb));
+        HIPCHK(hipMemcpy(d_p, pose, pb, hipMemcpyHostToDevice));
+    }
+    const dim3 grid((count + 63) / 64);
+    auto launch = [&]() { launch_degeneracy_scores<T>(metric, grid, d_m, d_p, count, mask, d_o); };
+    launch();
+    HIPCHK(hipDeviceSynchronize());
+    if (kernel_ms && reps > 0) {
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; r++) launch();
+        HIPCHK(hipEventRecord(e1, 0));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        *kernel_ms = ms / reps;
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
+    (void)hipFree(d_m); (void)hipFree(d_o);
+    if (d_p) (void)hipFree(d_p);
+    return VF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -804,7 +1021,7 @@ extern "C" {
 int vf_degeneracy_spectrum_batch(const void* mats, int count, int dtype, int subset, void* e_opt, void* max_eigen, void* condition_number,
                                  int reps, float* kernel_ms) {
     if (!mats || !e_opt || !max_eigen || !condition_number || count < 0) return derr(VF_ERR_INVALID, "null argument");
-    if (subset < 0 || subset > 2) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans) or 2 (rot)");
+    if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
     if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
     if (count == 0) return VF_OK;
     int ndev = 0;
@@ -817,7 +1034,7 @@ int vf_degeneracy_batch(const void* mats, const void* pose, int count, int dtype
                         int reps, float* kernel_ms) {
     if (!mats || !out || count < 0) return derr(VF_ERR_INVALID, "null argument");
     if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
-    if (subset < 0 || subset > 2) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans) or 2 (rot)");
+    if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
     if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
     if (metric == KULLBACK_LEIBLER && !pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
     if (count == 0) return VF_OK;
@@ -825,6 +1042,20 @@ int vf_degeneracy_batch(const void* mats, const void* pose, int count, int dtype
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
     return dtype == 0 ? run_batch<double>(mats, pose, count, subset, metric, out, reps, kernel_ms)
                       : run_batch<float>(mats, pose, count, subset, metric, out, reps, kernel_ms);
+}
+
+int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, int dtype, int metric, unsigned subset_mask, void* out,
+                               int reps, float* kernel_ms) {
+    if (!mats || !out || count < 0) return derr(VF_ERR_INVALID, "null argument");
+    if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
+    if (subset_mask == 0 || (subset_mask >> N_SUBSETS) != 0) return derr(VF_ERR_INVALID, "subset_mask 0x%x: bits 0 .. 8, at least one", subset_mask);
+    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
+    if (metric == KULLBACK_LEIBLER && !pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
+    if (count == 0) return VF_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    return dtype == 0 ? run_scores<double>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms)
+                      : run_scores<float>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms);
 }
 
 int vf_dopt_filter_f32(const float* hessians, int count, float rot_thr, float trans_thr, float* rot_dopt,
