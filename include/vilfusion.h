@@ -469,6 +469,23 @@ int vf_engine_read_delta(vf_engine* e, int window, int k0, int n, double* delta1
  * rows of L in the keyframe's 15 columns for [k+1:15][k+2:pose 6][k+3:pose 6] (27 rows), the
  * forward-substituted rhs row (1), and L_kk^-T (15 rows, upper triangular). */
 int vf_engine_read_panels(vf_engine* e, int window, int k0, int n, double* panels688);
+/* Marginal covariances of every window's keyframes (no reference code: the counterpart of ISAM2::marginalCovariance /
+ * gtsam::Marginals).  Enqueues, for every window: linearisation at the current states (what vf_engine_get_states returns: the
+ * estimate of an LM engine, the linearisation points theta of a reference-compat one), assembly, a whole-window forward sweep
+ * with lambda = 0 (forms 0-3 of vf_engine_solve_form; an engine whose solves are partitioned sweeps whole windows here), and
+ * selected inversion of its panels (K4s, the block form of Takahashi's recursion).  The LM state is left as it was -- states,
+ * increments, lambda, counters, done flags, sticky words, the cached result block -- and the engine is marked cold (the next
+ * vf_engine_iterate gives the bits it would have given without the call); vf_engine_read_panels returns the undamped panels
+ * afterwards.  Refused with VF_ERR_INVALID: time-sharded engines, and engines with far factors alive in any window, linear ones
+ * included (vf_engine_get_extra_between, vf_engine_get_linear_far).  The blocks live in a device array of 2.7 KB per keyframe
+ * slot, allocated by the first call. */
+int vf_engine_marginals(vf_engine* e);
+/* ... read back (synchronises): for keyframes k0 .. k0+n-1 of the range the last vf_engine_marginals saw, Sigma_kk (full
+ * symmetric 15x15, row-major) and the cross block Sigma_{k+1,k} (15x15, row = dof of k+1, column = dof of k; zero for the window's
+ * last keyframe).  Tangent order [omega, v] of Pose3, velocity, bias [acc, gyro].  Either pointer may be NULL.  VF_ERR_NOT_SPD:
+ * the window's undamped normal equations are not positive definite; VF_ERR_INVALID: no vf_engine_marginals since the engine was
+ * made or compacted; VF_ERR_BAD_KEY: outside that range. */
+int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* cov225, double* cross225);
 int vf_engine_read_lm(vf_engine* e, int window, double* cost, double* lambda, int* accepted,
                       int* rejected, int* solve_failures);
 /* non-monotone LM: trials kept provisionally so far (not counted in accepted / rejected), and whether an excursion is open */
@@ -652,6 +669,20 @@ int vf_most_recent_pose_time(vf_graph* g, double* time, uint64_t* key);
 int vf_get_most_recent_estimate(vf_graph* g, double q[4], double t[3], double v[3]);
 /* GraphManager::addOptimizationCallback (GraphManager.cpp:96-99) */
 int vf_set_callback(vf_graph* g, vf_callback cb, void* user);
+/* ISAM2::marginalCovariance(X(key)) (no reference call: the reference never asks for it) -- the 15x15 marginal covariance of a
+ * solved key (tangent order [omega, v] of Pose3, velocity, bias [acc, gyro]; reference-compat handles: at the linearisation
+ * points, as iSAM2 factors it).  The first call after a solve computes the window's covariances (vf_engine_marginals), later ones
+ * read them; vf_solve and vf_set_initial_state void them.  VF_ERR_INVALID before the first solve and while far factors are alive;
+ * VF_ERR_BAD_KEY for a key not solved yet or marginalised out of the window.  Takes the state lock like vf_get_state: never call it
+ * from inside a callback. */
+int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
+/* the callback of vf_set_callback plus the marginal covariance of the solved keyframe */
+typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
+                                const double bias[6], const double cov225[225]);
+/* Only while one is registered does vf_solve compute covariances: after the result read, before the callbacks (which run inside the
+ * state lock as the plain ones do).  If they cannot be had (far factors alive, undamped system not positive definite) the covariance
+ * callbacks receive NaN and vf_last_error says why; the solve itself succeeds. */
+int vf_set_covariance_callback(vf_graph* g, vf_cov_callback cb, void* user);
 /* GraphManager::graph()->size(): factors staged since the last solve (3 priors at start +
  * between factors; IMU factors wait in the queue, GraphManager.cpp:66,150) and the queue length */
 int vf_graph_staged(vf_graph* g, int* staged_factors, int* queued_imu_factors);

@@ -264,6 +264,7 @@ void vf_engine_destroy(vf_engine* e) {
     if (e->res_host) (void)hipHostFree(e->res_host);
     if (e->x_gtmp) (void)hipFree(e->x_gtmp);
     if (e->x_Z) (void)hipFree(e->x_Z);
+    if (e->sig) (void)hipFree(e->sig);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream && e->own_stream) (void)hipStreamDestroy(e->stream);

@@ -282,6 +282,7 @@ int vf_engine_compact(vf_engine* e, int shift) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
     vf::View& v = e->v;
     if (shift <= 0 || shift % 64 != 0 || shift >= v.M) return fail(VF_ERR_INVALID, "shift must be a positive multiple of 64 below the capacity");
+    e->sig_valid = false;       // (the covariance blocks stay in the slots they were computed for)
     for (int w = 0; w < v.B; w++)
         if (e->h_lo[w] < shift) return fail(VF_ERR_BAD_KEY, "window %d: lo %d < shift %d (live keyframes would be lost)", w, e->h_lo[w], shift);
     const size_t keepk = (size_t)(v.M - shift);              // slots kept per window

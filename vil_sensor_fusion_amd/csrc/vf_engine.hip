@@ -359,6 +359,15 @@ struct vf_engine {
             (rc = alloc(&v.n_prov, (size_t)v.B)) || (rc = alloc(&v.relin, (size_t)v.B)) || (rc = alloc(&v.carry, (size_t)v.B))) return rc;
         return VF_OK;
     }
+    // marginal covariances (engine/engine_marginals.inc): [G][SIG_SLOT] blocks + per-window failure flags, a zero lambda and
+    // all-ones `fresh` flags for the undamped factorisation, one allocation made by the first vf_engine_marginals; sig_lo /
+    // sig_hi: the ranges the blocks were computed for
+    double* sig = nullptr;
+    double* sig_zero = nullptr;
+    int *sig_fail = nullptr, *sig_ones = nullptr;
+    long sig_G = 0;
+    bool sig_valid = false;
+    std::vector<int> sig_lo, sig_hi;
     int ensure_stage(size_t bytes) {
         if (bytes <= stage_bytes) return VF_OK;
         if (stage) HIPCHK(hipFree(stage));
@@ -395,4 +404,5 @@ extern "C" {
 #include "engine/engine_compat.inc"
 #include "engine/engine_window.inc"
 #include "engine/engine_read.inc"
+#include "engine/engine_marginals.inc"
 }  // extern "C"

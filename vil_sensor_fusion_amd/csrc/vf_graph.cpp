@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -114,6 +115,9 @@ struct vf_graph {
     int lo = 0;               // slot of the oldest keyframe in the window
     uint64_t key_base = 0;    // slot = key - key_base (advances by multiples of 64 on compaction)
     std::vector<std::pair<vf_callback, void*>> callbacks;
+    std::vector<std::pair<vf_cov_callback, void*>> cov_callbacks;
+    bool solved_once = false;   // a vf_solve has succeeded
+    bool cov_valid = false;     // the engine holds the covariances of the window as the last solve left it (vf_engine_marginals)
 };
 
 extern "C" {
@@ -260,6 +264,7 @@ int vf_set_initial_state(vf_graph* g, const double state16[16]) {
     int rc;
     if ((rc = vf_engine_set_states(g->eng, 0, 0, 1, st)) || (rc = vf_engine_set_prior(g->eng, 0, 0, rec))) return rc;
     memcpy(g->state, st, sizeof(st));
+    g->cov_valid = false;
     memcpy(g->anchor, st, sizeof(st));
     return VF_OK;
 }
@@ -486,6 +491,24 @@ int vf_graph_get_staged(vf_graph* g, int index, int* kind, uint64_t* key1, uint6
     return VF_OK;
 }
 
+// (weak: the handle is also linked against a device-free engine double that predates these two -- tests/native/fake_engine.cpp;
+// in libvilfusion.so they are always defined)
+#pragma weak vf_engine_marginals
+#pragma weak vf_engine_read_marginals
+// the covariance of a solved key; the caller holds state_mutex
+static int marginal_covariance(vf_graph* g, uint64_t key, double* cov225) {
+    if (!vf_engine_marginals || !vf_engine_read_marginals) return gerr(VF_ERR_INVALID, "this engine has no marginal covariances");
+    if (!g->solved_once) return gerr(VF_ERR_INVALID, "no solve yet: there is no covariance to report");
+    if (key > g->solved_key) return gerr(VF_ERR_BAD_KEY, "key %llu not solved yet (last solved key %llu)", (unsigned long long)key, (unsigned long long)g->solved_key);
+    if (key < g->key_base + (uint64_t)g->lo)
+        return gerr(VF_ERR_BAD_KEY, "key %llu has left the window (oldest key %llu)", (unsigned long long)key, (unsigned long long)(g->key_base + (uint64_t)g->lo));
+    if (!g->cov_valid) {
+        if (int rc = vf_engine_marginals(g->eng)) return rc;
+        g->cov_valid = true;
+    }
+    return vf_engine_read_marginals(g->eng, 0, (int)(key - g->key_base), 1, cov225, nullptr);
+}
+
 int vf_solve(vf_graph* g) {
     if (!g) return gerr(VF_ERR_INVALID, "null argument");
     static const bool timing = getenv("VF_SOLVE_TIMING") != nullptr;
@@ -554,6 +577,7 @@ int vf_solve(vf_graph* g) {
     auto give_back = [&](int code) { requeue = true; return code; };
     auto locked = [&]() -> int {
     std::lock_guard<std::mutex> sl(g->state_mutex);  // :117
+    g->cov_valid = false;
     int rc;
     // host-side validation first: a between factor whose source keyframe has already left the fixed-lag window (late
     // odometry) can never be added; it is dropped, the rest is given back, and the caller is told once
@@ -737,8 +761,15 @@ int vf_solve(vf_graph* g) {
     if (flags & 1) return gerr(VF_ERR_NOT_SPD, "preintegrated covariance not positive definite");
     if (flags & 6) return gerr(VF_ERR_INDETERMINATE, "marginalisation: %s not positive definite", (flags & 4) ? "the far ends' block of the marginal" : "pivot block of the oldest keyframe");
     g->solved_key = last_key;
+    g->solved_once = true;
+    // covariance callbacks (no reference code): the marginal covariance of the solved keyframe, computed only while one is registered
+    double cov[225];
+    if (!g->cov_callbacks.empty() && marginal_covariance(g, last_key, cov) != VF_OK)
+        for (double& c : cov) c = std::numeric_limits<double>::quiet_NaN();
     for (auto& cb : g->callbacks)  // :135-138, on the solving thread, inside _stateMutex
         cb.first(cb.second, last_time, g->state, g->state + 4, g->state + 7, g->state + 10);
+    for (auto& cb : g->cov_callbacks)
+        cb.first(cb.second, last_time, g->state, g->state + 4, g->state + 7, g->state + 10, cov);
     // a full fixed-lag window marginalises its oldest keyframe at the next update, from the linearisation this solve leaves:
     // have the device compute that marginal prior now, behind the solve, instead of in front of the next one
     if (g->opts.lag > 0 && !g->opts.synchronous_staging && last_slot + 1 - g->lo >= g->opts.lag) (void)vf_engine_marginalize_ahead(g->eng);
@@ -782,6 +813,19 @@ int vf_get_state(vf_graph* g, double q[4], double t[3], double v[3], double bias
     if (t) memcpy(t, g->state + 4, sizeof(double) * 3);
     if (v) memcpy(v, g->state + 7, sizeof(double) * 3);
     if (bias) memcpy(bias, g->state + 10, sizeof(double) * 6);
+    return VF_OK;
+}
+
+int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]) {
+    if (!g || !cov225) return gerr(VF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(g->state_mutex);
+    return marginal_covariance(g, key, cov225);
+}
+
+int vf_set_covariance_callback(vf_graph* g, vf_cov_callback cb, void* user) {
+    if (!g || !cb) return gerr(VF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(g->state_mutex);
+    g->cov_callbacks.emplace_back(cb, user);
     return VF_OK;
 }
 

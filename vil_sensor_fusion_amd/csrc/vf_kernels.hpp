@@ -317,6 +317,12 @@ void launch_assemble_window(const View& v, int window, hipStream_t s);   // H an
 void launch_assemble_for_partitioned(const View& v, hipStream_t s);   // hybrid solves with an assembling sweep (asm_in_hybrid)
 void launch_band_solve(const View& v, hipStream_t s);
 void launch_count_active(const View& v, hipStream_t s);
+// marginal covariances (vf_engine_marginals): the forward sweep alone (one wave per window; assembling: the sweep forms H itself),
+// then selected inversion of its panels into sig ([G][SIG_SLOT]: Sigma_kk lower triangle, Sigma_{k+1,k}); windows flagged in
+// `failed` are skipped
+constexpr int SIG_SLOT = 120 + 225;
+void launch_band_factor(const View& v, bool assembling, hipStream_t s);
+void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s);
 // hybrid K4 (see View::gate): vp = the same engine viewed with the partitioned form's chunk count
 void launch_band_solve_hybrid(const View& v, const View& vp, hipStream_t s);
 void launch_retract(const View& v, hipStream_t s);

@@ -371,6 +371,19 @@ class Engine:
         check(self._l.vf_engine_read_panels(self._h, window, k0, n, _d(p)))
         return p
 
+    def marginals(self):
+        """Enqueue the marginal covariances of every window's keyframes at the current states (vf_engine_marginals): undamped
+        factorisation + selected inversion.  Leaves the LM state as it was; read them with read_marginals."""
+        check(self._l.vf_engine_marginals(self._h))
+
+    def read_marginals(self, window, k0, n, cross=False):
+        """Sigma_kk of keyframes k0 .. k0+n-1 as (n, 15, 15); with cross=True also Sigma_{k+1,k} (n, 15, 15), row = dof of k+1.
+        Tangent order [omega, v] of Pose3, velocity, bias [acc, gyro]."""
+        cov = np.zeros((n, 15, 15))
+        x = np.zeros((n, 15, 15)) if cross else None
+        check(self._l.vf_engine_read_marginals(self._h, window, k0, n, _d(cov), _d(x) if cross else None))
+        return (cov, x) if cross else cov
+
     def read_lm(self, window):
         cost, lam = C.c_double(), C.c_double()
         acc, rej, fails = C.c_int(), C.c_int(), C.c_int()

@@ -128,6 +128,23 @@ class GraphManager:
         self._cbs.append(cb)
         check(self._l.vf_set_callback(self._h, cb, None))
 
+    def addCovarianceCallback(self, callback):
+        """callback(time, q_wxyz, t, v, bias, cov15x15): the optimisation callback plus the marginal covariance of the solved
+        keyframe (vf_set_covariance_callback).  While one is registered every solve computes covariances."""
+        def tramp(_user, time, q, t, v, b, cov):
+            callback(time, np.array(q[:4]), np.array(t[:3]), np.array(v[:3]), np.array(b[:6]),
+                     np.array(cov[:225]).reshape(15, 15))
+        cb = _lib.COV_CALLBACK(tramp)
+        self._cbs.append(cb)
+        check(self._l.vf_set_covariance_callback(self._h, cb, None))
+
+    def marginalCovariance(self, key):
+        """ISAM2::marginalCovariance(X(key)): the 15x15 covariance of a solved key in the tangent order [omega, v, velocity,
+        bias acc, bias gyro] (vf_get_marginal_covariance)."""
+        cov = np.zeros((15, 15))
+        check(self._l.vf_get_marginal_covariance(self._h, C.c_uint64(key), _d(cov)))
+        return cov
+
     def getState(self):
         q, t, v, b = np.zeros(4), np.zeros(3), np.zeros(3), np.zeros(6)
         check(self._l.vf_get_state(self._h, _d(q), _d(t), _d(v), _d(b)))

@@ -92,7 +92,12 @@ class FusionNode:
         self.pub = rospy.Publisher("~odometry", msgs.Odometry, queue_size=1)             # gtsam_fusion_node.cpp:58
         self.broadcaster = tf2_ros.TransformBroadcaster()
         self.static_frame, self.odom_frame = P("tf/static_frame"), P("tf/odom_frame")    # :61-62
-        self.graph.addOptimizationCallback(self.publish)                                 # :64
+        # ~publish_covariance (no reference twin; default false: the messages stay as the reference publishes them, with zero
+        # covariances): every solve computes the solved keyframe's marginal covariance and fills pose / twist covariance
+        if bool(P("publish_covariance", False)):
+            self.graph.addCovarianceCallback(self.publish_with_covariance)
+        else:
+            self.graph.addOptimizationCallback(self.publish)                             # :64
 
     def _serialised(self, fn):
         """fn under the node's lock.  VF_ERR_CAPACITY from a callback (no keyframe slot left with solver/capacity fixed, or a
@@ -121,9 +126,18 @@ class FusionNode:
         a, w = m.linear_acceleration, m.angular_velocity
         self.graph.addIMUMeasurement(m.header.stamp.to_sec(), [a.x, a.y, a.z], [w.x, w.y, w.z])
 
-    def publish(self, time, q, p, v, bias):                                              # gtsam_fusion_node.cpp:64-98
+    def publish_with_covariance(self, time, q, p, v, bias, cov15):
+        """publish() with pose.covariance / twist.covariance from the keyframe's marginal covariance (covariance.py)"""
+        from ..covariance import ros_pose_covariance
+        pose36, twist36 = ros_pose_covariance(q, cov15)
+        self.publish(time, q, p, v, bias, covariance=(pose36, twist36))
+
+    def publish(self, time, q, p, v, bias, covariance=None):                             # gtsam_fusion_node.cpp:64-98
         stamp = self.rospy.Time.from_sec(time)
         o = self.msgs.Odometry()
+        if covariance is not None:
+            o.pose.covariance = [float(x) for x in covariance[0]]
+            o.twist.covariance = [float(x) for x in covariance[1]]
         o.header.stamp, o.header.frame_id, o.child_frame_id = stamp, self.static_frame, self.odom_frame
         o.pose.pose.position.x, o.pose.pose.position.y, o.pose.pose.position.z = (float(x) for x in p)
         (o.pose.pose.orientation.w, o.pose.pose.orientation.x, o.pose.pose.orientation.y,
