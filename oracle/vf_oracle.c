@@ -81,7 +81,7 @@ static void setblk(double* M, int ld, int r0, int c0, const double* B, int br, i
 
 /* ------------------------------------------------------------------ series coefficients */
 /* x = theta^2.  A=sin/th, B=(1-cos)/th^2, C=(th-sin)/th^3, dB=B'(th)/th, dC=C'(th)/th,
- * E = 1/th^2 - (1+cos)/(2 th sin)  (coefficient of W^2 in J_r^{-1}). */
+ * E = 1/th^2 - cot(th/2)/(2 th)  (coefficient of W^2 in J_r^{-1}). */
 #define SERIES_X 0.25
 
 static void coef_ABC(double x, double* A, double* B, double* C) {
@@ -112,8 +112,9 @@ static double coef_E(double x) {
         /* sum |B_2n| x^(n-1) / (2n)! */
         return 1.0 / 12 + x * (1.0 / 720 + x * (1.0 / 30240 + x * (1.0 / 1209600 + x * (1.0 / 47900160 + x * (691.0 / 1307674368000.0 + x * (1.0 / 74724249600.0 + x * (3617.0 / 10670622842880000.0)))))));
     }
-    double th = sqrt(x);
-    return 1.0 / x - (1.0 + cos(th)) / (2.0 * th * sin(th));
+    /* half-angle form of (1+cos)/(2 th sin) = cot(th/2)/(2 th): 1+cos cancels as th -> pi, cos(th/2) does not */
+    double th = sqrt(x), h = 0.5 * th;
+    return 1.0 / x - cos(h) / (2.0 * th * sin(h));
 }
 
 /* ------------------------------------------------------------------ SO(3) */

@@ -1,0 +1,477 @@
+"""-m gpu: the device's SO(3) / SE(3) helpers (csrc/vf_math.hpp) and the kernels built on them at large rotation angles,
+against the mpmath reference (tests/mp_lie.py) and the CPU oracle.
+
+The suite's other windows turn by at most ~0.1 rad per factor, so the closed-form halves of coef_abc / coef_dbdc / coef_e /
+coef_de (x = theta^2 >= 0.25) never ran on the device.  Here:
+  * a probe (tests/native/vf_math_probe.hip, compiled with the library's CXXFLAGS) evaluates every helper over the edge
+    angles of mp_lie.EDGE_ANGLES and a dense sweep of x in [0, (2 pi - 0.1)^2];
+  * K0, K1, K2 / K2b, K3 (both solver forms), K5's retract and k_predict run on windows built so that preintegrated
+    rotations, rotation residuals, prior errors and solved increments take those angles.
+Tolerances are in ulps of the output's scale, each with its reason; factor blocks keep test_gpu_parity's 1e-12 * max|block|."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import helpers
+from tests import mp_lie as M
+from tests.test_lie_edges_host import pim_record, rand_q
+from vil_sensor_fusion_amd import Engine, EngineOpts, synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "vil_sensor_fusion_amd", "csrc")
+EPS = np.finfo(np.float64).eps
+TOL = 1e-12
+SERIES_X = 0.25
+G = np.array([0.0, 0.0, -9.81])
+BHAT = np.array([0.02, -0.01, 0.03, 0.01, -0.02, 0.005])
+
+
+def relerr(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(b).max(), 1e-300))
+
+
+# ------------------------------------------------------------------------------------------------ the probe
+def library_build_flags():
+    """(hipcc, CXXFLAGS) exactly as csrc/Makefile compiles the library"""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    var = {k: re.search(rf"^{k} \?= (.*)$", mk, re.M).group(1).strip() for k in ("HIPCC", "ARCH", "CXXFLAGS")}
+    return var["HIPCC"], var["CXXFLAGS"].replace("$(ARCH)", var["ARCH"]).split()
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    hipcc, flags = library_build_flags()
+    assert {"-O3", "-ffp-contract=fast", "--offload-arch=gfx950"} <= set(flags), flags
+    so = str(tmp_path_factory.mktemp("vf_math_probe") / "vf_math_probe.so")
+    p = subprocess.run([hipcc, *flags, "-shared", "-I", CSRC, os.path.join(ROOT, "tests", "native", "vf_math_probe.hip"), "-o", so],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lib = C.CDLL(so)
+    lib.vf_math_probe.restype = C.c_int
+
+    def run(inp):
+        inp = np.ascontiguousarray(inp, dtype=np.float64).reshape(-1, 17)
+        out = np.zeros((inp.shape[0], 72))
+        rc = lib.vf_math_probe(inp.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(inp.shape[0]), out.ctypes.data_as(C.POINTER(C.c_double)))
+        assert rc == 0, f"hip error {rc}"
+        return out
+    return run
+
+
+COEFS = ["A", "B", "C", "dB", "dC", "E", "dE"]
+OUT = dict(qexp=slice(7, 11), qlog=slice(11, 14), jr=slice(14, 23), jr_inv=slice(23, 32), dexp=slice(32, 41),
+           log_w=slice(41, 44), log_u=slice(44, 47), exp_q=slice(47, 51), exp_t=slice(51, 54), Jw=slice(54, 63), Q2=slice(63, 72))
+# the largest term each closed form divides down from (x >= SERIES_X): A = s/th, B = (1-c)/x, C = (1-A)/x, dB = (A-2B)/x,
+# dC = (B-3C)/x, E = 1/x - ..., dE = ((1+A)/(2B) - 2)/x^2
+TERM_POWER = dict(A=0.5, B=1, C=1, dB=2, dC=2, E=1, dE=2)
+
+
+def print_table(title, worst):
+    print(f"\n{title} (worst error in ulps of the output's scale)")
+    bands = sorted({b for v in worst.values() for b in v})
+    print(" " * 10 + "".join(f"{b:>24}" for b in bands))
+    for name, v in worst.items():
+        print(f"{name:>10}" + "".join(f"{v.get(b, float('nan')):>24.2f}" for b in bands))
+
+
+def test_probe_coefficients_dense_sweep(probe):
+    """A, B, C, dB, dC, E, dE at 3 000 x in [0, (2 pi - 0.1)^2], the squares of the edge angles and both neighbours of
+    the switch.  Bounds: Horner branch 16 ulps of |value| (the dB and dE series stop at x^5 / x^6: their truncation reaches
+    9 and 13 ulps just below x = 0.25 on the device, the others stay below 3); closed form
+    16 ulps of the largest term it divides down from (1/x^p), since that term's rounding is what survives the cancellation.
+    Both add eps * |theta f'(theta)|: the reference takes sqrt(x) exactly, the device rounds it once.
+    dE is the one coefficient whose closed form loses digits next to the switch (6e-12 relative at x = 0.26, all inside the
+    16-ulp bound of 2/x^2): it scales the dE (w.u) W^2 term of Q2, and test_probe_helpers_at_edge_angles shows Q2 within
+    32 ulps of the Jacobian's scale at 100 m translations, so it is left as it is (changing the switch would move the bits
+    of every Horner evaluation the benchmark runs)."""
+    xs = np.linspace(0.0, (2 * np.pi - 0.1) ** 2, 3000)
+    edge = [a * a for a in M.EDGE_ANGLES + M.ABOVE_PI]
+    near = [np.nextafter(SERIES_X, 0), SERIES_X, np.nextafter(SERIES_X, 1), 1e-4, np.nextafter(1e-4, 0)]
+    xs = np.concatenate([xs, edge, near])
+    inp = np.zeros((xs.size, 17))
+    inp[:, 0] = xs
+    inp[:, 7] = 1.0
+    out = probe(inp)
+    worst = {k: {} for k in COEFS}
+    fails = []
+    for i, x in enumerate(xs):
+        ref, sens = M.coefs(x), M.coef_sensitivity(x)
+        band = M.band(np.sqrt(x))
+        for j, k in enumerate(COEFS):
+            r = float(ref[k])
+            if x < SERIES_X:
+                scale, ulps = abs(r), 16
+            else:
+                scale, ulps = max(abs(r), x ** -TERM_POWER[k]), 16
+            scale += float(sens[k])
+            e = abs(out[i, j] - r) / (EPS * scale)
+            worst[k][band] = max(worst[k].get(band, 0.0), e)
+            if not e <= ulps:
+                fails.append((k, x, out[i, j], r, e))
+    print_table("coefficients, dense sweep", worst)
+    xe = (np.pi - 1e-8) ** 2
+    i = int(np.where(xs == xe)[0][0])
+    print(f"E at theta = pi - 1e-8: device {out[i, 5]!r} reference {float(M.coefs(xe)['E'])!r} "
+          f"relative error {abs(out[i, 5] / float(M.coefs(xe)['E']) - 1):.2e}")
+    assert not fails, fails[:10]
+
+
+def edge_items(rng, per_angle=3):
+    """probe inputs: (angle, x, w, c, q, t, v) on random axes; |t|, |v| up to ~100 m"""
+    rows, angles = [], []
+    for ang in M.EDGE_ANGLES + M.ABOVE_PI:
+        for _ in range(per_angle):
+            w = M.axis(rng) * ang
+            q = M.to_np(M.quat_w(M.vec(w)))
+            rows.append(np.concatenate([[w @ w], w, rng.normal(size=3) * 3.0, q, rng.normal(size=3) * 40.0, rng.normal(size=3) * 40.0]))
+            angles.append(ang)
+    return np.array(rows), angles
+
+
+def test_probe_helpers_at_edge_angles(probe):
+    """qexp, qlog, so3_jr, so3_jr_inv, so3_jr_apply_dtheta, se3_log, se3_exp, se3_jr_inv on random axes at every edge angle
+    (the Pose3 maps up to pi - 1e-8, the SO(3) Jacobians K0 uses also at 3.5 .. 6 rad)."""
+    rng = np.random.default_rng(77)
+    inp, angles = edge_items(rng)
+    out = probe(inp)
+    worst, fails = {}, []
+
+    def check(name, got, ref, scale, ulps, ang):
+        e = float(np.abs(np.asarray(got) - np.asarray(ref)).max() / (EPS * max(scale, 1e-300)))
+        worst.setdefault(name, {})
+        worst[name][M.band(ang)] = max(worst[name].get(M.band(ang), 0.0), e)
+        if not e <= ulps:
+            fails.append((name, ang, e))
+
+    for row, o, ang in zip(inp, out, angles):
+        w, c, q, t, v = (M.vec(row[a:b]) for a, b in ((1, 4), (4, 7), (7, 11), (11, 14), (14, 17)))
+        x = row[0]
+        # unit quaternion from sin / cos of th/2: 4 ulps of 1
+        ref = M.to_np(M.quat_w(w))
+        check("qexp", o[OUT["qexp"]], ref, 1.0, 4, ang)
+        # J_r = I - B W + C W^2: 8 ulps of max |J|
+        ref = M.to_np(M.so3_jr_w(w))
+        check("so3_jr", o[OUT["jr"]].reshape(3, 3), ref, np.abs(ref).max(), 8, ang)
+        # J_r^{-1} = I + W/2 + E W^2: 8 ulps of max |J| + E's sensitivity to the rounding of x (|W^2| <= x; E has a pole at 2 pi)
+        ref = M.to_np(M.so3_jr_inv_w(w))
+        check("so3_jr_inv", o[OUT["jr_inv"]].reshape(3, 3), ref, np.abs(ref).max() + float(M.coef_sensitivity(x)["E"]) * x, 8, ang)
+        # d/dtheta [J_r(theta) c]: B, C, dB, dC times products of |theta| and |c| (central differences in mpmath): 16 ulps of max
+        ref = M.to_np(M.so3_jr_apply_dtheta_w(w, c))
+        check("jr_apply_dtheta", o[OUT["dexp"]].reshape(3, 3), ref, np.abs(ref).max(), 16, ang)
+        if ang > np.pi:
+            continue                      # Pose3's Logmap never returns theta > pi
+        # qlog of the double quaternion: atan2 + one division, 8 ulps of theta
+        ref = M.to_np(M.quat_log(q))
+        check("qlog", o[OUT["qlog"]], ref, np.abs(ref).max(), 8, ang)
+        # se3_log: w as qlog; u = t - W t / 2 + E W^2 t sums terms up to theta |t|: 16 ulps of max(|u|, |t|)
+        wr, ur = M.se3_log_q(q, t)
+        check("se3_log", np.concatenate([o[OUT["log_w"]], o[OUT["log_u"]]]), M.to_np(wr + ur),
+              max(np.abs(M.to_np(ur)).max(), np.abs(row[11:14]).max()), 16, ang)
+        # se3_exp: q as qexp, t = v + B W v + C W^2 v: 16 ulps of max(|t|, |v|)
+        Rr, tr_ = M.se3_exp_w(w, v)
+        check("se3_exp_q", o[OUT["exp_q"]], M.to_np(M.quat_w(w)), 1.0, 4, ang)
+        check("se3_exp_t", o[OUT["exp_t"]], M.to_np(tr_), max(np.abs(M.to_np(tr_)).max(), np.abs(row[14:17]).max()), 16, ang)
+        # se3_jr_inv at xi = [w, v]: Jw as J_r^{-1}; Q2 = D J_r^{-1}(w)[v] against central differences of Log(Exp(xi) Exp(d)),
+        # a sum of 4 products whose terms reach theta |v|: 32 ulps of the 6x6 Jacobian's max entry
+        J = M.to_np(M.se3_jr_inv_xi(w, v))
+        sJ = np.abs(J).max()
+        check("se3_jr_inv Jw", o[OUT["Jw"]].reshape(3, 3), J[:3, :3], sJ, 32, ang)
+        check("se3_jr_inv Q2", o[OUT["Q2"]].reshape(3, 3), J[3:, :3], sJ, 32, ang)
+    print_table("helpers at the edge angles", worst)
+    assert not fails, fails[:10]
+
+
+# ------------------------------------------------------------------------------------------------ windows at the edges
+ANG = M.EDGE_ANGLES[1:]                    # 16 angles: one window each
+THETA_PIM = [0.02, 0.4999999, 0.5000001, 1.3, 2.0, 2.9, np.pi - 1e-3, 0.1]
+N = 10
+
+
+def edge_problem(oracle, w, n=N):
+    """window w: IMU factors with preintegrated rotations from THETA_PIM and rotation residuals from ANG, state biases 0.1 rad/s
+    (gyro) off the records' bhat, between factors k-1 -> k whose error pose has |xi_w| from ANG, the prior on keyframe 0
+    with pose error |xi_w| = ANG[w]; translations up to ~100 m."""
+    rng = np.random.default_rng(500 + w)
+    states = np.zeros((n, 16))
+    imu = np.zeros((n, oracle.IMU_DATA))
+    states[0] = np.concatenate([rand_q(rng), rng.normal(size=3) * 50, rng.normal(size=3) * 5, BHAT + [0.01, 0.02, -0.01, 0.1, -0.05, 0.08]])
+    r_theta = np.zeros(n)
+    for k in range(1, n):
+        imu[k] = pim_record(oracle, rng, THETA_PIM[(w + k) % len(THETA_PIM)], bhat=BHAT)
+        r_theta[k] = ANG[(w + k) % len(ANG)]
+        xk = oracle.predict(imu[k], G, states[k - 1])
+        states[k] = oracle.retract(xk, np.concatenate([-M.axis(rng) * r_theta[k], rng.normal(size=3), rng.normal(size=3) * 0.5,
+                                                       rng.normal(size=6) * 0.01]))
+    btw_a, btw_b, btw = np.arange(n - 1, dtype=np.int32), np.arange(1, n, dtype=np.int32), np.zeros((n - 1, oracle.BTW_DATA))
+    for i, (a, b) in enumerate(zip(btw_a, btw_b)):
+        Ra, Rb = oracle.quat_to_rot(states[a, :4]), oracle.quat_to_rot(states[b, :4])
+        Rh, th = Ra.T @ Rb, Ra.T @ (states[b, 4:7] - states[a, 4:7])
+        Re, te = oracle.se3_exp(np.concatenate([M.axis(rng) * ANG[(w + 2 * b) % len(ANG)], rng.normal(size=3) * 40.0]))
+        Rm = Rh @ Re.T                       # measured^-1 * hx = (Re, te)
+        A = rng.normal(size=(6, 6))
+        btw[i] = np.concatenate([oracle.rot_to_quat(Rm), th - Rm @ te, oracle.sqrt_info_upper(A @ A.T * 0.05 + np.eye(6) * 0.01)])
+    xi = np.concatenate([M.axis(rng) * ANG[w % len(ANG)], rng.normal(size=3) * 40.0, rng.normal(size=9) * 0.1])
+    mean = oracle.retract(states[0], -xi)     # Log(prior^-1 x0) = xi (Pose3 chart = full Expmap)
+    prior = np.concatenate([mean, [1e-2] * 3 + [5e-2] * 3 + [1e-1] * 3 + [1e-3] * 6])
+    return dict(n=n, states=states, imu=imu, btw_a=btw_a, btw_b=btw_b, btw=btw, prior=prior, gravity=G, r_theta=r_theta)
+
+
+@pytest.fixture(scope="module")
+def edge_windows(oracle):
+    return [edge_problem(oracle, w) for w in range(len(ANG))]
+
+
+def edge_engine(probs, assembling):
+    """one_wave (K3 + k_band_solve) or the assembling sweep (K3 inside K4): the two forms small engines pick between"""
+    eng = Engine(EngineOpts(windows=len(probs), capacity=N, chunks=1, sweep_two_sided_max=0, solve_assemble_min=int(assembling)))
+    assert eng.solve_form() == ("assembling" if assembling else "one_wave")
+    for w, p in enumerate(probs):
+        helpers.load_engine(eng, w, p)
+    return eng
+
+
+def mp_cost(p):
+    """0.5 |r|^2 of every whitened factor of a window, residuals in mpmath"""
+    c = 0.0
+    sts = [M.State.of(x) for x in p["states"]]
+    for k in range(1, p["n"]):
+        c += 0.5 * float(np.sum(M.imu_residual_only(p["imu"][k], G, p["states"][k - 1], p["states"][k]) ** 2))
+    for a, b, rec in zip(p["btw_a"], p["btw_b"], p["btw"]):
+        c += 0.5 * float(np.sum(M.to_np(M.between_residual(rec, sts[a], sts[b])) ** 2))
+    c += 0.5 * float(np.sum(M.to_np(M.prior_residual(p["prior"], sts[0])) ** 2))
+    return c
+
+
+def test_k1_k2_at_edge_angles(oracle, edge_windows):
+    """K1 (15x30 whitened IMU blocks) and K2 (between) against the oracle at 1e-12 * max|block|, residuals against mpmath;
+    the between Jacobians against mpmath central differences once per angle; the cost (K2b's prior included) against the
+    oracle's and against mpmath's."""
+    eng = edge_engine(edge_windows, False)
+    eng.linearize(0)
+    eng.decide(init=True)
+    worst = dict(imu=0.0, imu_mp=0.0, btw=0.0, btw_mp=0.0, cost=0.0)
+    seen = set()
+    for w, p in enumerate(edge_windows):
+        r, J = eng.read_imu_lin(w, 1, N - 1)
+        for k in range(1, N):
+            ro, Jo = oracle.imu_factor(p["imu"][k], G, p["states"][k - 1], p["states"][k])
+            ru = oracle.imu_factor(p["imu"][k], G, p["states"][k - 1], p["states"][k], whiten=False)[0]
+            assert abs(np.linalg.norm(ru[:3]) - p["r_theta"][k]) <= 1e-6 * max(p["r_theta"][k], 1e-6)     # the input has the angle
+            e = max(relerr(r[k - 1], ro), relerr(J[k - 1], Jo))
+            worst["imu"] = max(worst["imu"], e)
+            assert e <= TOL, (w, k, p["r_theta"][k], e)
+            em = relerr(r[k - 1], M.imu_residual_only(p["imu"][k], G, p["states"][k - 1], p["states"][k]))
+            worst["imu_mp"] = max(worst["imu_mp"], em)
+            assert em <= TOL, (w, k, em)
+        rb, Ja, Jb = eng.read_between_lin(w, 0, N)
+        for a, b, rec in zip(p["btw_a"], p["btw_b"], p["btw"]):
+            ro, Jao, Jbo = oracle.between_factor(rec, p["states"][a], p["states"][b])
+            e = max(relerr(rb[b], ro), relerr(Ja[b], Jao), relerr(Jb[b], Jbo))
+            worst["btw"] = max(worst["btw"], e)
+            assert e <= TOL, (w, b, e)
+            ang = ANG[(w + 2 * b) % len(ANG)]
+            if ang not in seen:
+                seen.add(ang)
+                rm, Jam, Jbm = M.between_factor(rec, p["states"][a], p["states"][b])
+                em = max(relerr(rb[b], rm), relerr(Ja[b], Jam), relerr(Jb[b], Jbm))
+                worst["btw_mp"] = max(worst["btw_mp"], em)
+                assert em <= TOL, (ang, em)
+        cost = eng.read_lm(w)["cost"]
+        co = helpers.oracle_window(oracle, p).cost()
+        cm = mp_cost(p)
+        worst["cost"] = max(worst["cost"], abs(cost - co) / co, abs(cost - cm) / cm)
+        assert abs(cost - co) <= TOL * co and abs(cost - cm) <= TOL * cm, (w, cost, co, cm)
+    assert len(seen) == len(ANG)
+    print("worst relative errors:", {k: f"{v:.2e}" for k, v in worst.items()})
+    eng.close()
+
+
+def band_matvec(H, lam, x):
+    from tests.test_gpu_parity import band_matvec as bm
+    return bm(H, lam, x)
+
+
+@pytest.mark.parametrize("assembling", [False, True])
+def test_k3_normal_equations_and_solve_at_edge_angles(oracle, edge_windows, assembling):
+    """K3's H, g against the oracle's assembly of the same windows (1e-12 * max|block|), then one solve in the form under test:
+    the increment solves the device's own system to backward-stable accuracy (the assembling form builds H again inside
+    the sweep, so this checks that assembly too)."""
+    eng = edge_engine(edge_windows, assembling)
+    eng.linearize(0)
+    eng.decide(init=True)
+    eng.assemble()
+    worst = 0.0
+    Hs = []
+    for w, p in enumerate(edge_windows):
+        H, g = eng.read_normal(w, 0, N)
+        Hs.append((H, g))
+        _, Ho, go = helpers.oracle_window(oracle, p).assemble(w=3)
+        for k in range(N):
+            for d in range(min(k, 3) + 1):
+                if np.abs(Ho[k, d]).max() == 0:
+                    assert np.abs(H[k, d]).max() == 0
+                else:
+                    worst = max(worst, relerr(H[k, d], Ho[k, d]))
+                    assert relerr(H[k, d], Ho[k, d]) <= TOL, (w, k, d)
+        worst = max(worst, relerr(g, go))
+        assert relerr(g, go) <= TOL, w
+    eng.solve()
+    bw = 0.0
+    for w, (H, g) in enumerate(Hs):
+        d = eng.read_delta(w, 0, N)
+        lam = eng.read_lm(w)["lam"]
+        Hl, gl = H.astype(np.longdouble), g.astype(np.longdouble)
+        b = float(np.abs(band_matvec(Hl, np.longdouble(lam), d.astype(np.longdouble)) + gl).max() / np.abs(gl).max())
+        bw = max(bw, b)
+        assert eng.read_lm(w)["solve_failures"] == 0
+        assert b < 1e-9, (w, b)
+    print(f"{'assembling' if assembling else 'one_wave'}: normal equations worst relative error {worst:.2e}, backward error {bw:.2e}")
+    eng.close()
+
+
+def test_retract_of_large_increments(oracle):
+    """Consistent windows with keyframe 5 turned 0.7 .. 3.0 rad off: one LM trial, whose increments reach the closed-form
+    branch of se3_exp in k_retract.  Accepted states against oracle.retract(theta, delta) and mpmath at 1e-12 * max|state|."""
+    offs = [0.7, 1.5, 2.5, 3.0]
+    probs = []
+    for w, off in enumerate(offs):
+        p = edge_problem(oracle, 100 + w)
+        rng = np.random.default_rng(900 + w)
+        st = p["states"]
+        for k in range(1, N):                          # exact predictions: IMU residuals zero
+            st[k] = oracle.predict(p["imu"][k], G, st[k - 1])
+        for i, (a, b) in enumerate(zip(p["btw_a"], p["btw_b"])):      # exact between measurements
+            Ra = oracle.quat_to_rot(st[a, :4])
+            p["btw"][i, :4] = oracle.rot_to_quat(Ra.T @ oracle.quat_to_rot(st[b, :4]))
+            p["btw"][i, 4:7] = Ra.T @ (st[b, 4:7] - st[a, 4:7])
+        p["prior"][:16] = st[0]
+        st[5] = oracle.retract(st[5], np.concatenate([M.axis(rng) * off, np.zeros(12)]))
+        probs.append(p)
+    eng = Engine(EngineOpts(windows=len(offs), capacity=N))
+    for w, p in enumerate(probs):
+        helpers.load_engine(eng, w, p)
+    eng.linearize(0)
+    eng.decide(init=True)
+    eng.assemble()
+    eng.solve()
+    deltas = [eng.read_delta(w, 0, N) for w in range(len(offs))]
+    eng.retract()
+    eng.decide()
+    big = np.linalg.norm(deltas[offs.index(2.5)][5, :3])
+    print("|delta theta| of the turned keyframe:", [f"{np.linalg.norm(d[5, :3]):.3f}" for d in deltas])
+    assert big >= 0.6, big                                  # the test's own input reaches the closed form
+    worst = worst_mp = 0.0
+    for w, p in enumerate(probs):
+        lm = eng.read_lm(w)
+        assert lm["accepted"] == 1, (offs[w], lm)
+        got = eng.get_states(w, 0, N)
+        for k in range(N):
+            ref = oracle.retract(p["states"][k], deltas[w][k])
+            refm = M.retract(p["states"][k], deltas[w][k]).to_np()
+            for r in (ref, refm):
+                if np.dot(r[:4], got[k, :4]) < 0:
+                    r[:4] = -r[:4]
+            s = max(1.0, np.abs(ref).max())
+            worst, worst_mp = max(worst, np.abs(got[k] - ref).max() / s), max(worst_mp, np.abs(got[k] - refm).max() / s)
+    print(f"retract: worst vs oracle {worst:.2e}, vs mpmath {worst_mp:.2e}")
+    assert worst <= TOL and worst_mp <= TOL
+    eng.close()
+
+
+def test_predict_at_large_preintegrated_rotations(oracle):
+    """k_predict on records whose preintegrated rotation is 0.5 .. 3 rad: the chain from keyframe 0 against the oracle's, and
+    every single step from the oracle's previous state against mpmath, at 1e-12 * max|state| (test_gpu_parity's bar)."""
+    thetas = [0.4999999, 0.5000001, 1.3, 2.0, 2.9, 3.0]
+    rng = np.random.default_rng(41)
+    n = len(thetas) + 1
+    recs = np.array([pim_record(oracle, rng, t, bhat=BHAT) for t in thetas])
+    assert np.linalg.norm(recs[-1, 1:4]) > 2.9
+    x0 = np.concatenate([rand_q(rng), rng.normal(size=3) * 50, rng.normal(size=3) * 5, BHAT + [0, 0, 0, 0.1, -0.05, 0.08]])
+    chain = [x0]
+    for r in recs:
+        chain.append(oracle.predict(r, G, chain[-1]))
+    chain = np.array(chain)
+    eng = Engine(EngineOpts(windows=1, capacity=n + 2))
+    eng.set_states(0, 0, x0[None])
+    eng.set_imu(0, 1, recs)
+    eng.set_range(0, 0, 1)
+    eng.predict(0, 1, n - 1)
+    got = eng.get_states(0, 0, n)
+    flip = np.sum(got[:, :4] * chain[:, :4], axis=1) < 0      # q and -q: the oracle returns w >= 0, qmul keeps the sign it gets
+    got[flip, :4] = -got[flip, :4]
+    err = np.abs(got - chain).max(axis=0) / np.abs(chain).max(axis=0).clip(min=1.0)
+    eng.set_states(0, 0, chain)
+    worst_mp = 0.0
+    for k in range(1, n):
+        eng.predict(0, k, 1)
+        one = eng.get_states(0, k, 1)[0]
+        ref = M.predict(recs[k - 1], G, chain[k - 1])
+        if np.dot(ref[:4], one[:4]) < 0:
+            ref[:4] = -ref[:4]
+        worst_mp = max(worst_mp, np.abs(one - ref).max() / max(1.0, np.abs(ref).max()))
+    print(f"predict: chain vs oracle {err.max():.2e}, single steps vs mpmath {worst_mp:.2e}")
+    assert err.max() <= TOL and worst_mp <= TOL
+    eng.close()
+
+
+def k0_segments():
+    """(name, steps (dt, acc, gyro), bhat): accumulated tangent rotations that cross 0.5 rad, pass near pi and end in (pi, 2 pi)"""
+    rng = np.random.default_rng(5)
+    segs = []
+
+    def turn(n, dt, total, bhat, wobble=0.3):
+        t = np.arange(n) * dt
+        ax = np.stack([np.cos(wobble * t), np.sin(wobble * t), np.full(n, 2.0)], axis=1)
+        ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+        gyro = ax * (total / (n * dt)) + bhat[3:] + rng.normal(size=(n, 3)) * 1e-3
+        acc = np.array([0.3, -0.2, 9.81]) + bhat[:3] + rng.normal(size=(n, 3)) * 0.5
+        return np.concatenate([np.full((n, 1), dt), acc, gyro], axis=1)
+    b = np.array([0.05, -0.03, 0.02, 0.1, -0.08, 0.06])
+    segs.append(("2000 steps to 5 rad, biased", turn(2000, 0.0025, 5.0, b), b))
+    segs.append(("one step", turn(1, 0.01, 0.6, b), b))
+    segs.append(("400 steps to pi - 0.01", turn(400, 0.005, np.pi - 0.01, np.zeros(6), 0.0), np.zeros(6)))
+    segs.append(("200 steps across 0.5 to 3.5", turn(200, 0.005, 3.5, b), b))
+    return segs
+
+
+def test_k0_preintegration_at_large_angles(oracle):
+    """K0 on the segments of k0_segments: the mean against mpmath (rounding accumulates at most linearly: 8 ulps of the
+    mean's scale per step), H and R against the oracle's pim_to_record, the covariance against the independent twin
+    (test_gpu_k0_covariance's 5e-6, or twice the oracle's own distance from the twin where that is larger)."""
+    from tests.test_oracle_twin import _twin_cov
+    segs = k0_segments()
+    off = np.cumsum([0] + [len(s) for _, s, _ in segs])
+    steps = np.concatenate([s for _, s, _ in segs])
+    bh = np.array([b for _, _, b in segs])
+    cov = synth.CARLA_IMU_COV
+    eng = Engine(EngineOpts(windows=1, capacity=len(segs) + 2))
+    eng.preintegrate(0, 1, off, steps, bh, cov)
+    recs = eng.get_imu(0, 1, len(segs))
+    prm = oracle.make_imu_params(cov["acc"], cov["gyro"], cov["integration"], cov["bias_acc"], cov["bias_omega"], cov["bias_acc_omega_int"])
+    for (name, s, b), rec in zip(segs, recs):
+        T, mean = M.preintegrate_mean(s, b)
+        em = np.abs(rec[1:10] - mean).max() / np.abs(mean).max()
+        p = oracle.pim_new(b)
+        for st in s:
+            oracle.pim_integrate(p, prm, st[1:4], st[4:7], st[0])
+        ro = oracle.pim_to_record(p)
+        eH, eR = relerr(rec[16:70], ro[16:70]), relerr(rec[70:], ro[70:])
+        Pt = _twin_cov(s, b, cov)
+        R = oracle.unpack_upper(rec[70:], 15)
+        resid = np.abs(R.T @ R @ Pt - np.eye(15)).max()
+        Ro = oracle.unpack_upper(ro[70:], 15)
+        resid_o = np.abs(Ro.T @ Ro @ Pt - np.eye(15)).max()     # the twin's own central differences drift over 2 000 steps
+        print(f"{name}: |theta| {np.linalg.norm(mean[:3]):.4f}; mean vs mpmath {em:.2e}, H {eH:.2e}, R {eR:.2e} vs oracle, "
+              f"|R^T R P_twin - I| {resid:.2e} (oracle's {resid_o:.2e})")
+        assert abs(rec[0] - T) <= 1e-14 * len(s)
+        assert em <= 8 * EPS * len(s), (name, em)
+        assert eH <= 1e-10 and eR <= 1e-8, (name, eH, eR)
+        assert resid < max(5e-6, 2 * resid_o), name                  # test_gpu_k0_covariance's bar, or the oracle's own distance
+    assert any(np.linalg.norm(r[1:4]) > np.pi for r in recs)
+    eng.close()

@@ -78,7 +78,7 @@ __device__ __forceinline__ void linearize_prior_window(const View& v, int which,
         out[15 + (6 + i) * 15 + 6 + i] = 1.0 / sig[6 + i];
     }
 }
-__global__ void k_linearize_prior(View v, int which) {
+__global__ void __launch_bounds__(64) k_linearize_prior(View v, int which) {   // launched with 64-lane blocks (launch.inc)
     linearize_prior_window(v, which, blockIdx.x * blockDim.x + threadIdx.x);
 }
 // K2 + K2b in one launch (large batches): the prior linearisations are one lane per window, i.e. a handful of waves

@@ -126,14 +126,15 @@ VF_DI CoefD coef_dbdc(double x, const CoefABC& c) {
     }
     return d;
 }
-// E = 1/th^2 - (1+cos)/(2 th sin): coefficient of W^2 in J_r^{-1}; dE = E'(th)/th
+// E = 1/th^2 - (1+cos)/(2 th sin): coefficient of W^2 in J_r^{-1}; dE = E'(th)/th.  The closed form is evaluated in the
+// half-angle form 1/th^2 - cos(th/2)/(2 th sin(th/2)): 1+cos cancels as th -> pi (8e-9 relative at pi - 1e-8), cos(th/2) does not
 VF_DI double coef_e(double x) {
     if (x < SERIES_X)
         return fma(x, fma(x, fma(x, fma(x, fma(x, fma(x, fma(x, 3617.0 / 10670622842880000.0, 1.0 / 74724249600.0), 691.0 / 1307674368000.0), 1.0 / 47900160.0), 1.0 / 1209600.0), 1.0 / 30240.0), 1.0 / 720.0), 1.0 / 12.0);
     const double th = sqrt(x);
     double s, co;
-    sincos(th, &s, &co);
-    return 1.0 / x - (1.0 + co) / (2.0 * th * s);
+    sincos(0.5 * th, &s, &co);
+    return 1.0 / x - co / (2.0 * th * s);
 }
 VF_DI double coef_de(double x) {
     if (x < SERIES_X)
