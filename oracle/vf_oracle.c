@@ -382,8 +382,11 @@ void vfo_pim_integrate(vfo_pim* p, const vfo_imu_params* prm, const double macc[
     tr3(tHb, tHbT);
     mm(vHb, vHbT, vv, 3, 3, 3);
     mm(tHb, tHbT, rr, 3, 3, 3);
-    const double sv = (prm->acc_cov + prm->bias_acc_omega_int) / dt;
-    const double sr = (prm->gyro_cov + prm->bias_acc_omega_int) / dt;
+    /* GTSAM's literal (1/dt) vHb (.) vHb^T is inf * 0 = NaN at dt = 0 (two IMU samples with one timestamp).  Its limit is
+     * taken there instead: vHb = tHb = 0, so the step adds nothing (K0 writes the same term as dt R R^T, which is defined at
+     * dt = 0).  For dt > 0 the 4.0.x expression is kept as it is, bit for bit. */
+    const double sv = dt == 0.0 ? 0.0 : (prm->acc_cov + prm->bias_acc_omega_int) / dt;
+    const double sr = dt == 0.0 ? 0.0 : (prm->gyro_cov + prm->bias_acc_omega_int) / dt;
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) {
             G[(6 + i) * 15 + 6 + j] = sv * vv[i * 3 + j]; /* D_v_v */

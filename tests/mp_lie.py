@@ -405,7 +405,12 @@ def imu_residual_only(rec, gravity, xi, xj, whiten=True):
 
 def preintegrate_mean(steps, bhat):
     """TangentPreintegration::update's mean over steps (dt, acc xyz, gyro xyz): returns (dt, [theta, p, v]) as float64"""
-    b = vec(bhat)
+    T, d = preintegrate_mean_mp(steps, vec(bhat))
+    return float(T), to_np(d)
+
+
+def preintegrate_mean_mp(steps, b):
+    """preintegrate_mean for a bias estimate b given as 6 mpf (so that it can be perturbed): (dt, [theta, p, v]) in mpf"""
     th, p, v = [mp.mpf(0)] * 3, [mp.mpf(0)] * 3, [mp.mpf(0)] * 3
     T = mp.mpf(0)
     for st in np.asarray(steps, dtype=np.float64):
@@ -419,7 +424,7 @@ def preintegrate_mean(steps, bhat):
         v = [v[i] + an[i] * dt for i in range(3)]
         th = [th[i] + wt[i] * dt for i in range(3)]
         T += dt
-    return float(T), to_np(th + p + v)
+    return T, th + p + v
 
 
 # ---------------------------------------------------------------- edge inputs shared by the host and the device tests

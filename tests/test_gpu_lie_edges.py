@@ -18,6 +18,7 @@ import pytest
 
 from tests import helpers
 from tests import mp_lie as M
+from tests.pim_cases import k0_segments
 from tests.test_lie_edges_host import pim_record, rand_q
 from vil_sensor_fusion_amd import Engine, EngineOpts, synth
 
@@ -418,26 +419,6 @@ def test_predict_at_large_preintegrated_rotations(oracle):
     print(f"predict: chain vs oracle {err.max():.2e}, single steps vs mpmath {worst_mp:.2e}")
     assert err.max() <= TOL and worst_mp <= TOL
     eng.close()
-
-
-def k0_segments():
-    """(name, steps (dt, acc, gyro), bhat): accumulated tangent rotations that cross 0.5 rad, pass near pi and end in (pi, 2 pi)"""
-    rng = np.random.default_rng(5)
-    segs = []
-
-    def turn(n, dt, total, bhat, wobble=0.3):
-        t = np.arange(n) * dt
-        ax = np.stack([np.cos(wobble * t), np.sin(wobble * t), np.full(n, 2.0)], axis=1)
-        ax /= np.linalg.norm(ax, axis=1, keepdims=True)
-        gyro = ax * (total / (n * dt)) + bhat[3:] + rng.normal(size=(n, 3)) * 1e-3
-        acc = np.array([0.3, -0.2, 9.81]) + bhat[:3] + rng.normal(size=(n, 3)) * 0.5
-        return np.concatenate([np.full((n, 1), dt), acc, gyro], axis=1)
-    b = np.array([0.05, -0.03, 0.02, 0.1, -0.08, 0.06])
-    segs.append(("2000 steps to 5 rad, biased", turn(2000, 0.0025, 5.0, b), b))
-    segs.append(("one step", turn(1, 0.01, 0.6, b), b))
-    segs.append(("400 steps to pi - 0.01", turn(400, 0.005, np.pi - 0.01, np.zeros(6), 0.0), np.zeros(6)))
-    segs.append(("200 steps across 0.5 to 3.5", turn(200, 0.005, 3.5, b), b))
-    return segs
 
 
 def test_k0_preintegration_at_large_angles(oracle):
