@@ -36,8 +36,7 @@ static int isam_step_incremental(vf_engine* e, double relin_threshold) {
     a.stop_on = 0;
     vf::launch_inc_begin(a, relin_threshold, appended, invalid, e->stream);
     HIPCHK(hipMemsetAsync(e->v.lambda, 0, e->v.B * sizeof(double), e->stream));     // Gauss-Newton: no damping
-    if (a.B <= 128) vf::launch_linearize_all(a, 0, e->stream);
-    else { vf::launch_linearize_imu(a, 0, e->stream); vf::launch_linearize_between_prior(a, 0, e->stream); }
+    vf::launch_linearize(a, 0, e->stream);
     vf::launch_assemble(a, e->stream);
     vf::launch_inc_solve(a, e->stream);
     vf::launch_inc_retract(a, e->stream);

@@ -45,14 +45,11 @@ int vf_engine_marginals(vf_engine* e) {
     a.P = 0;                         // whole-window sweep whatever form the engine's solves take (they may be partitioned)
     HIPCHK(hipMemsetAsync(e->sig_fail, 0, B * sizeof(int), e->stream));
     // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
-    if (a.B <= 128) vf::launch_linearize_all(a, 0, e->stream);
-    else {
-        vf::launch_linearize_imu(a, 0, e->stream);
-        vf::launch_linearize_between_prior(a, 0, e->stream);
-    }
-    const bool assembling = assembles_in_solve(e);      // form 2; forms 0, 1, 3 and 4 factor by the plain forward sweep
-    if (!assembling) vf::launch_assemble(a, e->stream);
-    vf::launch_band_factor(a, assembling, e->stream);
+    vf::launch_linearize(a, 0, e->stream);
+    // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3
+    const vf::SolvePlan plan = solve_plan(e);
+    if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
+    vf::launch_band_factor(a, plan, e->stream);
     vf::launch_selinv(a, e->sig_fail, e->sig, e->stream);
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;

@@ -61,7 +61,7 @@ int vf_engine_read_normal(vf_engine* e, int window, int k0, int n, double* Hband
     if (rc) return rc;
     if (n == 0) return VF_OK;
     const size_t g0 = (size_t)window * e->v.M + k0;
-    if (assembles_in_solve(e) || assembles_in_hybrid(e)) {
+    if (solve_plan(e).k3 != vf::K3::all) {
         // H and g are not kept by the solves of this engine: assemble them now, for this window only, whether or not the
         // termination rule has finished it (a converged window's H is what Engine.pose_information is asked for)
         vf::launch_assemble_window(e->v, window, e->stream);
@@ -157,12 +157,18 @@ int vf_engine_time_stage(vf_engine* e, int stage, int reps, float* avg_ms) {
     if (!e || !avg_ms || reps < 1) return fail(VF_ERR_INVALID, "bad argument");
     vf::View tv = e->v;
     tv.stop_on = 0;           // stage timings are of the full work, whatever the windows' convergence flags say
+    // K4's stage is the form the View alone gives: never the hybrid, and the assembling sweep even where the engine's own solves
+    // are vetoed from it
+    vf::SolveInputs in = solve_inputs(e);
+    in.hybrid = false;
+    in.vetoed = false;
+    const vf::SolvePlan plan = vf::solve_plan(in);
     auto run = [&]() {
         switch (stage) {
             case VF_STAGE_LINEARIZE_IMU: vf::launch_linearize_imu(tv, 0, e->stream); break;
             case VF_STAGE_LINEARIZE_BTW: vf::launch_linearize_between(tv, 0, e->stream); break;
             case VF_STAGE_ASSEMBLE: vf::launch_assemble(tv, e->stream); break;
-            case VF_STAGE_SOLVE: vf::launch_band_solve(tv, e->stream); break;
+            case VF_STAGE_SOLVE: vf::launch_band_solve(tv, tv, plan, e->stream); break;
             case VF_STAGE_RETRACT: vf::launch_retract(tv, e->stream); break;
             case VF_STAGE_DECIDE: vf::launch_decide(tv, 1, e->stream); break;
             case VF_STAGE_ASSEMBLE_IDLE: vf::launch_assemble(tv, e->stream); break;

@@ -16,31 +16,25 @@ int vf_engine_linearize(vf_engine* e, int which) {
         HIPCHK(hipMemsetAsync(e->v.fresh, 0x01, e->v.B * sizeof(int), e->stream));
         HIPCHK(hipMemsetAsync(e->v.done, 0, e->v.B * sizeof(int), e->stream));
     }
-    if (e->v.B <= 128 || e->v.sh_G > 1) {
-        vf::launch_linearize_all(e->v, which, e->stream);       // latency form: K1, K2, K2b side by side
-    } else {
-        vf::launch_linearize_imu(e->v, which, e->stream);
-        vf::launch_linearize_between_prior(e->v, which, e->stream);
-    }
+    vf::launch_linearize(e->v, which, e->stream);
     if (e->x_used > 0) vf::launch_linearize_extra(e->v, which, e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
-// the next vf_engine_solve forms the normal equations inside its forward sweep (vf_engine_opts.solve_assemble_min): K3 has
-// nothing to do.  Not while far factors are held (their correction solves from H and g) nor in the hybrid form.
-static bool assembles_in_solve(const vf_engine* e) {
-    return vf::asm_in_solve(e->v) && e->x_used == 0 && !(e->hybrid && e->v.stop_on) && e->refine_iters() == 0 && !(e->v.min_fidelity > 0.0);
+// What the form of this engine's solves depends on (vf_solve_plan.hpp).  The sweep may not assemble H itself while something in
+// the solve reads H and g: the far factors' correction solves, the refined solve's, GTSAM's accept rule (k_model_change).
+static vf::SolveInputs solve_inputs(const vf_engine* e) {
+    return vf::solve_inputs(e->v, e->hybrid && e->v.stop_on, e->act_list != nullptr,
+                            e->x_used > 0 || e->refine_iters() > 0 || e->v.min_fidelity > 0.0);
 }
-// hybrid solves (termination rule on): the sweep half assembles its own rows, K3 runs for the partitioned half only
-static bool assembles_in_hybrid(const vf_engine* e) {
-    return e->hybrid && e->v.stop_on && vf::asm_in_hybrid(e->v) && e->x_used == 0 && e->refine_iters() == 0 && !(e->v.min_fidelity > 0.0);
-}
+static vf::SolvePlan solve_plan(const vf_engine* e) { return vf::solve_plan(solve_inputs(e)); }
 int vf_engine_assemble(vf_engine* e) {
     DeviceGuard dev_guard_(e);
     if (e) cold(e);
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
-    if (assembles_in_solve(e)) return VF_OK;
-    if (assembles_in_hybrid(e)) {
+    const vf::K3 k3 = solve_plan(e).k3;
+    if (k3 == vf::K3::none) return VF_OK;
+    if (k3 == vf::K3::partitioned) {
         vf::launch_assemble_for_partitioned(e->v, e->stream);
         HIPCHK(hipGetLastError());
         return VF_OK;
@@ -61,22 +55,21 @@ int vf_engine_solve(vf_engine* e) {
     if (e) cold(e);
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
     if (int rc = not_sharded(e, "vf_engine_solve")) return rc;
+    const vf::SolvePlan plan = solve_plan(e);
     auto band_solve = [&](double* gvec, double* delta, const int* skip = nullptr) {      // the engine's K4 form on another right-hand side / increment buffer
-        vf::View a = e->v;
-        a.gvec = gvec;
-        a.delta = delta;
         // (skip: windows that take no part -- a refinement's correction solves pass its stop flags, which include the windows
         // the termination rule has finished, so that a window whose corrections have converged costs its later solves nothing)
-        if (skip) { a.stop_on = 1; a.done = const_cast<int*>(skip); }
-        if (!assembles_in_solve(e) && !assembles_in_hybrid(e)) a.asm_min = 0;
-        if (e->hybrid && e->v.stop_on) {
-            vf::View p = e->partitioned_view();
-            p.gvec = gvec;
-            p.delta = delta;
-            if (skip) { p.stop_on = 1; p.done = const_cast<int*>(skip); }     // (the partitioned half skips the same windows)
+        auto on = [&](vf::View a) {
+            a.gvec = gvec;
+            a.delta = delta;
+            if (skip) { a.stop_on = 1; a.done = const_cast<int*>(skip); }
+            return a;
+        };
+        vf::View a = on(e->v);
+        if (plan.hybrid()) {
             a.act = e->act_list;
-            vf::launch_band_solve_hybrid(a, p, e->stream);
-        } else vf::launch_band_solve(a, e->stream);
+            vf::launch_band_solve(a, on(e->partitioned_view()), plan, e->stream);     // (the partitioned half skips the same windows)
+        } else vf::launch_band_solve(a, a, plan, e->stream);
     };
     // (single-window engines with a second stream -- the GraphManager's: the column engine's solve needs H and the far factors'
     // rows, nothing the window's own solve writes, and each of the two is a chain of small launches that leaves most of the part
@@ -226,8 +219,7 @@ int vf_engine_retract(vf_engine* e) {
 static int relinearize_restored(vf_engine* e) {
     vf::View a = e->v;
     a.relin_only = 1;
-    if (a.B <= 128 || a.sh_G > 1) vf::launch_linearize_all(a, 0, e->stream);
-    else { vf::launch_linearize_imu(a, 0, e->stream); vf::launch_linearize_between_prior(a, 0, e->stream); }
+    vf::launch_linearize(a, 0, e->stream);
     HIPCHK(hipMemsetAsync(e->v.relin, 0, e->v.B * sizeof(int), e->stream));
     return VF_OK;
 }
@@ -366,13 +358,7 @@ int vf_engine_iterate(vf_engine* e, int iterations) {
 }
 int vf_engine_solve_form(vf_engine* e, int* form) {
     if (!e || !form) return fail(VF_ERR_INVALID, "null argument");
-    const vf::View& v = e->v;
-    if (v.P >= 2) *form = 4;
-    else if (e->hybrid && v.stop_on) *form = 5;
-    else if (v.B <= v.tw_max) *form = 3;
-    else if (assembles_in_solve(e)) *form = 2;
-    else if (v.split_min > 0 && v.B >= v.split_min) *form = 1;
-    else *form = 0;
+    *form = solve_plan(e).form;
     return VF_OK;
 }
 int vf_engine_graph_info(vf_engine* e, int* enabled, int* captures, long* replays) {

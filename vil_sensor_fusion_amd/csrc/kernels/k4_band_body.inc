@@ -167,7 +167,7 @@ constexpr int MID_TOTAL = 45 * MID_LD + 48;     // + the 45 solved increments ha
 //   as two kernels.  They hand over through HBM only (the panels and the rhs row the forward sweep stores anyway); the
 //   back substitution needs 9 KB of LDS instead of 38 and so runs two and more waves per SIMD where the fused kernel
 //   is held to one by the forward sweep's trailing window.
-// MODE 6 (assembling forward sweep, batches of >= View::asm_min windows): SOLVE_FULL_FWD that forms the block rows of H itself,
+// MODE 6 (assembling forward sweep, where solve_plan() picks it: vf_solve_plan.hpp): SOLVE_FULL_FWD that forms the block rows of H itself,
 //   from the J stream and the between linearisations K1 / K2 leave, on the matrix cores, under the waits of the pivot
 //   chain -- K3 is not launched, H is neither written nor read.  See "assembling sweep" below.
 // MODE 7 / 8 (k_band_forward_asm2): MODE 6 as TWO waves of one workgroup sharing its LDS -- wave 0 eliminates (SOLVE_ASM_A: the

@@ -89,12 +89,7 @@ __global__ void __launch_bounds__(64) k_band_selinv(View v, const int* __restric
         __syncthreads();
     }
 }
-void launch_band_factor(const View& v, bool assembling, hipStream_t s) {
-    if (assembling) {
-        if (v.asm_waves == 2) launch_asm2(v, s);
-        else hipLaunchKernelGGL(k_band_forward_asm, dim3(v.B), dim3(64), 0, s, v);
-    } else hipLaunchKernelGGL(k_band_forward, dim3(v.B), dim3(64), 0, s, v);
-}
+void launch_band_factor(const View& v, const SolvePlan& plan, hipStream_t s) { launch_band_forward(v, plan.factor, s); }
 void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s) {
     hipLaunchKernelGGL(k_band_selinv, dim3(v.B), dim3(64), 0, s, v, failed, sig);
 }

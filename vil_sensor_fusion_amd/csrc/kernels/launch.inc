@@ -35,7 +35,7 @@ void launch_extra_combine(const View& v, const double* Zm, size_t zstride, int s
         hipLaunchKernelGGL(k_extra_apply<false>, dim3(nblk((long)v.M * 15, 256), (unsigned)v.B), dim3(256), 0, s, v, Zm, zstride, slots);
     }
 }
-void launch_linearize_all(const View& v, int which, hipStream_t s) {
+static void launch_linearize_all(const View& v, int which, hipStream_t s) {
     const int nb_imu = (int)nblk(v.G, VF_K1_BLOCK), nb_btw = nb_imu, nb_pri = (int)nblk(v.B, VF_K1_BLOCK);
     if (v.sh_G > 1) hipLaunchKernelGGL(k_linearize_all<true>, dim3(nb_imu + nb_btw + nb_pri), dim3(VF_K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
     else hipLaunchKernelGGL(k_linearize_all<false>, dim3(nb_imu + nb_btw + nb_pri), dim3(VF_K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
@@ -46,9 +46,16 @@ void launch_linearize_imu(const View& v, int which, hipStream_t s) {
 void launch_linearize_between(const View& v, int which, hipStream_t s) {
     hipLaunchKernelGGL(k_linearize_between, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which);
 }
-void launch_linearize_between_prior(const View& v, int which, hipStream_t s) {
+static void launch_linearize_between_prior(const View& v, int which, hipStream_t s) {     // K2 + K2b in one launch
     const int nb_pri = (int)nblk(v.B, 64);
     hipLaunchKernelGGL(k_linearize_between_prior, dim3(nblk(v.G, 256) + nb_pri), dim3(256), 0, s, v, which, nb_pri);
+}
+void launch_linearize(const View& v, int which, hipStream_t s) {
+    if (v.B <= 128 || v.sh_G > 1) launch_linearize_all(v, which, s);
+    else {
+        launch_linearize_imu(v, which, s);
+        launch_linearize_between_prior(v, which, s);
+    }
 }
 void launch_linearize_tail(const View& v, int nslid, hipStream_t s) {
     hipLaunchKernelGGL(k_linearize_tail, dim3(2 * v.B + nblk(v.B, 64)), dim3(VF_K1_BLOCK), 0, s, v, nslid);
@@ -119,20 +126,32 @@ static void launch_asm2(const View& v, hipStream_t s) {
         hipLaunchKernelGGL(k_band_forward_asm2, dim3(nb), dim3(128), 0, s, v, w0);
     }
 }
-void launch_band_solve(const View& v, hipStream_t s) {
-    if (v.P >= 2) { launch_partitioned_solve(v, s); return; }
-    // few windows: two waves per window from both ends (latency); many: one wave per window (throughput)
-    if (v.B <= v.tw_max) hipLaunchKernelGGL(k_band_solve_tw, dim3(v.B), dim3(128), 0, s, v);
-    else if (asm_in_solve(v)) {
-        if (v.asm_waves == 2) {
-            launch_asm2(v, s);
-        }
-        else hipLaunchKernelGGL(k_band_forward_asm, dim3(v.B), dim3(64), 0, s, v);
-        hipLaunchKernelGGL(k_band_backward, dim3(v.B), dim3(64), 0, s, v);
-    } else if (v.split_min > 0 && v.B >= v.split_min) {
-        hipLaunchKernelGGL(k_band_forward, dim3(v.B), dim3(64), 0, s, v);
-        hipLaunchKernelGGL(k_band_backward, dim3(v.B), dim3(64), 0, s, v);
-    } else hipLaunchKernelGGL(k_band_solve, dim3(v.B), dim3(64), 0, s, v);
+// the forward half of a split or assembling sweep (launch_band_factor: all there is of it)
+static void launch_band_forward(const View& v, Sweep f, hipStream_t s) {
+    if (f == Sweep::asm2) launch_asm2(v, s);
+    else if (f == Sweep::asm1) hipLaunchKernelGGL(k_band_forward_asm, dim3(v.B), dim3(64), 0, s, v);
+    else hipLaunchKernelGGL(k_band_forward, dim3(v.B), dim3(64), 0, s, v);
+}
+void launch_band_solve(const View& v, const View& vp, const SolvePlan& plan, hipStream_t s) {
+    View a = v, b = vp;
+    if (plan.hybrid()) {
+        a.gate = 1;
+        b.gate = 2;
+    }
+    // few windows: two waves per window from both ends (latency); many: one wave per window (throughput).  (a.act, when the
+    // engine hands it to a hybrid's sweep: the active windows are visited first)
+    switch (plan.sweep) {
+        case Sweep::none: break;
+        case Sweep::two_sided: hipLaunchKernelGGL(k_band_solve_tw, dim3(a.B), dim3(128), 0, s, a); break;
+        case Sweep::fused: hipLaunchKernelGGL(k_band_solve, dim3(a.B), dim3(64), 0, s, a); break;
+        case Sweep::split:
+        case Sweep::asm1:
+        case Sweep::asm2:
+            launch_band_forward(a, plan.sweep, s);
+            hipLaunchKernelGGL(k_band_backward, dim3(a.B), dim3(64), 0, s, a);
+            break;
+    }
+    if (plan.partitioned) launch_partitioned_solve(b, s);
 }
 // windows of the running solve that still take LM trials (termination rule on)
 __global__ void __launch_bounds__(1024) k_count_active(View v) {
@@ -162,25 +181,6 @@ __global__ void __launch_bounds__(1024) k_count_active(View v) {
 }
 void launch_count_active(const View& v, hipStream_t s) {
     hipLaunchKernelGGL(k_count_active, dim3(1), dim3(1024), 0, s, v);
-}
-void launch_band_solve_hybrid(const View& v, const View& vp, hipStream_t s) {
-    View a = v, b = vp;
-    a.gate = 1;
-    b.gate = 2;
-    // (a.act, when the engine has allocated it: the sweeps visit the active windows first)
-    if (asm_in_hybrid(v)) {
-        // (two waves per window here too, round 5: with the compacted list, the eliminator's priority and -- what had made it
-        // 5 % slower than one wave in round 4 and 21 % slower than itself in the headline's launch -- the placement kernel in
-        // front of it, launch_asm2)
-        if (a.asm_waves == 2 && a.act) launch_asm2(a, s);
-        else
-        hipLaunchKernelGGL(k_band_forward_asm, dim3(a.B), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(k_band_backward, dim3(a.B), dim3(64), 0, s, a);
-    } else if (a.split_min > 0 && a.B >= a.split_min) {
-        hipLaunchKernelGGL(k_band_forward, dim3(a.B), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(k_band_backward, dim3(a.B), dim3(64), 0, s, a);
-    } else hipLaunchKernelGGL(k_band_solve, dim3(a.B), dim3(64), 0, s, a);
-    launch_partitioned_solve(b, s);
 }
 void launch_model_change(const View& v, hipStream_t s) {
     hipLaunchKernelGGL(k_model_change, dim3(v.B), dim3(256), 0, s, v);

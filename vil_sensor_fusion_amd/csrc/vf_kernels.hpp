@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vf_solve_plan.hpp"
+
 namespace vf {
 
 constexpr int TILE = 64;        // AoSoA tile = one wavefront of factors
@@ -199,10 +201,11 @@ struct View {
     int gate, gate_T;
     int* act;           // [B] or null: compacted list of the windows still taking trials (k_count_active); the one-wave sweeps of a hybrid
                         // solve then map workgroup i to window act[i], so that the active windows are dispatched first and contiguously
+    // the four below are read by the host only, in solve_plan() (vf_solve_plan.hpp), which says when each applies
     int tw_max;         // whole-window sweeps: up to this many windows two waves per window from both ends, above one wave per window
     int split_min;      // whole-window sweeps: from this many windows on, forward sweep and back substitution as two kernels (0 = never)
-    int asm_min;        // whole-window sweeps: from this many windows on, the forward sweep assembles H itself from the J stream and
-                        // K3 is not launched (0 = never; asm_in_solve() below)
+    int asm_min;        // whole-window sweeps: from this many windows on, the forward sweep may assemble H itself from the J stream and
+                        // K3 is not launched (0 = never)
     int asm_waves;      // ... as one wave per window (1) or as an eliminator wave + an assembler wave sharing the window's LDS (2)
     unsigned* place;    // [PLACE_CELLS] per-CU claims of the two-wave sweep's launch (which SIMDs have their eliminator): k_band_forward_asm2
     // "far" between factors: BetweenFactor<Pose3> on any pair of keyframes of a window (wider than the band, or a second factor
@@ -282,15 +285,6 @@ void launch_refine_step(const View& v, const Refine& q, double rel_stop, hipStre
 void launch_refine_end(const View& v, const Refine& q, hipStream_t s);                    // delta := x
 void launch_refine_apply(const View& v, const Refine& q, const double* p, double* out, hipStream_t s);   // out := J^T (J p) + lambda p
 
-// does launch_band_solve(v) assemble the normal equations inside the forward sweep (so that launch_assemble may be skipped)?
-// One-wave whole-window sweeps of an unsharded engine only; the far-factor correction and the hybrid form solve from H.
-inline bool asm_in_solve(const View& v) {
-    return v.asm_min > 0 && v.B >= v.asm_min && v.P < 2 && v.B > v.tw_max && v.sh_G <= 1 && v.gate == 0;
-}
-// the same question for the SWEEP half of a hybrid solve (launch_band_solve_hybrid; K3 then serves the partitioned half only)
-inline bool asm_in_hybrid(const View& v) {
-    return v.asm_min > 0 && v.B >= v.asm_min && v.P < 2 && v.B > v.tw_max && v.sh_G <= 1;
-}
 // isotropic IMU covariances (ImuManagerRos.cpp:20-33)
 struct ImuCov { double acc, gyro, integration, bias_acc, bias_omega, bias_int; };
 void launch_preintegrate(const View& v, long g0, int n, const int* off, const double* steps, const double* bhat6,
@@ -306,25 +300,25 @@ void launch_extra_combine(const View& v, const double* Zm, size_t zstride, int s
 void launch_cols_prepare(const View& v, const View& c, int ncols, hipStream_t s);    // single-window engines: the Woodbury columns as one batch
 void launch_cols_fail(const View& v, const View& c, int ncols, hipStream_t s);
 void launch_partitioned_solve(const View& v, hipStream_t s);
+// K1, K2 and K2b: one launch up to 128 windows and on time-sharded engines (latency), K1 and K2 + K2b as two above (throughput)
+void launch_linearize(const View& v, int which, hipStream_t s);
 void launch_linearize_imu(const View& v, int which, hipStream_t s);
 void launch_linearize_between(const View& v, int which, hipStream_t s);
 void launch_linearize_prior(const View& v, int which, hipStream_t s);
-void launch_linearize_between_prior(const View& v, int which, hipStream_t s);   // K2 + K2b in one launch (large batches)
 void launch_linearize_tail(const View& v, int nslid, hipStream_t s);   // warm start: factors of the appended keyframes + priors
-void launch_linearize_all(const View& v, int which, hipStream_t s);   // the three above in one launch (few windows)
 void launch_assemble(const View& v, hipStream_t s);
 void launch_assemble_window(const View& v, int window, hipStream_t s);   // H and g of one window, whatever its fresh / done flags say
-void launch_assemble_for_partitioned(const View& v, hipStream_t s);   // hybrid solves with an assembling sweep (asm_in_hybrid)
-void launch_band_solve(const View& v, hipStream_t s);
+void launch_assemble_for_partitioned(const View& v, hipStream_t s);   // hybrid solves with an assembling sweep (K3::partitioned)
+// K4 in the form the plan gives: its sweep on v, its partitioned solve on vp -- v itself, or for the hybrid (see View::gate) the
+// same engine viewed with the partitioned form's chunk count and buffers
+void launch_band_solve(const View& v, const View& vp, const SolvePlan& plan, hipStream_t s);
 void launch_count_active(const View& v, hipStream_t s);
-// marginal covariances (vf_engine_marginals): the forward sweep alone (one wave per window; assembling: the sweep forms H itself),
-// then selected inversion of its panels into sig ([G][SIG_SLOT]: Sigma_kk lower triangle, Sigma_{k+1,k}); windows flagged in
-// `failed` are skipped
+// marginal covariances (vf_engine_marginals): the forward sweep alone, one wave per window (SolvePlan::factor: the assembling
+// forms build H themselves), then selected inversion of its panels into sig ([G][SIG_SLOT]: Sigma_kk lower triangle,
+// Sigma_{k+1,k}); windows flagged in `failed` are skipped
 constexpr int SIG_SLOT = 120 + 225;
-void launch_band_factor(const View& v, bool assembling, hipStream_t s);
+void launch_band_factor(const View& v, const SolvePlan& plan, hipStream_t s);
 void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s);
-// hybrid K4 (see View::gate): vp = the same engine viewed with the partitioned form's chunk count
-void launch_band_solve_hybrid(const View& v, const View& vp, hipStream_t s);
 void launch_retract(const View& v, hipStream_t s);
 void launch_model_change(const View& v, hipStream_t s);     // View::model of every window, from g and the increment just solved
 void launch_decide(const View& v, int init, hipStream_t s);
