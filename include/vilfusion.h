@@ -477,9 +477,21 @@ int vf_engine_read_panels(vf_engine* e, int window, int k0, int n, double* panel
  * increments, lambda, counters, done flags, sticky words, the cached result block -- and the engine is marked cold (the next
  * vf_engine_iterate gives the bits it would have given without the call); vf_engine_read_panels returns the undamped panels
  * afterwards.  Refused with VF_ERR_INVALID: time-sharded engines, and engines with far factors alive in any window, linear ones
- * included (vf_engine_get_extra_between, vf_engine_get_linear_far).  The blocks live in a device array of 2.7 KB per keyframe
- * slot, allocated by the first call. */
+ * included (vf_engine_get_extra_between, vf_engine_get_linear_far) -- vf_engine_marginals_ex with VF_MARGINALS_FAR takes those.
+ * The blocks live in a device array of 2.7 KB per keyframe slot, allocated by the first call.  = vf_engine_marginals_ex(e, 0). */
 int vf_engine_marginals(vf_engine* e);
+/* vf_engine_marginals with flags.  VF_MARGINALS_FAR: far factors alive (linear ones included) are no longer refused; their
+ * Jacobians at the current states correct the band's covariances by a low-rank downdate, Sigma = A^-1 - Z C^-1 Z^T with A the
+ * undamped band, U the whitened far rows (m = 6 x slots in use), Z = A^-1 U and C = I + U^T Z, solved on the panels of the one
+ * factorisation the call makes (the factorisation vf_engine_marginals makes on the same engine without far factors).  Same
+ * output, same read-back; windows without a live far factor get exactly the bits vf_engine_marginals gives them on that engine,
+ * and an engine without far factors gives them everywhere.  A window whose C is not positive definite reads back VF_ERR_NOT_SPD.
+ * The LM state is untouched as above, and so are the far lists, the linear far factor, the marginal prior computed ahead
+ * (vf_engine_marginalize_ahead) and the column engine.  The call's scratch (M x 15 x m + m^2 doubles per window) is allocated by
+ * the first such call and kept; it is bounded by 1 GiB: more windows than fit are done in groups.  Unknown
+ * flags: VF_ERR_INVALID. */
+#define VF_MARGINALS_FAR 1u
+int vf_engine_marginals_ex(vf_engine* e, unsigned flags);
 /* ... read back (synchronises): for keyframes k0 .. k0+n-1 of the range the last vf_engine_marginals saw, Sigma_kk (full
  * symmetric 15x15, row-major) and the cross block Sigma_{k+1,k} (15x15, row = dof of k+1, column = dof of k; zero for the window's
  * last keyframe).  Tangent order [omega, v] of Pose3, velocity, bias [acc, gyro].  Either pointer may be NULL.  VF_ERR_NOT_SPD:
@@ -620,6 +632,9 @@ typedef struct {
     int max_far_factors;       /* vf_engine_opts.max_far_factors: loop closures (between factors the band cannot hold) alive at once;
                                   vf_add_between returns VF_ERR_CAPACITY beyond.  0 = the default, VF_MAX_FAR_LIMIT (a handle has no
                                   caller-sized arrays to keep small; while VF_MAX_EXTRA or fewer are alive it solves with the LDS forms) */
+    int far_covariance;        /* != 0: vf_get_marginal_covariance and the covariance callbacks take far factors alive (loop closures, linear
+                                  ones included) into account -- vf_engine_marginals_ex(VF_MARGINALS_FAR) -- instead of refusing while any is
+                                  alive.  Default 0 */
 } vf_graph_opts;
 
 /* (time, pose q_wxyz, position, velocity, bias[acc,gyro]) -- GraphManager::OptimizationCallback
@@ -672,7 +687,8 @@ int vf_set_callback(vf_graph* g, vf_callback cb, void* user);
 /* ISAM2::marginalCovariance(X(key)) (no reference call: the reference never asks for it) -- the 15x15 marginal covariance of a
  * solved key (tangent order [omega, v] of Pose3, velocity, bias [acc, gyro]; reference-compat handles: at the linearisation
  * points, as iSAM2 factors it).  The first call after a solve computes the window's covariances (vf_engine_marginals), later ones
- * read them; vf_solve and vf_set_initial_state void them.  VF_ERR_INVALID before the first solve and while far factors are alive;
+ * read them; vf_solve and vf_set_initial_state void them.  VF_ERR_INVALID before the first solve and, unless
+ * vf_graph_opts.far_covariance is set, while far factors are alive;
  * VF_ERR_BAD_KEY for a key not solved yet or marginalised out of the window.  Takes the state lock like vf_get_state: never call it
  * from inside a callback. */
 int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
@@ -680,7 +696,8 @@ int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
 typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
                                 const double bias[6], const double cov225[225]);
 /* Only while one is registered does vf_solve compute covariances: after the result read, before the callbacks (which run inside the
- * state lock as the plain ones do).  If they cannot be had (far factors alive, undamped system not positive definite) the covariance
+ * state lock as the plain ones do).  If they cannot be had (far factors alive without vf_graph_opts.far_covariance, undamped system
+ * not positive definite) the covariance
  * callbacks receive NaN and vf_last_error says why; the solve itself succeeds. */
 int vf_set_covariance_callback(vf_graph* g, vf_cov_callback cb, void* user);
 /* GraphManager::graph()->size(): factors staged since the last solve (3 priors at start +

@@ -54,11 +54,13 @@ class GraphOptsC(C.Structure):
                 ("prior_sigma", C.c_double * 15), ("rel_tol", C.c_double), ("abs_tol", C.c_double),
                 ("cold_start", C.c_int), ("fixed_capacity", C.c_int), ("reference_compat", C.c_int),
                 ("relin_threshold", C.c_double), ("incremental", C.c_int), ("wildfire", C.c_double), ("min_model_fidelity", C.c_double),
-                ("synchronous_staging", C.c_int), ("max_far_factors", C.c_int)]
+                ("synchronous_staging", C.c_int), ("max_far_factors", C.c_int), ("far_covariance", C.c_int)]
 
 
 CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                        C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+MARGINALS_FAR = 1        # vf_engine_marginals_ex: take far factors alive into account (VF_MARGINALS_FAR)
 
 COV_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -76,7 +78,7 @@ SYMBOLS = [
     "vf_engine_decide", "vf_engine_iterate", "vf_engine_slide", "vf_engine_predict",
     "vf_engine_sync", "vf_engine_graph_info", "vf_engine_solve_form",
     "vf_engine_read_imu_lin", "vf_engine_read_between_lin", "vf_engine_read_normal",
-    "vf_engine_read_delta", "vf_engine_read_panels", "vf_engine_read_lm", "vf_engine_marginals", "vf_engine_read_marginals",
+    "vf_engine_read_delta", "vf_engine_read_panels", "vf_engine_read_lm", "vf_engine_marginals", "vf_engine_marginals_ex", "vf_engine_read_marginals",
     "vf_engine_time_stage", "vf_engine_time_iterate", "vf_engine_counts",
     "vf_engine_preintegrate", "vf_engine_get_imu", "vf_engine_ingest_tail", "vf_engine_ingest_status",
     "vf_engine_marginalize", "vf_engine_drop_oldest", "vf_engine_read_marginal", "vf_engine_compact", "vf_engine_grow",
@@ -111,6 +113,7 @@ def lib():
         l.vf_graph_default_opts_sized.restype = None
         l.vf_graph_default_opts.restype = None
         l.vf_destroy.restype = None
+        l.vf_engine_marginals_ex.argtypes = [C.c_void_p, C.c_uint]
         _lib = l
     return _lib
 

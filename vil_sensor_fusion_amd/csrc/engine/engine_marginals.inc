@@ -6,16 +6,43 @@
 // point at arrays of this section: the LM state of the engine (states, increments, lambda, counters, done flags, sticky words,
 // the cached result block) is not touched.  What is overwritten -- the current buffer's linearisation (the same bits: it is of
 // the same states), H, g and the panels -- is what a cold start rebuilds, and the engine is marked cold.
-int vf_engine_marginals(vf_engine* e) {
+//
+// VF_MARGINALS_FAR: far factors alive are taken in as the low-rank downdate of k4_selinv_far.inc, after k_band_selinv.  Their
+// lists and the linear far factor are only read (the current buffer's far linearisation is rewritten, with the same bits as
+// the rest of it); the scratch is this section's own (fc_scratch), never far_scratch, x_Z, x_gtmp or the column engine's.
+// Z takes M x 15 x m doubles per window: at most FARCOV_BUDGET bytes of windows are done at a time, in groups.  Each group costs
+// the latency of its substitution chains (two dependent steps per keyframe) whatever its size, so a group should hold every window
+// the GPU can run at once.  1 GiB holds one far factor per window on a 1 024-window engine of 1 088 slots (0.8 GB, as much as the
+// solve's own Woodbury columns take on that engine, x_Z): that case is one group.  With eight closures per window (m = 48) it
+// makes groups of about 180 windows of 1 024 slots instead of asking for 6 GB.
+constexpr size_t FARCOV_BUDGET = (size_t)1 << 30;
+int vf_engine_marginals(vf_engine* e) { return vf_engine_marginals_ex(e, 0); }
+int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    if (flags & ~(unsigned)VF_MARGINALS_FAR) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
+    const bool far = (flags & VF_MARGINALS_FAR) != 0;
     const bool cached = e->res_cached;
     DeviceGuard dev_guard_(e);
     e->res_cached = cached;      // (nothing here touches the result block of the last solve)
     if (int rc = not_sharded(e, "vf_engine_marginals")) return rc;
     e->recount_far();
-    if (e->x_used > 0)
+    if (e->x_used > 0 && !far)
         return fail(VF_ERR_INVALID, "vf_engine_marginals: a window holds far factors (vf_engine_get_extra_between / vf_engine_get_linear_far); "
-                    "their correction of the covariance is not implemented");
+                    "their correction of the covariance needs vf_engine_marginals_ex(e, VF_MARGINALS_FAR)");
+    const int m = 6 * e->x_used;
+    const size_t zwin = (size_t)e->v.M * 15 * m, cwin = (size_t)m * m;
+    int group = 0;
+    if (m > 0) {
+        const size_t per = (zwin + cwin) * sizeof(double);
+        group = (int)std::max<size_t>(1, std::min<size_t>((size_t)e->v.B, FARCOV_BUDGET / per));
+        const size_t want = (size_t)group * (zwin + cwin);
+        if (want > e->fc_doubles) {
+            HIPCHK(hipStreamSynchronize(e->stream));
+            if (e->fc_scratch) { (void)hipFree(e->fc_scratch); e->fc_scratch = nullptr; e->fc_doubles = 0; }
+            HIPCHK(hipMalloc((void**)&e->fc_scratch, want * sizeof(double)));
+            e->fc_doubles = want;
+        }
+    }
     const size_t G = (size_t)e->v.G, B = (size_t)e->v.B;
     if (!e->sig || e->sig_G != e->v.G) {
         // allocated on first use (G x 2.7 KB): engines that never ask for covariances do not grow
@@ -46,11 +73,28 @@ int vf_engine_marginals(vf_engine* e) {
     HIPCHK(hipMemsetAsync(e->sig_fail, 0, B * sizeof(int), e->stream));
     // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
     vf::launch_linearize(a, 0, e->stream);
-    // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3
-    const vf::SolvePlan plan = solve_plan(e);
+    if (m > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
+    // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3.  The plan
+    // is the one the same engine without far factors would have: far factors veto the assembling sweep for the SOLVE (its Woodbury
+    // columns read H and g), but they never enter the band and the downdate reads only the panels -- so a window without far
+    // factors gets the bits it gets from an engine that has none, on batch engines that assemble as well
+    const vf::SolvePlan plan = vf::solve_plan(vf::solve_inputs(e->v, e->hybrid && e->v.stop_on, e->act_list != nullptr,
+                                                               e->refine_iters() > 0 || e->v.min_fidelity > 0.0));
     if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
     vf::launch_band_factor(a, plan, e->stream);
     vf::launch_selinv(a, e->sig_fail, e->sig, e->stream);
+    for (int w0 = 0; w0 < e->v.B && m > 0; w0 += group) {
+        vf::FarCov fc{};
+        fc.Z = e->fc_scratch;
+        fc.C = e->fc_scratch + (size_t)group * zwin;
+        fc.failed = e->sig_fail;
+        fc.w0 = w0;
+        fc.m = m;
+        fc.slots = e->x_used;
+        fc.zwin = zwin;
+        fc.cwin = cwin;
+        vf::launch_farcov(a, fc, std::min(group, e->v.B - w0), e->sig, e->stream);
+    }
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;
     e->sig_hi = e->h_hi;

@@ -368,6 +368,10 @@ struct vf_engine {
     long sig_G = 0;
     bool sig_valid = false;
     std::vector<int> sig_lo, sig_hi;
+    // vf_engine_marginals_ex with VF_MARGINALS_FAR: Z = A^-1 U and the m x m systems of a group of windows (vf::FarCov), allocated
+    // on first use and grown when a later call needs more; FARCOV_BUDGET bounds it, more windows than fit are done in groups
+    double* fc_scratch = nullptr;
+    size_t fc_doubles = 0;
     int ensure_stage(size_t bytes) {
         if (bytes <= stage_bytes) return VF_OK;
         if (stage) HIPCHK(hipFree(stage));

@@ -158,6 +158,7 @@ static void graph_defaults(vf_graph_opts* o) {
     o->min_model_fidelity = 0.0;
     o->synchronous_staging = 0;
     o->max_far_factors = 0;      // = VF_MAX_FAR_LIMIT
+    o->far_covariance = 0;
 }
 // (the caller's struct may be shorter than the library's: include/vilfusion.h "struct_size")
 void vf_graph_default_opts_sized(vf_graph_opts* o, uint32_t struct_size) {
@@ -494,6 +495,7 @@ int vf_graph_get_staged(vf_graph* g, int index, int* kind, uint64_t* key1, uint6
 // (weak: the handle is also linked against a device-free engine double that predates these two -- tests/native/fake_engine.cpp;
 // in libvilfusion.so they are always defined)
 #pragma weak vf_engine_marginals
+#pragma weak vf_engine_marginals_ex
 #pragma weak vf_engine_read_marginals
 // the covariance of a solved key; the caller holds state_mutex
 static int marginal_covariance(vf_graph* g, uint64_t key, double* cov225) {
@@ -503,7 +505,12 @@ static int marginal_covariance(vf_graph* g, uint64_t key, double* cov225) {
     if (key < g->key_base + (uint64_t)g->lo)
         return gerr(VF_ERR_BAD_KEY, "key %llu has left the window (oldest key %llu)", (unsigned long long)key, (unsigned long long)(g->key_base + (uint64_t)g->lo));
     if (!g->cov_valid) {
-        if (int rc = vf_engine_marginals(g->eng)) return rc;
+        // (far_covariance: far factors alive, loop closures and what the marginalisation has left of them, downdate the band's
+        // covariances; without it they are refused as they always were)
+        if (g->opts.far_covariance) {
+            if (!vf_engine_marginals_ex) return gerr(VF_ERR_INVALID, "this engine has no far-factor marginal covariances");
+            if (int rc = vf_engine_marginals_ex(g->eng, VF_MARGINALS_FAR)) return rc;
+        } else if (int rc = vf_engine_marginals(g->eng)) return rc;
         g->cov_valid = true;
     }
     return vf_engine_read_marginals(g->eng, 0, (int)(key - g->key_base), 1, cov225, nullptr);

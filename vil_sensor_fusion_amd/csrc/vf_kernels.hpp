@@ -319,6 +319,16 @@ void launch_count_active(const View& v, hipStream_t s);
 constexpr int SIG_SLOT = 120 + 225;
 void launch_band_factor(const View& v, const SolvePlan& plan, hipStream_t s);
 void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s);
+// ... with far factors alive (vf_engine_marginals_ex, VF_MARGINALS_FAR): the low-rank downdate of sig (k4_selinv_far.inc) for the
+// windows [w0, w0 + nw), whose scratch FarCov holds; m = 6 x slots in use
+struct FarCov {
+    double* Z;          // [nw][M][15][m]   Z = A^-1 U: column q of window w0 + i at Z + i zwin, entry (slot k, dof d) at (15 k + d) m + q
+    double* C;          // [nw][m][m]       C = I + U^T Z and its Cholesky factor R (lower, row-major, leading dimension m) at C + i cwin
+    int* failed;        // [B]              the marginals' failure flags (set for a window whose C is not positive definite)
+    int w0, m, slots;
+    size_t zwin, cwin;
+};
+void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStream_t s);
 void launch_retract(const View& v, hipStream_t s);
 void launch_model_change(const View& v, hipStream_t s);     // View::model of every window, from g and the increment just solved
 void launch_decide(const View& v, int init, hipStream_t s);

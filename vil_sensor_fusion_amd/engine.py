@@ -371,10 +371,15 @@ class Engine:
         check(self._l.vf_engine_read_panels(self._h, window, k0, n, _d(p)))
         return p
 
-    def marginals(self):
+    def marginals(self, far=False):
         """Enqueue the marginal covariances of every window's keyframes at the current states (vf_engine_marginals): undamped
-        factorisation + selected inversion.  Leaves the LM state as it was; read them with read_marginals."""
-        check(self._l.vf_engine_marginals(self._h))
+        factorisation + selected inversion.  Leaves the LM state as it was; read them with read_marginals.  far=True
+        (vf_engine_marginals_ex with VF_MARGINALS_FAR): far factors alive, linear ones included, correct the covariances by a
+        low-rank downdate instead of being refused."""
+        if far:
+            check(self._l.vf_engine_marginals_ex(self._h, _lib.MARGINALS_FAR))
+        else:
+            check(self._l.vf_engine_marginals(self._h))
 
     def read_marginals(self, window, k0, n, cross=False):
         """Sigma_kk of keyframes k0 .. k0+n-1 as (n, 15, 15); with cross=True also Sigma_{k+1,k} (n, 15, 15), row = dof of k+1.

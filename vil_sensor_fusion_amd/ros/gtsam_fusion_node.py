@@ -60,7 +60,9 @@ class FusionNode:
                                                    iterations=int(P("solver/iterations", 5)), device=int(P("solver/device", 0)),
                                                    rel_tol=tol("rel_tol"), abs_tol=tol("abs_tol"),
                                                    # loop closures / wide between factors alive at once (32, the library's default and its limit, unless set lower)
-                                                   max_far_factors=(int(P("solver/max_far_factors", 0)) or None))
+                                                   max_far_factors=(int(P("solver/max_far_factors", 0)) or None),
+                                                   # covariances with loop closures alive (~publish_covariance; default false: none then)
+                                                   far_covariance=bool(P("solver/far_covariance", False)))
         x0 = rospy.get_param("~solver/initial_state", [])
         if graph_manager is None and len(x0) == 16:
             self.graph.setInitialState(x0)
