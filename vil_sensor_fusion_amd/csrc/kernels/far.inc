@@ -52,30 +52,11 @@ __global__ void __launch_bounds__(64) k_extra_gradient(View v) {
     const int w = blockIdx.x, lane = threadIdx.x;
     if (!v.fresh[w] || window_done(v, w)) return;
     const int b = v.sel[w];
-    __shared__ int kb_l[MAX_EXTRA_BIG];                // far ends of the linear far factor (every linear slot's columns 27.. lie on them)
-    if (lane < v.x_max) kb_l[lane] = v.xl_b[w * v.x_max + lane];
-    __syncthreads();
+    __shared__ int kb_l[MAX_EXTRA_BIG];
+    far_ends(v, w, lane, kb_l);
     for (int s = 0; s < v.x_max; s++) {              // sequential over the slots: two factors may share a keyframe
         const FarRef f = far_ref(v, w, s);
-        const int nc = f.kind >= 0 ? far_cols(f) : 0;
-        for (int c0 = 0; c0 < nc; c0 += 64) {        // (and over the column groups: two far ends may be the same keyframe)
-            const int c = c0 + lane;
-            if (c < nc) {
-                int k, d;
-                far_col(v, w, f, c, k, d);
-                double acc = 0.0;
-                for (int r = 0; r < 6; r++) acc = fma(far_jac(v, w, f, b, r, c), far_res(v, w, f, b, r), acc);
-                bool first = true;                   // of the columns that land on this (keyframe, dof): far-end columns only
-                if (f.kind == 1 && c >= 27)
-                    for (int c2 = 27 + d; c2 < nc; c2 += 6) {
-                        if (c2 == c || kb_l[(c2 - 27) / 6] != k) continue;
-                        if (c2 < c) { first = false; break; }
-                        for (int r = 0; r < 6; r++) acc = fma(far_jac(v, w, f, b, r, c2), far_res(v, w, f, b, r), acc);
-                    }
-                if (first) v.gvec[((size_t)w * v.M + k) * 15 + d] += acc;
-            }
-            __syncthreads();
-        }
+        far_jt_apply(v, w, f, b, lane, kb_l, [&](int r) { return far_res(v, w, f, b, r); }, v.gvec);
     }
 }
 // right-hand side number (s, j) of the low-rank correction: row j of the far factor in slot s of every window, scattered
@@ -83,14 +64,7 @@ __global__ void __launch_bounds__(64) k_extra_gradient(View v) {
 __global__ void __launch_bounds__(64) k_extra_rhs(View v, int s, int j, double* __restrict__ gtmp) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= v.B || window_done(v, w)) return;
-    const FarRef f = far_ref(v, w, s);
-    if (f.kind < 0) return;
-    const int b = v.sel[w], nc = far_cols(f);
-    for (int c = 0; c < nc; c++) {
-        int k, d;
-        far_col(v, w, f, c, k, d);
-        gtmp[((size_t)w * v.M + k) * 15 + d] += far_jac(v, w, f, b, j, c);
-    }
+    far_scatter<false>(v, w, far_ref(v, w, s), v.sel[w], j, gtmp + (size_t)w * v.M * 15, 1);
 }
 // ---- the Woodbury columns of a SINGLE-window engine as one batch (vf_engine.hip "far_columns"): window q of the view `c` (an
 // engine of 6 x MAX_EXTRA windows with the same capacity) is a copy of the window's block rows of H with column q of U as its
@@ -113,14 +87,7 @@ __global__ void __launch_bounds__(256) k_cols_prepare(View v, View c, int ncols)
 __global__ void __launch_bounds__(64) k_cols_rhs(View v, View c, int ncols) {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= ncols || window_done(v, 0)) return;
-    const FarRef f = far_ref(v, 0, q / 6);
-    if (f.kind < 0) return;
-    const int b = v.sel[0], nc = far_cols(f), j = q % 6;
-    for (int col = 0; col < nc; col++) {
-        int k, d;
-        far_col(v, 0, f, col, k, d);
-        c.gvec[((size_t)q * c.M + k) * 15 + d] += far_jac(v, 0, f, b, j, col);
-    }
+    far_scatter<false>(v, 0, far_ref(v, 0, q / 6), v.sel[0], q % 6, c.gvec + (size_t)q * c.M * 15, 1);
 }
 __global__ void __launch_bounds__(64) k_cols_fail(View v, View c, int ncols) {
     const int q = blockIdx.x * 64 + threadIdx.x;
@@ -144,27 +111,19 @@ constexpr size_t SMALL_SCRATCH = 64;     // doubles of far_scratch per window on
 constexpr size_t BIG_CVEC = (size_t)6 * MAX_EXTRA_BIG * BIG_LD;     // offset of the solution (6 MAX_EXTRA_BIG doubles) in far_scratch
 static_assert(BIG_CVEC + 6 * MAX_EXTRA_BIG <= FAR_SCRATCH, "far_scratch holds the Woodbury system and its solution");
 __global__ void __launch_bounds__(256) k_extra_fill(View v, const double* __restrict__ Zm, size_t zstride, int slots) {
-    constexpr int NCMAX = 27 + 6 * MAX_EXTRA_BIG;
-    __shared__ double J[6 * NCMAX];
-    __shared__ int off[NCMAX];
+    __shared__ double J[6 * FAR_NCMAX];
+    __shared__ int off[FAR_NCMAX];
     const int s = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
     if (v.hi[w] - v.lo[w] <= 0 || window_done(v, w)) return;
     double* const C = v.far_scratch + (size_t)w * FAR_SCRATCH;
     const int m = 6 * slots, b = v.sel[w];
-    const FarRef f = far_ref(v, w, s);
-    const int nc = f.kind >= 0 ? far_cols(f) : 0;
-    for (int c = tid; c < nc; c += 256) {
-        int k, d;
-        far_col(v, w, f, c, k, d);
-        off[c] = k * 15 + d;
-        for (int j = 0; j < 6; j++) J[j * NCMAX + c] = far_jac(v, w, f, b, j, c);
-    }
+    const int nc = far_stage<false>(v, w, far_ref(v, w, s), b, tid, 256, J, off);
     __syncthreads();
     for (int e = tid; e < 6 * (m + 1); e += 256) {
         const int j = e / (m + 1), q = e - j * (m + 1), p = 6 * s + j;
         const double* col = (q < m ? Zm + (size_t)q * zstride : v.delta) + (size_t)w * v.M * 15;
         double acc = 0.0;
-        for (int c = 0; c < nc; c++) acc = fma(J[j * NCMAX + c], col[off[c]], acc);
+        for (int c = 0; c < nc; c++) acc = fma(J[j * FAR_NCMAX + c], col[off[c]], acc);
         C[p * BIG_LD + q] = q < m ? (p == q ? 1.0 : 0.0) - acc : acc;
     }
 }

@@ -27,16 +27,10 @@ VF_DI bool farcov_skip(const View& v, const FarCov& fc, int w) {
 __global__ void __launch_bounds__(256) k_farcov_rhs(View v, FarCov fc) {
     const int w = fc.w0 + blockIdx.x, q = threadIdx.x, m = fc.m;
     if (q >= m || farcov_skip(v, fc, w)) return;
-    const int lo = v.lo[w], hi = v.hi[w], b = v.sel[w];
+    const int lo = v.lo[w], hi = v.hi[w];
     double* __restrict__ Z = fc.Z + (size_t)blockIdx.x * fc.zwin;
     for (int i = lo * 15; i < hi * 15; i++) Z[(size_t)i * m + q] = 0.0;
-    const FarRef f = far_ref(v, w, q / 6);
-    const int nc = f.kind >= 0 ? far_cols(f) : 0;
-    for (int c = 0; c < nc; c++) {
-        int k, d;
-        far_col(v, w, f, c, k, d);
-        if (k >= lo && k < hi) Z[((size_t)k * 15 + d) * m + q] += far_jac(v, w, f, b, q % 6, c);
-    }
+    far_scatter<true>(v, w, far_ref(v, w, q / 6), v.sel[w], q % 6, Z + q, (size_t)m);
 }
 // Z = A^-1 U on the panels of the undamped sweep, as two launches of one wave per (window, 64 columns), a lane per column:
 //   k_farcov_forward  y_k = L_kk^-1 (u_k - the B updates of k-1 .. k-3) = U_k^T r_k, then the updates of S_k: B_k y_k
@@ -169,13 +163,12 @@ __global__ void __launch_bounds__(64) k_farcov_back(View v, FarCov fc) {
 // slot's six rows staged in LDS), then C = R R^T by right-looking Cholesky, entry-parallel.  BIG: C in the window's part of
 // FarCov::C throughout; else in LDS, R copied there at the end.  Every entry takes the same chain of operations in both forms,
 // so they give the same bits.
-constexpr int FC_NCMAX = 27 + 6 * MAX_EXTRA_BIG;
 template <bool BIG>
 __global__ void __launch_bounds__(256) k_farcov_chol(View v, FarCov fc) {
     constexpr int MM = 6 * MAX_EXTRA, NT = 256;
     __shared__ double C_lds[BIG ? 1 : MM * MM];
-    __shared__ double J[6 * FC_NCMAX];
-    __shared__ int off[FC_NCMAX];
+    __shared__ double J[6 * FAR_NCMAX];
+    __shared__ int off[FAR_NCMAX];
     const int w = fc.w0 + blockIdx.x, tid = threadIdx.x, m = fc.m;
     if (farcov_skip(v, fc, w)) return;
     const int b = v.sel[w];
@@ -183,22 +176,15 @@ __global__ void __launch_bounds__(256) k_farcov_chol(View v, FarCov fc) {
     double* const Rg = fc.C + (size_t)blockIdx.x * fc.cwin;
     double* const C = BIG ? Rg : C_lds;
     for (int s = 0; s < fc.slots; s++) {
-        const FarRef f = far_ref(v, w, s);
-        const int nc = f.kind >= 0 ? far_cols(f) : 0;
         __syncthreads();
-        for (int c = tid; c < nc; c += NT) {
-            int k, d;
-            far_col(v, w, f, c, k, d);
-            off[c] = k >= v.lo[w] && k < v.hi[w] ? k * 15 + d : -1;     // (never outside the window: a guard, as in the scatter)
-            for (int j = 0; j < 6; j++) J[j * FC_NCMAX + c] = far_jac(v, w, f, b, j, c);
-        }
+        const int nc = far_stage<true>(v, w, far_ref(v, w, s), b, tid, NT, J, off);
         __syncthreads();
         for (int q = tid; q < 6 * s + 6; q += NT) {
             double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (int c = 0; c < nc; c++) {
                 const double z = off[c] >= 0 ? Z[(size_t)off[c] * m + q] : 0.0;
 #pragma unroll
-                for (int j = 0; j < 6; j++) acc[j] = fma(J[j * FC_NCMAX + c], z, acc[j]);
+                for (int j = 0; j < 6; j++) acc[j] = fma(J[j * FAR_NCMAX + c], z, acc[j]);
             }
 #pragma unroll
             for (int j = 0; j < 6; j++) {
@@ -283,7 +269,7 @@ void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStre
     hipLaunchKernelGGL(k_farcov_rhs, dim3((unsigned)nw), dim3(64 * cb), 0, s, v, fc);
     hipLaunchKernelGGL(k_farcov_forward, dim3((unsigned)nw, cb), dim3(64), 0, s, v, fc);
     hipLaunchKernelGGL(k_farcov_back, dim3((unsigned)nw, cb), dim3(64), 0, s, v, fc);
-    if (fc.slots > MAX_EXTRA || v.far_big) hipLaunchKernelGGL(k_farcov_chol<true>, dim3((unsigned)nw), dim3(256), 0, s, v, fc);
+    if (far_big_form(v, fc.slots)) hipLaunchKernelGGL(k_farcov_chol<true>, dim3((unsigned)nw), dim3(256), 0, s, v, fc);
     else hipLaunchKernelGGL(k_farcov_chol<false>, dim3((unsigned)nw), dim3(256), 0, s, v, fc);
     hipLaunchKernelGGL(k_farcov_downdate, dim3((unsigned)v.M, (unsigned)nw), dim3(64), (size_t)FC_YROWS * (fc.m + 1) * sizeof(double), s,
                        v, fc, sig);

@@ -23,10 +23,8 @@ void launch_extra_gradient(const View& v, hipStream_t s) {
 void launch_extra_rhs(const View& v, int slot, int row, double* gtmp, hipStream_t s) {
     hipLaunchKernelGGL(k_extra_rhs, dim3(nblk(v.B, 64)), dim3(64), 0, s, v, slot, row, gtmp);
 }
-// (the form follows the slots IN USE, not the engine's capacity: an engine made for 32 far factors that holds eight or fewer takes
-// the LDS forms -- the lists are compact, so what is there sits in the first slots -- and gets the same bits either way)
 void launch_extra_combine(const View& v, const double* Zm, size_t zstride, int slots, hipStream_t s) {
-    if (slots > MAX_EXTRA || v.far_big) {
+    if (far_big_form(v, slots)) {
         hipLaunchKernelGGL(k_extra_fill, dim3((unsigned)slots, (unsigned)v.B), dim3(256), 0, s, v, Zm, zstride, slots);
         hipLaunchKernelGGL(k_extra_combine<true>, dim3(v.B), dim3(1024), 0, s, v, Zm, zstride, slots);
         hipLaunchKernelGGL(k_extra_apply<true>, dim3(nblk((long)v.M * 15, 256), (unsigned)v.B), dim3(256), 0, s, v, Zm, zstride, slots);
@@ -257,9 +255,10 @@ void launch_marg_commit(const View& v, const double* stash, hipStream_t s) {
     hipLaunchKernelGGL(k_marg_commit, dim3(v.B), dim3(256), 0, s, v, stash);
 }
 void launch_marginalize(const View& v, int slots, int* status, hipStream_t s) {
-    if (slots > MAX_EXTRA || (v.far_big && v.x_max > 0)) hipLaunchKernelGGL(k_marginalize<2>, dim3(v.B), dim3(1024), 0, s, v, status, (double*)nullptr);
-    else if (v.x_max > 0) hipLaunchKernelGGL(k_marginalize<1>, dim3(v.B), dim3(256), 0, s, v, status, (double*)nullptr);
-    else hipLaunchKernelGGL(k_marginalize<0>, dim3(v.B), dim3(256), 0, s, v, status, (double*)nullptr);
+    // (an engine without far capacity holds no slots and never has far_big set)
+    if (v.x_max == 0) hipLaunchKernelGGL(k_marginalize<0>, dim3(v.B), dim3(256), 0, s, v, status, (double*)nullptr);
+    else if (far_big_form(v, slots)) hipLaunchKernelGGL(k_marginalize<2>, dim3(v.B), dim3(1024), 0, s, v, status, (double*)nullptr);
+    else hipLaunchKernelGGL(k_marginalize<1>, dim3(v.B), dim3(256), 0, s, v, status, (double*)nullptr);
 }
 void launch_shift_copy(const double* src, double* dst, long n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_shift_copy, dim3(nblk(n, 256)), dim3(256), 0, s, src, dst, n);

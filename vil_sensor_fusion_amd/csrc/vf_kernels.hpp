@@ -249,6 +249,10 @@ struct View {
     double wildfire;    // back substitution: an increment that changes by at most this in every component counts as unchanged
 };
 __host__ __device__ inline int xl_ld(const View& v) { return 27 + 6 * v.x_max; }   // row stride of View::xl_U
+// Do the dense far systems (the Woodbury combine, the marginals' C, the joint marginalisation) take their device-memory form?  The
+// form follows the slots IN USE, not the engine's capacity: an engine made for 32 far factors that holds eight or fewer takes the
+// LDS forms -- the lists are compact, so what is there sits in the first slots -- and gets the same bits either way.
+inline bool far_big_form(const View& v, int slots) { return slots > MAX_EXTRA || v.far_big; }
 constexpr int CK_LOG = 3, CK = 1 << CK_LOG;       // a checkpoint every 8 keyframe slots
 constexpr int CK_SZ = 768;                        // 27 x 28 doubles (SEPM), padded
 // first keyframe slot the incremental forward sweep eliminates again, given the first changed slot: a factor reaches three

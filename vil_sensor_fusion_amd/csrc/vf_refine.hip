@@ -184,9 +184,8 @@ __global__ void __launch_bounds__(64) k_far_apply(View v, Refine q, const double
     if (v.hi[w] - v.lo[w] <= 0 || refine_off(v, q, w)) return;
     const int b = v.sel[w];
     __shared__ double u[6];
-    __shared__ int kb_l[MAX_EXTRA_BIG];                // far ends of the linear far factor (every linear slot's columns 27.. lie on them)
-    if (lane < v.x_max) kb_l[lane] = v.xl_b[w * v.x_max + lane];
-    __syncthreads();
+    __shared__ int kb_l[MAX_EXTRA_BIG];
+    far_ends(v, w, lane, kb_l);
     for (int s = 0; s < v.x_max; s++) {
         const FarRef f = far_ref(v, w, s);
         if (f.kind < 0) continue;                    // (the same for every lane)
@@ -202,24 +201,7 @@ __global__ void __launch_bounds__(64) k_far_apply(View v, Refine q, const double
             u[lane] = acc;
         }
         __syncthreads();
-        for (int c0 = 0; c0 < nc; c0 += 64) {
-            const int c = c0 + lane;
-            if (c < nc) {
-                int k, d;
-                far_col(v, w, f, c, k, d);
-                double acc = 0.0;
-                for (int r = 0; r < 6; r++) acc = fma(far_jac(v, w, f, b, r, c), u[r], acc);
-                bool first = true;
-                if (f.kind == 1 && c >= 27)
-                    for (int c2 = 27 + d; c2 < nc; c2 += 6) {
-                        if (c2 == c || kb_l[(c2 - 27) / 6] != k) continue;
-                        if (c2 < c) { first = false; break; }
-                        for (int r = 0; r < 6; r++) acc = fma(far_jac(v, w, f, b, r, c2), u[r], acc);
-                    }
-                if (first) out[((size_t)w * v.M + k) * 15 + d] += acc;
-            }
-        }
-        __syncthreads();
+        far_jt_apply(v, w, f, b, lane, kb_l, [&](int r) { return u[r]; }, out);      // (its last barrier: u is free again)
     }
 }
 
