@@ -50,3 +50,24 @@ def test_staged_graph_host_logic(tmp_path):
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     print(p.stdout, p.stderr[-2000:])
     assert p.returncode == 0 and "graph_staged ok" in p.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_solve_makes_the_recorded_engine_calls(tmp_path):
+    """What the engine sees of vf_solve: tests/native/graph_trace.cpp walks a handle through the cases vf_solve distinguishes
+    (growth, marginalisation and compaction, band factors out of order, far factors taken over by the engine, late odometry of
+    every kind, a refused preintegration, sticky flags, records mixed with reserved nodes, synchronous staging, reference_compat,
+    covariance callbacks, the far-factor limit) against the engine double with its call log on, and prints every return code,
+    message, staged factor, engine call and callback.  The output is compared byte for byte with tests/golden/graph_trace.txt,
+    which was recorded from vf_graph.cpp as it was BEFORE vf_solve was split into steps (regenerate: see the driver's header)."""
+    exe = tmp_path / "graph_trace"
+    srcs = [os.path.join(ROOT, "tests", "native", "graph_trace.cpp"), os.path.join(ROOT, "tests", "native", "fake_engine.cpp"),
+            os.path.join(ROOT, "vil_sensor_fusion_amd", "csrc", "vf_graph.cpp")]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-o", str(exe)] + srcs)
+    p = subprocess.run([str(exe)], capture_output=True, timeout=120)
+    with open(os.path.join(ROOT, "tests", "golden", "graph_trace.txt"), "rb") as f:
+        golden = f.read()
+    assert p.returncode == 0, p.stderr[-2000:]
+    got, want = p.stdout.splitlines(), golden.splitlines()
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    assert p.stdout == golden, f"line {first + 1}: got {got[first:first + 1]}, recorded {want[first:first + 1]}"

@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -38,6 +37,32 @@ struct PendingImu {            // one queued CombinedImuFactor (GraphManager::_i
 struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device = false; };
 // a between factor as the caller handed it in: what GraphManager::graph() shows until the next solve (vf_graph_get_staged)
 struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; };
+
+struct LateFactor { bool any = false; uint64_t a = 0, b = 0; };   // the first between factor a solve has dropped as late odometry
+// what one vf_solve took from the handle (take), as its steps have left it, and what they decided (give_back, publish_far_list)
+struct SolveTake {
+    std::deque<PendingImu> imus;
+    std::vector<PendingBetween> betweens, fars;
+    size_t fars_snapshot = 0;               // length of the handle's far list when `fars` was copied: what is behind it was added since
+    int staged = 0, far_new = 0;            // the handle's counts, less what was dropped as late
+    std::vector<StagedFactor> log;
+    bool priors = false, marginalised = false;   // (marginalised: this solve has moved the window's oldest key)
+    uint64_t last_key = 0;
+    double last_time = 0.0;
+    LateFactor late_far, late_band;         // dropped: a far factor that was late when the solve began; a band factor (its end key is to be unmarked)
+    bool fars_changed = false;              // `fars` is no longer what the handle's list holds
+    bool requeue = false;                   // the solve failed before the optimisation: everything goes back
+};
+
+struct Lap {   // VF_SOLVE_TIMING: "[vf_solve] <label> <us>" on stderr behind every step of a solve (tools/gm_lap_summary.py reads the labels)
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        static const bool timing = getenv("VF_SOLVE_TIMING") != nullptr;
+        const auto now = timing ? std::chrono::steady_clock::now() : last;
+        if (timing) fprintf(stderr, "[vf_solve] %-12s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - last).count());
+        last = now;
+    }
+};
 
 // R upper-triangular, R^T R = cov^-1 (noiseModel::Gaussian::Covariance, SensorManagerRos.cpp:99).
 // 6x6 noise-model construction is factor *construction*, done once per measurement on the host
@@ -492,324 +517,299 @@ int vf_graph_get_staged(vf_graph* g, int index, int* kind, uint64_t* key1, uint6
     return VF_OK;
 }
 
-// (weak: the handle is also linked against a device-free engine double that predates these two -- tests/native/fake_engine.cpp;
-// in libvilfusion.so they are always defined)
-#pragma weak vf_engine_marginals
-#pragma weak vf_engine_marginals_ex
-#pragma weak vf_engine_read_marginals
+static int slot_of(const vf_graph* g, uint64_t key) { return (int)(key - g->key_base); }
+static uint64_t oldest_key(const vf_graph* g) { return g->key_base + (uint64_t)g->lo; }
+// a far factor the engine can take: both keys inside the window
+static bool in_window(const vf_graph* g, const PendingBetween& f, uint64_t last_key) { return f.a >= oldest_key(g) && f.b <= last_key; }
 // the covariance of a solved key; the caller holds state_mutex
 static int marginal_covariance(vf_graph* g, uint64_t key, double* cov225) {
-    if (!vf_engine_marginals || !vf_engine_read_marginals) return gerr(VF_ERR_INVALID, "this engine has no marginal covariances");
     if (!g->solved_once) return gerr(VF_ERR_INVALID, "no solve yet: there is no covariance to report");
     if (key > g->solved_key) return gerr(VF_ERR_BAD_KEY, "key %llu not solved yet (last solved key %llu)", (unsigned long long)key, (unsigned long long)g->solved_key);
-    if (key < g->key_base + (uint64_t)g->lo)
-        return gerr(VF_ERR_BAD_KEY, "key %llu has left the window (oldest key %llu)", (unsigned long long)key, (unsigned long long)(g->key_base + (uint64_t)g->lo));
+    if (key < oldest_key(g)) return gerr(VF_ERR_BAD_KEY, "key %llu has left the window (oldest key %llu)", (unsigned long long)key, (unsigned long long)oldest_key(g));
     if (!g->cov_valid) {
         // (far_covariance: far factors alive, loop closures and what the marginalisation has left of them, downdate the band's
         // covariances; without it they are refused as they always were)
-        if (g->opts.far_covariance) {
-            if (!vf_engine_marginals_ex) return gerr(VF_ERR_INVALID, "this engine has no far-factor marginal covariances");
-            if (int rc = vf_engine_marginals_ex(g->eng, VF_MARGINALS_FAR)) return rc;
-        } else if (int rc = vf_engine_marginals(g->eng)) return rc;
+        if (int rc = g->opts.far_covariance ? vf_engine_marginals_ex(g->eng, VF_MARGINALS_FAR) : vf_engine_marginals(g->eng)) return rc;
         g->cov_valid = true;
     }
-    return vf_engine_read_marginals(g->eng, 0, (int)(key - g->key_base), 1, cov225, nullptr);
+    return vf_engine_read_marginals(g->eng, 0, slot_of(g, key), 1, cov225, nullptr);
 }
-
-int vf_solve(vf_graph* g) {
-    if (!g) return gerr(VF_ERR_INVALID, "null argument");
-    static const bool timing = getenv("VF_SOLVE_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_a = now();
-    auto lap = [&](const char* what) { if (timing) { auto t_b = now(); fprintf(stderr, "[vf_solve] %-12s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t_b - t_a).count()); t_a = t_b; } };
-    // ---- under _graphMutex: emptyImuQueue + snapshot of the staged factors (GraphManager.cpp:104-114)
-    std::deque<PendingImu> imus;
-    std::vector<PendingBetween> betweens, fars;
-    uint64_t last_key;
-    double last_time;
-    int staged_before, far_new_before = 0;
-    std::vector<StagedFactor> log_before;
-    bool priors_before = false;
-    bool fars_changed = false;
-    size_t fars_snapshot = 0;
-    bool late_far = false;          // a far factor added since the last solve whose older key had already left the window
-    unsigned long long late_a = 0, late_b = 0;
-    int late_n = 0;
-    std::lock_guard<std::mutex> solve_lk(g->solve_mutex);
-    {
-        std::lock_guard<std::mutex> lk(g->graph_mutex);
-        imus.swap(g->imu_queue);
-        betweens.swap(g->staged_between);
-        for (const auto& bt : betweens) g->set_band_end(bt.b, 1);   // these keys now carry their band factor (a second one goes to the far list)
-        // (keys below the window can never be named again by a factor that is accepted: their marks are let go)
-        while (!g->band_end.empty() && g->band_base < g->key_base + (uint64_t)g->lo) { g->band_end.pop_front(); g->band_base++; }
-        // A far factor whose older key has left the window (as of the previous solve: lo / key_base change under solve_mutex,
-        // which this thread holds) is no business of this list: one that was on the device then was marginalised with its key and
-        // lives on in the engine (the list was replaced after that solve's marginalisations); one that was added SINCE that
-        // solve never made it into the window -- late odometry, reported like a late band factor below
-        {
-            const uint64_t oldest = g->key_base + (uint64_t)g->lo;
-            auto& fb = g->far_between;
-            for (size_t i = fb.size() - (size_t)g->far_new; i < fb.size(); i++)
-                if (fb[i].a < oldest) {
-                    if (!late_far) { late_a = fb[i].a; late_b = fb[i].b; }
-                    late_far = true;
-                    late_n++;
-                    for (size_t j = 0; j < g->staged_log.size(); j++)      // (dropped: it leaves graph()'s list as well)
-                        if (g->staged_log[j].a == fb[i].a && g->staged_log[j].b == fb[i].b) { g->staged_log.erase(g->staged_log.begin() + (long)j); break; }
-                }
-            fb.erase(std::remove_if(fb.begin(), fb.end(), [&](const PendingBetween& f) { return f.a < oldest; }), fb.end());
+// Late odometry: a between factor whose older key is below the window's oldest key can never be added.  It is dropped -- from its
+// list, from the staged log it is in (graph()'s list), from the counts --, the caller is told once, the rest is given back.
+static bool is_late(const PendingBetween& f, uint64_t oldest) { return f.a < oldest; }
+static void drop_late(std::vector<PendingBetween>& list, size_t i, std::vector<StagedFactor>& log, int& staged, int* far_new, LateFactor& first) {
+    if (!first.any) first = {true, list[i].a, list[i].b};
+    for (size_t j = 0; j < log.size(); j++)
+        if (log[j].a == list[i].a && log[j].b == list[i].b) { log.erase(log.begin() + (long)j); break; }
+    list.erase(list.begin() + (long)i);
+    staged--;
+    if (far_new) --*far_new;
+}
+static int late_error(const LateFactor& f, const char* when, uint64_t oldest) {
+    return gerr(VF_ERR_BAD_KEY, "between factor (%llu, %llu) dropped: key %llu left the fixed-lag window%s (oldest key %llu)", (unsigned long long)f.a,
+                (unsigned long long)f.b, (unsigned long long)f.a, when, (unsigned long long)oldest);
+}
+// take / give_back / publish_far_list: lock order is graph -> state everywhere (vf_reserve_node, vf_set_initial_state;
+// GraphManager.cpp:54,60 -> 176), and the reference's solve() has released _graphMutex before it takes _stateMutex (:104-117): the
+// three take graph_mutex themselves, before / after the state lock, never while it is held.  A solve that fails before the
+// optimisation has run must not lose what it took from the queues: every step up to vf_engine_iterate is idempotent on the
+// device (the same records, predictions and ranges are written again), so the take goes back to the FRONT of the queues and the
+// next vf_solve repeats it.  solve_mutex (taken first, by vf_solve only) keeps a second solver from taking newer entries between
+// the failure and the give-back.
+// under _graphMutex: emptyImuQueue + snapshot of the staged factors (GraphManager.cpp:104-114)
+static void take(vf_graph* g, SolveTake& t) {
+    std::lock_guard<std::mutex> lk(g->graph_mutex);
+    t.imus.swap(g->imu_queue);
+    t.betweens.swap(g->staged_between);
+    for (const auto& bt : t.betweens) g->set_band_end(bt.b, 1);   // these keys now carry their band factor (a second one goes to the far list)
+    // (keys below the window can never be named again by a factor that is accepted: their marks are let go)
+    while (!g->band_end.empty() && g->band_base < oldest_key(g)) { g->band_end.pop_front(); g->band_base++; }
+    // A far factor whose older key has left the window (as of the previous solve: lo / key_base change under solve_mutex,
+    // which this thread holds) is no business of this list: one that was on the device then was marginalised with its key and
+    // lives on in the engine (the list was replaced after that solve's marginalisations); one that was added SINCE that solve
+    // never made it into the window.  Late odometry: the new ones only, all at once, reported by the first (refuse_late)
+    const uint64_t oldest = oldest_key(g);
+    auto& fb = g->far_between;
+    for (size_t i = fb.size() - (size_t)g->far_new; i < fb.size();)
+        if (is_late(fb[i], oldest)) drop_late(fb, i, g->staged_log, g->staged_count, &g->far_new, t.late_far);
+        else i++;
+    fb.erase(std::remove_if(fb.begin(), fb.end(), [oldest](const PendingBetween& f) { return is_late(f, oldest); }), fb.end());
+    t.fars = fb;
+    t.fars_snapshot = fb.size();
+    std::swap(t.far_new, g->far_new);
+    std::swap(t.staged, g->staged_count);  // _graph->resize(0)
+    t.log.swap(g->staged_log);
+    std::swap(t.priors, g->priors_staged);
+    t.last_key = g->current_key, t.last_time = g->last_pose_time;
+}
+static void give_back(vf_graph* g, SolveTake& t) {
+    std::lock_guard<std::mutex> lk(g->graph_mutex);
+    for (auto it = t.imus.rbegin(); it != t.imus.rend(); ++it) g->imu_queue.push_front(std::move(*it));
+    g->staged_between.insert(g->staged_between.begin(), t.betweens.begin(), t.betweens.end());
+    g->staged_count += t.staged;
+    g->staged_log.insert(g->staged_log.begin(), t.log.begin(), t.log.end());
+    g->priors_staged = g->priors_staged || t.priors;
+    // the far factors added since the last successful solve are still "new" for the solve that repeats this one (its
+    // late-odometry test looks at the new ones only), and a band factor dropped as late leaves its end key free again
+    g->far_new += t.far_new;
+    if (t.late_band.any) g->set_band_end(t.late_band.b, 0);
+}
+// the entries taken are the front of the list (others only append, under graph_mutex): replace them by their current form
+// (the ones the engine has taken over are gone; on_device marks)
+static void publish_far_list(vf_graph* g, SolveTake& t) {
+    std::lock_guard<std::mutex> lk(g->graph_mutex);
+    if (g->far_between.size() < t.fars_snapshot) return;
+    std::vector<PendingBetween> now(t.fars);
+    now.insert(now.end(), g->far_between.begin() + (long)t.fars_snapshot, g->far_between.end());
+    g->far_between.swap(now);
+}
+// The steps of a solve, in the order vf_solve runs them, under state_mutex.  Host-side validation first: late odometry
+static int refuse_late(vf_graph* g, SolveTake& t) {
+    const uint64_t oldest = oldest_key(g);
+    if (t.late_far.any) return late_error(t.late_far, "", oldest);
+    // band factors: the first late one only per solve; its end key carries no band factor after all (give_back clears the mark)
+    for (size_t i = 0; i < t.betweens.size(); i++)
+        if (is_late(t.betweens[i], oldest)) {
+            drop_late(t.betweens, i, t.log, t.staged, nullptr, t.late_band);
+            return late_error(t.late_band, "", oldest);
         }
-        fars = g->far_between;
-        fars_snapshot = fars.size();
-        far_new_before = g->far_new - late_n;      // (the late ones have just been erased and are reported below)
-        g->far_new = 0;
-        staged_before = g->staged_count - late_n;
-        g->staged_count = 0;  // _graph->resize(0)
-        log_before.swap(g->staged_log);
-        priors_before = g->priors_staged;
-        g->priors_staged = false;
-        last_key = g->current_key;
-        last_time = g->last_pose_time;
-    }
-    // Lock order is graph -> state everywhere (vf_reserve_node, vf_set_initial_state; GraphManager.cpp:54,60 -> 176), and the
-    // reference's solve() has released _graphMutex before it takes _stateMutex (:104-117).  A solve that fails before the
-    // optimisation has run must not lose what it took from the queues: every step up to vf_engine_iterate is idempotent
-    // on the device (the same records, predictions and ranges are written again), so the snapshots go back to the FRONT
-    // of the queues and the next vf_solve repeats them -- AFTER the state lock is released (requeue below), never
-    // while it is held.  solve_mutex (taken first, by vf_solve only) keeps a second solver from snapshotting newer
-    // entries between the failure and the give-back.
-    bool requeue = false, late_band = false;
-    uint64_t late_band_key = 0, late_band_a = 0;
-    auto give_back = [&](int code) { requeue = true; return code; };
-    auto locked = [&]() -> int {
-    std::lock_guard<std::mutex> sl(g->state_mutex);  // :117
-    g->cov_valid = false;
-    int rc;
-    // host-side validation first: a between factor whose source keyframe has already left the fixed-lag window (late
-    // odometry) can never be added; it is dropped, the rest is given back, and the caller is told once
-    {
-        const uint64_t oldest = g->key_base + (uint64_t)g->lo;
-        if (late_far)
-            return give_back(gerr(VF_ERR_BAD_KEY, "between factor (%llu, %llu) dropped: key %llu left the fixed-lag window (oldest key %llu)",
-                        late_a, late_b, late_a, (unsigned long long)oldest));
-        for (size_t i = 0; i < betweens.size(); i++)
-            if (betweens[i].a < oldest) {
-                const unsigned long long a = betweens[i].a, b = betweens[i].b;
-                late_band_key = betweens[i].b;          // (its end key carries no band factor after all: requeue clears the mark)
-                late_band_a = betweens[i].a;
-                late_band = true;
-                betweens.erase(betweens.begin() + (long)i);
-                staged_before--;
-                return give_back(gerr(VF_ERR_BAD_KEY, "between factor (%llu, %llu) dropped: key %llu left the fixed-lag window (oldest key %llu)",
-                            a, b, a, (unsigned long long)oldest));
-            }
-    }
-    // whole-history mode (lag = 0, the reference's unbounded graph): the engine grows with the history
-    if (g->opts.lag == 0 && (int)(last_key - g->key_base) + 1 > g->opts.capacity) {
+    return VF_OK;
+}
+static int make_room(vf_graph* g, SolveTake& t, Lap& lap) {
+    if (slot_of(g, t.last_key) + 1 <= g->opts.capacity) return VF_OK;
+    if (g->opts.lag == 0) {
+        // whole-history mode (the reference's unbounded graph): the engine grows with the history
         int want = g->opts.capacity;
-        while ((int)(last_key - g->key_base) + 1 > want) want *= 2;
-        if ((rc = vf_engine_grow(g->eng, want))) return give_back(rc);
+        while (slot_of(g, t.last_key) + 1 > want) want *= 2;
+        if (int rc = vf_engine_grow(g->eng, want)) return rc;
         g->opts.capacity = want;
         lap("grow");
+        return VF_OK;
     }
     // fixed-lag mode: reclaim slots below the window when the new keyframes would not fit
-    if (g->opts.lag > 0 && (int)(last_key - g->key_base) + 1 > g->opts.capacity) {
-        const int shift = (g->lo / 64) * 64;
-        if (shift <= 0) return give_back(gerr(VF_ERR_CAPACITY, "capacity %d too small for lag %d plus the keyframes added per solve", g->opts.capacity, g->opts.lag));
-        if ((rc = vf_engine_compact(g->eng, shift))) return give_back(rc);
-        g->lo -= shift;
-        g->key_base += shift;
-        if ((int)(last_key - g->key_base) + 1 > g->opts.capacity) return give_back(gerr(VF_ERR_CAPACITY, "capacity %d exhausted even after compaction", g->opts.capacity));
-    }
-    // fixed-lag window: marginalise the keyframes that fall out of the lag, one at a time, at the
-    // linearisation of the previous solve (their factors have not changed since).  FIRST: the engine runs it on a second
-    // stream, beside the preintegration / prediction / staging of the keyframes that arrive (vf_engine_set_async)
-    const int last_slot = (int)(last_key - g->key_base);
-    bool marginalised = false;
-    while (g->opts.lag > 0 && last_slot + 1 - g->lo > g->opts.lag && (int)(g->solved_key - g->key_base) - g->lo >= 3) {
-        if ((rc = vf_engine_marginalize(g->eng))) return give_back(rc);
-        if ((rc = vf_engine_drop_oldest(g->eng))) return give_back(rc);
+    const int shift = (g->lo / 64) * 64;
+    if (shift <= 0) return gerr(VF_ERR_CAPACITY, "capacity %d too small for lag %d plus the keyframes added per solve", g->opts.capacity, g->opts.lag);
+    if (int rc = vf_engine_compact(g->eng, shift)) return rc;
+    g->lo -= shift, g->key_base += shift;
+    if (slot_of(g, t.last_key) + 1 > g->opts.capacity) return gerr(VF_ERR_CAPACITY, "capacity %d exhausted even after compaction", g->opts.capacity);
+    return VF_OK;
+}
+// fixed-lag window: marginalise the keyframes that fall out of the lag, one at a time, at the linearisation of the previous
+// solve (their factors have not changed since).  FIRST: the engine runs it on a second stream, beside the preintegration /
+// prediction / staging of the keyframes that arrive (vf_engine_set_async)
+static int marginalise(vf_graph* g, SolveTake& t, Lap& lap) {
+    while (g->opts.lag > 0 && slot_of(g, t.last_key) + 1 - g->lo > g->opts.lag && slot_of(g, g->solved_key) - g->lo >= 3) {
+        if (int rc = vf_engine_marginalize(g->eng)) return rc;
+        if (int rc = vf_engine_drop_oldest(g->eng)) return rc;
         g->lo++;      // (kept in step with the device: a keyframe that has been marginalised stays marginalised)
-        marginalised = true;
+        t.marginalised = true;
     }
-    const int lo = g->lo;
     lap("marginalize");
-    // a far factor added since the last solve whose older key the marginalisations above have just moved out of the window never
-    // reached the device: it is late odometry like any other (dropped, reported once, the rest given back)
-    {
-        const uint64_t oldest = g->key_base + (uint64_t)lo;
-        bool dropped = false;
-        unsigned long long da = 0, db = 0;
-        for (size_t i = 0; i < fars.size();) {
-            if (!fars[i].on_device && fars[i].a < oldest) {
-                if (!dropped) { da = fars[i].a; db = fars[i].b; }
-                dropped = true;
-                for (size_t j = 0; j < log_before.size(); j++)
-                    if (log_before[j].a == fars[i].a && log_before[j].b == fars[i].b) { log_before.erase(log_before.begin() + (long)j); break; }
-                fars.erase(fars.begin() + (long)i);
-                staged_before--;
-                far_new_before--;
-                fars_changed = true;
-            } else i++;
-        }
-        if (dropped)
-            return give_back(gerr(VF_ERR_BAD_KEY, "between factor (%llu, %llu) dropped: key %llu left the fixed-lag window in this solve (oldest key %llu)",
-                                  da, db, da, (unsigned long long)oldest));
-    }
-    if (!imus.empty()) {
-        // K0 on the device for all queued factors, then the initial values by IMU prediction
-        // (GraphManager.cpp:150-160).  Keys are consecutive by construction.
-        const int n = (int)imus.size();
-        const uint64_t k0 = imus.front().key - g->key_base;
-        // runs of factors cut from the IMU buffer (reserveNode) are preintegrated on the device in one K0 launch;
-        // ready-made factors (addFactor) are staged as records
-        for (int i = 0; i < n;) {
-            int j = i;
-            if (imus[i].staged) { i++; continue; }          // preintegrated at reserveNode time: the record is on the device
-            const bool ready = !imus[i].record.empty();
-            while (j < n && !imus[j].staged && imus[j].record.empty() == !ready) j++;
-            const int cnt = j - i;
-            if (ready) {
-                std::vector<double> recs((size_t)cnt * VF_IMU_RECORD);
-                for (int l = 0; l < cnt; l++) memcpy(&recs[(size_t)l * VF_IMU_RECORD], imus[i + l].record.data(), sizeof(double) * VF_IMU_RECORD);
-                if ((rc = vf_engine_set_imu(g->eng, 0, (int)k0 + i, cnt, recs.data()))) return give_back(rc);
-            } else {
-                std::vector<int32_t> off(cnt + 1, 0);
-                std::vector<double> steps, bias((size_t)cnt * 6);
-                for (int l = 0; l < cnt; l++) {
-                    off[l + 1] = off[l] + (int)(imus[i + l].steps.size() / 7);
-                    steps.insert(steps.end(), imus[i + l].steps.begin(), imus[i + l].steps.end());
-                    memcpy(&bias[(size_t)l * 6], imus[i + l].bias, sizeof(double) * 6);
-                }
-                if ((rc = vf_engine_preintegrate(g->eng, 0, (int)k0 + i, cnt, off.data(), steps.data(), bias.data(), &g->imu))) return give_back(rc);
+    // Late odometry: far factors whose older key the loop has just moved out of the window and that never reached the device
+    // (the engine has marginalised the others with their key), all at once, reported by the first, "in this solve".  (A band
+    // factor in that position has passed refuse_late and is staged below the window, where the kernels ignore it: ADVICE.md.
+    // Refusing it is one more drop_late here, over t.betweens with refuse_late's marks; that call is deliberately not made yet.)
+    const uint64_t oldest = oldest_key(g);
+    LateFactor late;
+    for (size_t i = 0; i < t.fars.size();)
+        if (!t.fars[i].on_device && is_late(t.fars[i], oldest)) drop_late(t.fars, i, t.log, t.staged, &t.far_new, late);
+        else i++;
+    t.fars_changed = t.fars_changed || late.any;
+    return late.any ? late_error(late, " in this solve", oldest) : VF_OK;
+}
+// K0 on the device for all queued factors, then the initial values by IMU prediction (GraphManager.cpp:150-160); keys are consecutive
+static int stage_imu(vf_graph* g, SolveTake& t, Lap& lap) {
+    if (t.imus.empty()) return VF_OK;
+    const auto& imus = t.imus;
+    const int n = (int)imus.size(), k0 = slot_of(g, imus.front().key);
+    // runs of factors cut from the IMU buffer (reserveNode) are preintegrated in one K0 launch; ready-made factors (addFactor) are staged as records
+    for (int i = 0; i < n;) {
+        int j = i;
+        if (imus[i].staged) { i++; continue; }          // preintegrated at reserveNode time: the record is on the device
+        const bool ready = !imus[i].record.empty();
+        while (j < n && !imus[j].staged && imus[j].record.empty() == !ready) j++;
+        const int cnt = j - i;
+        if (ready) {
+            std::vector<double> recs((size_t)cnt * VF_IMU_RECORD);
+            for (int l = 0; l < cnt; l++) memcpy(&recs[(size_t)l * VF_IMU_RECORD], imus[i + l].record.data(), sizeof(double) * VF_IMU_RECORD);
+            if (int rc = vf_engine_set_imu(g->eng, 0, k0 + i, cnt, recs.data())) return rc;
+        } else {
+            std::vector<int32_t> off(cnt + 1, 0);
+            std::vector<double> steps, bias((size_t)cnt * 6);
+            for (int l = 0; l < cnt; l++) {
+                off[l + 1] = off[l] + (int)(imus[i + l].steps.size() / 7);
+                steps.insert(steps.end(), imus[i + l].steps.begin(), imus[i + l].steps.end());
+                memcpy(&bias[(size_t)l * 6], imus[i + l].bias, sizeof(double) * 6);
             }
-            i = j;
+            if (int rc = vf_engine_preintegrate(g->eng, 0, k0 + i, cnt, off.data(), steps.data(), bias.data(), &g->imu)) return rc;
         }
-        lap("preintegrate");
-        // reference_compat: from the ESTIMATE of the last keyframe (_currentState, GraphManager.cpp:152), not its linearisation point
-        if ((rc = (g->opts.reference_compat && g->solved_key > 0) ? vf_engine_predict_from_estimate(g->eng, 0, (int)k0, n)
-                                                                    : vf_engine_predict(g->eng, 0, (int)k0, n))) return give_back(rc);
-        lap("predict");
+        i = j;
     }
-    if (!betweens.empty()) {
-        std::vector<int32_t> a(betweens.size()), b(betweens.size());
-        std::vector<double> rec(betweens.size() * VF_BTW_RECORD);
-        // the engine wants runs sorted by b
-        std::vector<size_t> order(betweens.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        for (size_t i = 1; i < order.size(); i++)
-            for (size_t j = i; j > 0 && betweens[order[j]].b < betweens[order[j - 1]].b; j--) std::swap(order[j], order[j - 1]);
-        for (size_t i = 0; i < order.size(); i++) {
-            a[i] = (int32_t)(betweens[order[i]].a - g->key_base);
-            b[i] = (int32_t)(betweens[order[i]].b - g->key_base);
-            memcpy(&rec[i * VF_BTW_RECORD], betweens[order[i]].rec, sizeof(double) * VF_BTW_RECORD);
-        }
-        if ((rc = vf_engine_set_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data()))) return give_back(rc);
-        lap("set_between");
+    lap("preintegrate");
+    // reference_compat: from the ESTIMATE of the last keyframe (_currentState, GraphManager.cpp:152), not its linearisation point
+    if (int rc = (g->opts.reference_compat && g->solved_key > 0) ? vf_engine_predict_from_estimate(g->eng, 0, k0, n) : vf_engine_predict(g->eng, 0, k0, n)) return rc;
+    lap("predict");
+    return VF_OK;
+}
+static int stage_band(vf_graph* g, SolveTake& t, Lap& lap) {
+    const auto& betweens = t.betweens;
+    if (betweens.empty()) return VF_OK;
+    std::vector<int32_t> a(betweens.size()), b(betweens.size());
+    std::vector<double> rec(betweens.size() * VF_BTW_RECORD);
+    // the engine wants runs sorted by b
+    std::vector<size_t> order(betweens.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    for (size_t i = 1; i < order.size(); i++)
+        for (size_t j = i; j > 0 && betweens[order[j]].b < betweens[order[j - 1]].b; j--) std::swap(order[j], order[j - 1]);
+    for (size_t i = 0; i < order.size(); i++) {
+        a[i] = slot_of(g, betweens[order[i]].a);
+        b[i] = slot_of(g, betweens[order[i]].b);
+        memcpy(&rec[i * VF_BTW_RECORD], betweens[order[i]].rec, sizeof(double) * VF_BTW_RECORD);
     }
-    if (marginalised && (g->far_on_device || g->far_linear.load() > 0)) {
-        // the engine has marginalised the far factors whose older key left together with that key (they are linear rows of its
-        // own now): the entries that were on the device are replaced by what the engine's list holds now
-        int cnt = 0;
-        int32_t ea[VF_MAX_FAR_LIMIT], eb[VF_MAX_FAR_LIMIT];
-        double erec[VF_MAX_FAR_LIMIT * VF_BTW_RECORD];
-        if ((rc = vf_engine_get_extra_between(g->eng, 0, &cnt, ea, eb, erec, nullptr, nullptr, nullptr))) return give_back(rc);
-        std::vector<PendingBetween> moved;
-        for (int i = 0; i < cnt; i++) {
-            PendingBetween f;
-            f.a = (uint64_t)ea[i] + g->key_base;
-            f.b = (uint64_t)eb[i] + g->key_base;
-            memcpy(f.rec, erec + (size_t)i * VF_BTW_RECORD, sizeof(f.rec));
-            f.on_device = true;
-            moved.push_back(f);
-        }
-        for (const auto& f : fars)
-            if (!f.on_device) moved.push_back(f);
-        fars.swap(moved);
-        fars_changed = true;
-        int lin = 0;
-        if ((rc = vf_engine_get_linear_far(g->eng, 0, &lin, nullptr))) return give_back(rc);
-        g->far_linear.store(lin);
+    if (int rc = vf_engine_set_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+    lap("set_between");
+    return VF_OK;
+}
+// the engine has marginalised the far factors whose older key left together with that key (they are linear rows of its own now):
+// the entries that were on the device are replaced by what the engine's list holds now
+static int adopt_engine_far_list(vf_graph* g, SolveTake& t) {
+    if (!t.marginalised || !(g->far_on_device || g->far_linear.load() > 0)) return VF_OK;
+    int rc, cnt = 0, lin = 0;
+    int32_t ea[VF_MAX_FAR_LIMIT], eb[VF_MAX_FAR_LIMIT];
+    double erec[VF_MAX_FAR_LIMIT * VF_BTW_RECORD];
+    if ((rc = vf_engine_get_extra_between(g->eng, 0, &cnt, ea, eb, erec, nullptr, nullptr, nullptr))) return rc;
+    std::vector<PendingBetween> moved;
+    for (int i = 0; i < cnt; i++) {
+        PendingBetween f;
+        f.a = (uint64_t)ea[i] + g->key_base, f.b = (uint64_t)eb[i] + g->key_base;
+        memcpy(f.rec, erec + (size_t)i * VF_BTW_RECORD, sizeof(f.rec));
+        f.on_device = true;
+        moved.push_back(f);
     }
-    if (!fars.empty() || g->far_on_device) {
-        // far between factors still inside the window, in window-local slots (the engine ignores one whose older keyframe
-        // is below `lo`; the list is re-sent at every solve, so compaction and growth need no bookkeeping here)
-        std::vector<int32_t> a, b;
-        std::vector<double> rec;
-        for (const auto& f : fars) {
-            if (f.a < g->key_base + (uint64_t)lo || f.b > last_key) continue;
-            a.push_back((int32_t)(f.a - g->key_base));
-            b.push_back((int32_t)(f.b - g->key_base));
-            rec.insert(rec.end(), f.rec, f.rec + VF_BTW_RECORD);
-        }
-        if ((rc = vf_engine_set_extra_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data()))) return give_back(rc);
-        g->far_on_device = !a.empty();
-        for (auto& f : fars)
-            if (!(f.a < g->key_base + (uint64_t)lo || f.b > last_key)) { fars_changed = fars_changed || !f.on_device; f.on_device = true; }
-        lap("set_extra");
+    for (const auto& f : t.fars)
+        if (!f.on_device) moved.push_back(f);
+    t.fars.swap(moved);
+    t.fars_changed = true;
+    if ((rc = vf_engine_get_linear_far(g->eng, 0, &lin, nullptr))) return rc;
+    g->far_linear.store(lin);
+    return VF_OK;
+}
+// far between factors still inside the window, in window-local slots (the engine ignores one whose older keyframe is below
+// `lo`; the list is re-sent at every solve, so compaction and growth need no bookkeeping here)
+static int stage_far_list(vf_graph* g, SolveTake& t, Lap& lap) {
+    if (t.fars.empty() && !g->far_on_device) return VF_OK;
+    std::vector<int32_t> a, b;
+    std::vector<double> rec;
+    for (const auto& f : t.fars) {
+        if (!in_window(g, f, t.last_key)) continue;
+        a.push_back(slot_of(g, f.a));
+        b.push_back(slot_of(g, f.b));
+        rec.insert(rec.end(), f.rec, f.rec + VF_BTW_RECORD);
     }
-    if ((rc = vf_engine_set_range(g->eng, 0, lo, last_slot + 1))) return give_back(rc);
+    if (int rc = vf_engine_set_extra_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+    g->far_on_device = !a.empty();
+    for (auto& f : t.fars)
+        if (in_window(g, f, t.last_key)) { t.fars_changed = t.fars_changed || !f.on_device; f.on_device = true; }
+    lap("set_extra");
+    return VF_OK;
+}
+static int optimise_and_read(vf_graph* g, SolveTake& t, Lap& lap, int& fails, int& flags) {
+    const int last_slot = slot_of(g, t.last_key);
     lap("set_range");
-    int fails = 0, flags = 0;
     if (g->opts.reference_compat) {
-        if ((rc = vf_engine_isam_step(g->eng, g->opts.relin_threshold))) return rc;  // one ISAM2::update
+        if (int rc = vf_engine_isam_step(g->eng, g->opts.relin_threshold)) return rc;  // one ISAM2::update
         lap("isam_step");
-        if ((rc = vf_engine_read_result(g->eng, 0, last_slot, 1, g->state, nullptr, nullptr, nullptr, nullptr, &flags))) return rc;   // calculateEstimate, :127,131-133
+        if (int rc = vf_engine_read_result(g->eng, 0, last_slot, 1, g->state, nullptr, nullptr, nullptr, nullptr, &flags)) return rc;   // calculateEstimate, :127,131-133
     } else {
-        if ((rc = vf_engine_iterate(g->eng, g->opts.iterations))) return rc;   // (ISAM2::update + calculateEstimate: LM to convergence)
+        if (int rc = vf_engine_iterate(g->eng, g->opts.iterations)) return rc;   // (ISAM2::update + calculateEstimate: LM to convergence)
         lap("iterate(launch)");
         // the one synchronisation of the solve: the last state (:131-133), the failure count, what the staging kernels flagged
-        if ((rc = vf_engine_read_result(g->eng, 0, last_slot, 0, g->state, nullptr, nullptr, nullptr, &fails, &flags))) return rc;
+        if (int rc = vf_engine_read_result(g->eng, 0, last_slot, 0, g->state, nullptr, nullptr, nullptr, &fails, &flags)) return rc;
     }
     lap("read_result(sync)");
+    return VF_OK;
+}
+static int publish(vf_graph* g, SolveTake& t, int fails, int flags) {
     // (asynchronous staging: a preintegrated covariance / a marginalisation pivot that was not positive definite shows here, after
     // the solve that used it -- with positive IMU covariances and a determined graph neither happens)
     if (flags & 1) return gerr(VF_ERR_NOT_SPD, "preintegrated covariance not positive definite");
     if (flags & 6) return gerr(VF_ERR_INDETERMINATE, "marginalisation: %s not positive definite", (flags & 4) ? "the far ends' block of the marginal" : "pivot block of the oldest keyframe");
-    g->solved_key = last_key;
+    g->solved_key = t.last_key;
     g->solved_once = true;
     // covariance callbacks (no reference code): the marginal covariance of the solved keyframe, computed only while one is registered
     double cov[225];
-    if (!g->cov_callbacks.empty() && marginal_covariance(g, last_key, cov) != VF_OK)
+    if (!g->cov_callbacks.empty() && marginal_covariance(g, t.last_key, cov) != VF_OK)
         for (double& c : cov) c = std::numeric_limits<double>::quiet_NaN();
     for (auto& cb : g->callbacks)  // :135-138, on the solving thread, inside _stateMutex
-        cb.first(cb.second, last_time, g->state, g->state + 4, g->state + 7, g->state + 10);
+        cb.first(cb.second, t.last_time, g->state, g->state + 4, g->state + 7, g->state + 10);
     for (auto& cb : g->cov_callbacks)
-        cb.first(cb.second, last_time, g->state, g->state + 4, g->state + 7, g->state + 10, cov);
+        cb.first(cb.second, t.last_time, g->state, g->state + 4, g->state + 7, g->state + 10, cov);
     // a full fixed-lag window marginalises its oldest keyframe at the next update, from the linearisation this solve leaves:
     // have the device compute that marginal prior now, behind the solve, instead of in front of the next one
-    if (g->opts.lag > 0 && !g->opts.synchronous_staging && last_slot + 1 - g->lo >= g->opts.lag) (void)vf_engine_marginalize_ahead(g->eng);
+    if (g->opts.lag > 0 && !g->opts.synchronous_staging && slot_of(g, t.last_key) + 1 - g->lo >= g->opts.lag) (void)vf_engine_marginalize_ahead(g->eng);
     if (fails > 0 && fails >= g->opts.iterations && g->opts.iterations > 0)
         return gerr(VF_ERR_INDETERMINATE, "normal equations not positive definite in every LM trial (underdetermined graph?)");
     return VF_OK;
-    };
-    const int rc = locked();
-    if (fars_changed) {
-        // the entries snapshotted above are the front of the list (others only append, under graph_mutex): replace them by
-        // their current form (the ones the engine has taken over are gone; on_device marks)
-        std::lock_guard<std::mutex> lk(g->graph_mutex);
-        if (g->far_between.size() >= fars_snapshot) {
-            std::vector<PendingBetween> now(fars);
-            now.insert(now.end(), g->far_between.begin() + (long)fars_snapshot, g->far_between.end());
-            g->far_between.swap(now);
-        }
+}
+
+int vf_solve(vf_graph* g) {
+    if (!g) return gerr(VF_ERR_INVALID, "null argument");
+    Lap lap;
+    SolveTake t;
+    std::lock_guard<std::mutex> solve_lk(g->solve_mutex);
+    take(g, t);
+    int rc, fails = 0, flags = 0;
+    {
+        std::lock_guard<std::mutex> sl(g->state_mutex);  // :117
+        g->cov_valid = false;
+        (rc = refuse_late(g, t)) || (rc = make_room(g, t, lap)) || (rc = marginalise(g, t, lap)) || (rc = stage_imu(g, t, lap)) || (rc = stage_band(g, t, lap)) ||
+            (rc = adopt_engine_far_list(g, t)) || (rc = stage_far_list(g, t, lap)) || (rc = vf_engine_set_range(g->eng, 0, g->lo, slot_of(g, t.last_key) + 1));
+        t.requeue = rc != VF_OK;    // up to here a failure gives the take back; the optimisation consumes it, whatever it returns
+        if (!rc) rc = optimise_and_read(g, t, lap, fails, flags);
+        if (!rc) rc = publish(g, t, fails, flags);
     }
-    if (requeue) {
-        std::lock_guard<std::mutex> lk(g->graph_mutex);
-        for (auto it = imus.rbegin(); it != imus.rend(); ++it) g->imu_queue.push_front(std::move(*it));
-        g->staged_between.insert(g->staged_between.begin(), betweens.begin(), betweens.end());
-        g->staged_count += staged_before;
-        if (late_band)
-            for (size_t j = 0; j < log_before.size(); j++)
-                if (log_before[j].b == late_band_key && log_before[j].a == late_band_a) { log_before.erase(log_before.begin() + (long)j); break; }
-        g->staged_log.insert(g->staged_log.begin(), log_before.begin(), log_before.end());
-        g->priors_staged = g->priors_staged || priors_before;
-        // the far factors added since the last successful solve are still "new" for the solve that repeats this one (its
-        // late-odometry test looks at the new ones only), and a band factor dropped as late leaves its end key free again
-        g->far_new += far_new_before;
-        if (late_band) g->set_band_end(late_band_key, 0);
-    }
+    if (t.fars_changed) publish_far_list(g, t);
+    if (t.requeue) give_back(g, t);
     return rc;
 }
 
@@ -847,7 +847,7 @@ int vf_graph_lm_stats(vf_graph* g, double* cost, int* accepted, int* rejected, i
 int vf_graph_solver_info(vf_graph* g, int* window_keyframes, int* refine_corrections, int* provisional_trials) {
     if (!g) return gerr(VF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->state_mutex);
-    if (window_keyframes) *window_keyframes = (int)(g->solved_key - g->key_base) + 1 - g->lo;
+    if (window_keyframes) *window_keyframes = slot_of(g, g->solved_key) + 1 - g->lo;
     int rc;
     if (refine_corrections && (rc = vf_engine_refine_count(g->eng, refine_corrections))) return rc;
     if (provisional_trials && (rc = vf_engine_read_excursions(g->eng, 0, provisional_trials, nullptr))) return rc;
@@ -869,15 +869,15 @@ int vf_get_trajectory(vf_graph* g, uint64_t key0, int n, double* state16) {
     std::lock_guard<std::mutex> lk(g->state_mutex);
     if (n < 0 || key0 + (uint64_t)n > g->solved_key + 1) return gerr(VF_ERR_BAD_KEY, "keys [%llu, %llu) not solved yet", (unsigned long long)key0, (unsigned long long)(key0 + n));
     if (key0 < g->key_base) return gerr(VF_ERR_BAD_KEY, "key %llu has been compacted away (oldest retained key %llu)", (unsigned long long)key0, (unsigned long long)g->key_base);
-    if (g->opts.reference_compat) return vf_engine_get_estimate(g->eng, 0, (int)(key0 - g->key_base), n, state16);
-    return vf_engine_get_states(g->eng, 0, (int)(key0 - g->key_base), n, state16);
+    if (g->opts.reference_compat) return vf_engine_get_estimate(g->eng, 0, slot_of(g, key0), n, state16);
+    return vf_engine_get_states(g->eng, 0, slot_of(g, key0), n, state16);
 }
 
 int vf_get_imu_factor(vf_graph* g, uint64_t key, double* rec190) {
     if (!g || !rec190) return gerr(VF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->state_mutex);
     if (key < 1 || key > g->solved_key || key < g->key_base + 1) return gerr(VF_ERR_BAD_KEY, "imu factor %llu not on the device", (unsigned long long)key);
-    return vf_engine_get_imu(g->eng, 0, (int)(key - g->key_base), 1, rec190);
+    return vf_engine_get_imu(g->eng, 0, slot_of(g, key), 1, rec190);
 }
 
 }  // extern "C"
