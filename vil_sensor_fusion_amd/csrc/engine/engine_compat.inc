@@ -1,6 +1,6 @@
 // engine/engine_compat.inc -- the reference-compat update (one iSAM2-like Gauss-Newton update) and its incremental form.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 // ------------------------------------------------------------------ reference-compat solve
 // What the reference does per GraphManager::solve (GraphManager.cpp:38-43,126-127): ONE iSAM2 update -- Gauss-Newton
 // (QR, no damping) about per-variable linearisation points theta, relinearising only the variables whose pending
@@ -12,10 +12,9 @@
 // vf_engine_solve_local, ..., the refinement -- and vf_engine_retract): relinearise where the pending increment reaches the
 // threshold, lambda := 0 (Gauss-Newton), linearise every factor at theta
 int vf_engine_gn_begin(vf_engine* e, double relin_threshold) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (!(relin_threshold >= 0.0)) return fail(VF_ERR_INVALID, "relinearisation threshold must be >= 0");
-    cold(e);
+    e->mem.rewritten();
     int rc;
     vf::launch_relinearize(e->v, relin_threshold, e->stream);
     HIPCHK(hipMemsetAsync(e->v.lambda, 0, e->v.B * sizeof(double), e->stream));     // Gauss-Newton: no damping
@@ -26,13 +25,21 @@ int vf_engine_gn_begin(vf_engine* e, double relin_threshold) {
 // the first keyframe that changed, back-substitute until the increments stop changing (vf_kernels.hpp "Incremental
 // Gauss-Newton updates").  The first update of an engine, and every update after an entry point the bookkeeping does not
 // follow, covers the whole window.
+// the failure flags of the solve just enqueued, read back: the first window that failed is the one reported
+static int first_failed_window(vf_engine* e) {
+    std::vector<int> failed((size_t)e->v.B);
+    HIPCHK(hipMemcpyAsync(failed.data(), e->v.fail, failed.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int w = 0; w < e->v.B; w++)
+        if (failed[w]) return fail(VF_ERR_INDETERMINATE, "window %d: normal equations not positive definite (underdetermined graph)", w);
+    return VF_OK;
+}
 static int isam_step_incremental(vf_engine* e, double relin_threshold) {
-    const int invalid = (e->inc_valid && e->opts.incremental != 2) ? 0 : 1;     // (incremental = 2: the same kernels over the whole window, every time)
-    int appended = e->inc_slid;
-    if (e->v.B == 1 && e->inc_first_dirty != 0x7fffffff) appended = std::max(appended, e->h_hi[0] - e->inc_first_dirty);
+    const int invalid = (e->mem.inc_whole_window() || e->opts.incremental == 2) ? 1 : 0;     // (incremental = 2: the same kernels over the whole window, every time)
+    const int appended = e->mem.inc_appended(e->h_hi[0]);
     vf::View a = e->v;
     a.inc_on = 1;
-    a.inc_prior = (invalid || e->inc_slid > 0) ? 1 : 0;
+    a.inc_prior = (invalid || e->mem.inc_slid()) ? 1 : 0;
     a.stop_on = 0;
     vf::launch_inc_begin(a, relin_threshold, appended, invalid, e->stream);
     HIPCHK(hipMemsetAsync(e->v.lambda, 0, e->v.B * sizeof(double), e->stream));     // Gauss-Newton: no damping
@@ -41,22 +48,14 @@ static int isam_step_incremental(vf_engine* e, double relin_threshold) {
     vf::launch_inc_solve(a, e->stream);
     vf::launch_inc_retract(a, e->stream);
     HIPCHK(hipGetLastError());
-    cold(e);
-    e->inc_slid = 0;
-    e->inc_first_dirty = 0x7fffffff;
     e->inc_updates++;
     if (invalid) e->inc_full++;
-    std::vector<int> failed((size_t)e->v.B);
-    HIPCHK(hipMemcpyAsync(failed.data(), e->v.fail, failed.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int w = 0; w < e->v.B; w++)
-        if (failed[w]) return fail(VF_ERR_INDETERMINATE, "window %d: normal equations not positive definite (underdetermined graph)", w);
-    e->inc_valid = true;
-    return VF_OK;
+    const int rc = first_failed_window(e);
+    e->mem.inc_update_ended(rc == VF_OK);
+    return rc;
 }
 int vf_engine_isam_step(vf_engine* e, double relin_threshold) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (int rc0 = not_sharded(e, "vf_engine_isam_step")) return rc0;
     if (!(relin_threshold >= 0.0)) return fail(VF_ERR_INVALID, "relinearisation threshold must be >= 0");
     // (far factors are solved as a low-rank correction of the whole band: such windows take the full update)
@@ -64,16 +63,12 @@ int vf_engine_isam_step(vf_engine* e, double relin_threshold) {
     int rc;
     if ((rc = vf_engine_gn_begin(e, relin_threshold)) || (rc = vf_engine_assemble(e)) ||
         (rc = vf_engine_solve(e)) || (rc = vf_engine_retract(e))) return rc;
-    std::vector<int> failed((size_t)e->v.B);
-    HIPCHK(hipMemcpyAsync(failed.data(), e->v.fail, failed.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int w = 0; w < e->v.B; w++)
-        if (failed[w]) return fail(VF_ERR_INDETERMINATE, "window %d: normal equations not positive definite (underdetermined graph)", w);
-    cold(e);
+    if ((rc = first_failed_window(e))) return rc;
+    e->mem.rewritten();
     return VF_OK;
 }
 int vf_engine_incremental_info(vf_engine* e, int window, long* updates, long* whole_window_updates, int* first_eliminated, int* last_substituted) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
     if (updates) *updates = e->inc_updates;
@@ -89,9 +84,8 @@ int vf_engine_incremental_info(vf_engine* e, int window, long* updates, long* wh
     return VF_OK;
 }
 int vf_engine_predict_from_estimate(vf_engine* e, int window, int k0, int n) {
-    DeviceGuard dev_guard_(e, e && window >= 0 && window < e->v.B && k0 > e->h_lo[window] + 1);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
-    { const bool keep = e->inc_valid; touch(e, window, k0); cold(e); if (keep && e->v.B == 1 && window == 0 && k0 > e->h_lo[0]) e->inc_valid = true; }
+    VF_ENTER(e, Entry::reads, Entry::overlaps_if(e && window >= 0 && window < e->v.B && k0 > e->h_lo[window] + 1));
+    e->mem.predicted_from_estimate(window, k0, e->h_lo[0]);
     if (window >= e->v.B || k0 < 1 || n < 0 || k0 + n > e->v.M) return fail(VF_ERR_BAD_KEY, "bad predict range");
     if (n == 0) return VF_OK;
     vf::launch_predict(e->v, window, k0, n, 1, e->stream);
@@ -99,7 +93,7 @@ int vf_engine_predict_from_estimate(vf_engine* e, int window, int k0, int n) {
     return VF_OK;
 }
 int vf_engine_get_estimate(vf_engine* e, int window, int k0, int n, double* s) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (!s) return fail(VF_ERR_INVALID, "null states");

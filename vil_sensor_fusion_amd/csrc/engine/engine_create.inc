@@ -1,6 +1,6 @@
 // engine/engine_create.inc -- errors, option defaults (struct_size), creation from ONE device allocation, destruction.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 
 const char* vf_last_error(void) { return g_err.c_str(); }
 void vf_set_last_error_(const char* msg) { g_err = msg ? msg : ""; }  // used by vf_graph.cpp
@@ -235,7 +235,8 @@ static int create_engine(const vf_engine_opts* o_in, const vf_engine_tuning* t_i
     // with plain asynchronous launches -- the queue is never empty, so there is no launch gap to remove.
     // Hence opt-in only.
     e->graph_off = t->use_hip_graph == 0;
-    e->no_warm = o->cold_start != 0;
+    e->mem.one_window = v.B == 1;
+    e->mem.no_warm = o->cold_start != 0;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->h_lo.assign(v.B, 0);
     e->h_hi.assign(v.B, 0);
@@ -244,7 +245,7 @@ static int create_engine(const vf_engine_opts* o_in, const vf_engine_tuning* t_i
 }
 
 void vf_engine_destroy(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e) return;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     e->drop_graph();

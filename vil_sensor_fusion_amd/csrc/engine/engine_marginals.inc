@@ -21,9 +21,7 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
     if (flags & ~(unsigned)VF_MARGINALS_FAR) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
     const bool far = (flags & VF_MARGINALS_FAR) != 0;
-    const bool cached = e->res_cached;
-    DeviceGuard dev_guard_(e);
-    e->res_cached = cached;      // (nothing here touches the result block of the last solve)
+    Entry entry_(e, Entry::reads, Entry::leaves_result);      // (nothing here touches the result block of the last solve)
     if (int rc = not_sharded(e, "vf_engine_marginals")) return rc;
     e->recount_far();
     if (e->x_used > 0 && !far)
@@ -59,7 +57,7 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
         HIPCHK(hipMemcpyAsync(e->sig_ones, ones.data(), B * sizeof(int), hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
-    cold(e);
+    e->mem.rewritten();      // (inherited order: a refused call leaves the engine as it was)
     vf::View a = e->v;
     a.lambda = e->sig_zero;          // undamped
     a.fail = e->sig_fail;
@@ -98,15 +96,15 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;
     e->sig_hi = e->h_hi;
-    e->sig_valid = true;
+    e->mem.covariances_computed();
     return VF_OK;
 }
 
 int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* cov225, double* cross225) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
-    if (!e->sig_valid || e->sig_G != e->v.G) return fail(VF_ERR_INVALID, "no marginal covariances: call vf_engine_marginals first");
+    if (!e->mem.covariances_valid() || e->sig_G != e->v.G) return fail(VF_ERR_INVALID, "no marginal covariances: call vf_engine_marginals first");
     if (n < 0 || k0 < e->sig_lo[window] || k0 + n > e->sig_hi[window])
         return fail(VF_ERR_BAD_KEY, "keyframes [%d,%d) outside the range [%d,%d) the covariances were computed for", k0, k0 + n,
                     e->sig_lo[window], e->sig_hi[window]);

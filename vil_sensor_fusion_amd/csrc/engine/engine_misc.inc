@@ -1,10 +1,8 @@
 // engine/engine_misc.inc -- termination rule, damping reset, prediction.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 int vf_engine_set_convergence(vf_engine* e, double rel_tol, double abs_tol) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::rewrites);
     if (!(rel_tol >= 0.0) || !(abs_tol >= 0.0)) return fail(VF_ERR_INVALID, "tolerances must be >= 0");
     HIPCHK(hipStreamSynchronize(e->stream));
     e->v.rel_tol = rel_tol;
@@ -27,17 +25,15 @@ int vf_engine_set_convergence(vf_engine* e, double rel_tol, double abs_tol) {
     return VF_OK;
 }
 int vf_engine_reset_lambda(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     vf::launch_reset_lambda(e->v, e->lambda0_dev, 0, e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
 
 int vf_engine_predict(vf_engine* e, int window, int k0, int n) {
-    DeviceGuard dev_guard_(e, e && window >= 0 && window < e->v.B && k0 > e->h_lo[window] + 1);
-    touch(e, window, k0);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    // (inherited order: the write is recorded before the range is validated)
+    VF_ENTER(e, Entry::appends(window, k0), Entry::overlaps_if(e && window >= 0 && window < e->v.B && k0 > e->h_lo[window] + 1));
     if (window >= e->v.B || k0 < 1 || n < 0 || k0 + n > e->v.M) return fail(VF_ERR_BAD_KEY, "bad predict range");
     if (n == 0) return VF_OK;
     vf::launch_predict(e->v, window, k0, n, 0, e->stream);

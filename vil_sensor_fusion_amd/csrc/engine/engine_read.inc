@@ -1,6 +1,6 @@
 // engine/engine_read.inc -- read-back and measurement.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 // ------------------------------------------------------------------ read-back
 static int read_sel(vf_engine* e, int window, int* sel) {
     HIPCHK(hipMemcpyAsync(sel, e->v.sel + window, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -9,7 +9,7 @@ static int read_sel(vf_engine* e, int window, int* sel) {
 }
 
 int vf_engine_read_imu_lin(vf_engine* e, int window, int which, int k0, int n, double* r15, double* J450) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0) return VF_OK;
@@ -31,7 +31,7 @@ int vf_engine_read_imu_lin(vf_engine* e, int window, int which, int k0, int n, d
 }
 
 int vf_engine_read_between_lin(vf_engine* e, int window, int which, int k0, int n, double* r6, double* Ja, double* Jb) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0) return VF_OK;
@@ -56,7 +56,7 @@ int vf_engine_read_between_lin(vf_engine* e, int window, int which, int k0, int 
 }
 
 int vf_engine_read_normal(vf_engine* e, int window, int k0, int n, double* Hband, double* g15) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0) return VF_OK;
@@ -95,7 +95,7 @@ int vf_engine_read_normal(vf_engine* e, int window, int k0, int n, double* Hband
 }
 
 int vf_engine_read_delta(vf_engine* e, int window, int k0, int n, double* d) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0 || !d) return VF_OK;
@@ -105,7 +105,7 @@ int vf_engine_read_delta(vf_engine* e, int window, int k0, int n, double* d) {
 }
 
 int vf_engine_read_panels(vf_engine* e, int window, int k0, int n, double* panels) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0 || !panels) return VF_OK;
@@ -124,7 +124,7 @@ int vf_engine_read_panels(vf_engine* e, int window, int k0, int n, double* panel
 }
 
 int vf_engine_read_lm(vf_engine* e, int window, double* cost, double* lambda, int* acc, int* rej, int* fails) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -138,7 +138,7 @@ int vf_engine_read_lm(vf_engine* e, int window, double* cost, double* lambda, in
 
 // ------------------------------------------------------------------ measurement
 int vf_engine_read_excursions(vf_engine* e, int window, int* provisional_trials, int* open_now) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
     int np = 0, pr = 0;
@@ -152,8 +152,7 @@ int vf_engine_read_excursions(vf_engine* e, int window, int* provisional_trials,
     return VF_OK;
 }
 int vf_engine_time_stage(vf_engine* e, int stage, int reps, float* avg_ms) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     if (!e || !avg_ms || reps < 1) return fail(VF_ERR_INVALID, "bad argument");
     vf::View tv = e->v;
     tv.stop_on = 0;           // stage timings are of the full work, whatever the windows' convergence flags say
@@ -194,8 +193,7 @@ int vf_engine_time_stage(vf_engine* e, int stage, int reps, float* avg_ms) {
 }
 
 int vf_engine_time_iterate(vf_engine* e, int iterations, float* ms) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     if (!e || !ms) return fail(VF_ERR_INVALID, "bad argument");
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipEventRecord(e->ev0, e->stream));
@@ -208,8 +206,7 @@ int vf_engine_time_iterate(vf_engine* e, int iterations, float* ms) {
 }
 
 int vf_engine_counts(vf_engine* e, int64_t* n_imu, int64_t* n_btw, int64_t* n_kf) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     HIPCHK(hipStreamSynchronize(e->stream));
     std::vector<int> a((size_t)e->v.G);
     HIPCHK(hipMemcpy(a.data(), e->v.btw_a, a.size() * sizeof(int), hipMemcpyDeviceToHost));

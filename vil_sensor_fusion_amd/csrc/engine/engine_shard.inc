@@ -1,6 +1,6 @@
 // engine/engine_shard.inc -- chunk geometry, time-sharded windows, their collectives from C (RCCL by dlopen).
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 // ------------------------------------------------------------------ chunk geometry (host only, no device needed)
 int vf_chunk_geometry(int n, int chunks, int fit, int c, int* count, int* first, int* interior, int* has_separator) {
     if (n < 0 || chunks < 1) return fail(VF_ERR_INVALID, "bad geometry query");
@@ -29,9 +29,7 @@ int vf_shard_range(int n, int chunks, int fit, int rank, int world, int* chunk_l
 
 // ------------------------------------------------------------------ time-sharded windows (multi-GPU)
 int vf_engine_set_stream(vf_engine* e, void* hip_stream) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::rewrites);
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->own_stream && e->stream) HIPCHK(hipStreamDestroy(e->stream));
     e->drop_graph();
@@ -41,9 +39,7 @@ int vf_engine_set_stream(vf_engine* e, void* hip_stream) {
     return VF_OK;
 }
 int vf_engine_set_shard(vf_engine* e, int rank, int world) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::rewrites);
     if (world < 1 || rank < 0 || rank >= world) return fail(VF_ERR_INVALID, "bad shard %d of %d", rank, world);
     if (world > 1 && (e->v.P < 2 || e->v.P_fit))
         return fail(VF_ERR_INVALID, "time sharding needs an explicit chunk count (vf_engine_opts.chunks >= 2)");
@@ -51,11 +47,12 @@ int vf_engine_set_shard(vf_engine* e, int rank, int world) {
     HIPCHK(hipStreamSynchronize(e->stream));
     e->v.sh_r = rank;
     e->v.sh_G = world;
+    e->mem.sharded = world > 1;
     e->epoch++;
     return VF_OK;
 }
 int vf_engine_shard_info(vf_engine* e, vf_shard_info* out) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e || !out) return fail(VF_ERR_INVALID, "null argument");
     if (e->v.P < 2) return fail(VF_ERR_INVALID, "engine was not created with the partitioned solve (chunks >= 2)");
     memset(out, 0, sizeof(*out));
@@ -83,8 +80,7 @@ static int check_sharded(vf_engine* e) {
     return VF_OK;
 }
 int vf_engine_solve_local(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_sharded(e);
     if (rc) return rc;
     vf::View a = e->v;
@@ -94,8 +90,7 @@ int vf_engine_solve_local(vf_engine* e) {
     return VF_OK;
 }
 int vf_engine_solve_global(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_sharded(e);
     if (rc) return rc;
     vf::View a = e->v;
@@ -199,7 +194,7 @@ int vf_shard_exchange_plan(int windows, int capacity, int chunks, int rank, int 
     return VF_OK;
 }
 int vf_shard_iterate(vf_engine* e, void* nccl_comm, int iterations) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = shard_ready(e, nccl_comm, "vf_shard_iterate");
     if (rc) return rc;
     if (iterations < 0) return fail(VF_ERR_INVALID, "iterations < 0");
@@ -210,7 +205,7 @@ int vf_shard_iterate(vf_engine* e, void* nccl_comm, int iterations) {
     return VF_OK;
 }
 int vf_shard_gn_step(vf_engine* e, void* nccl_comm, double relin_threshold) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = shard_ready(e, nccl_comm, "vf_shard_gn_step");
     if (rc) return rc;
     if ((rc = vf_engine_gn_begin(e, relin_threshold)) || (rc = shard_solve(e, nccl_comm)) || (rc = vf_engine_retract(e))) return rc;

@@ -1,11 +1,10 @@
 // engine/engine_solve.inc -- the stages of an LM trial, the refined solve, the trial loop (vf_engine_iterate), hipGraph replay.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 // ------------------------------------------------------------------ stages
-int vf_engine_linearize(vf_engine* e, int which) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+// Each stage is a static function that only enqueues -- what vf_engine_iterate's sequence calls, so that a solve does not void
+// what it is about to leave behind -- and an entry point of the same name around it, for callers that stage their own trials.
+static int linearize(vf_engine* e, int which) {
     which = which ? 1 : 0;
     // time-sharded ranks write the Jacobian of every factor only while the solve is refined (windows longer than
     // refine_min_keyframes, or refine_iterations > 0): otherwise each writes what feeds its own rows, and K1's traffic shrinks
@@ -28,10 +27,7 @@ static vf::SolveInputs solve_inputs(const vf_engine* e) {
                             e->x_used > 0 || e->refine_iters() > 0 || e->v.min_fidelity > 0.0);
 }
 static vf::SolvePlan solve_plan(const vf_engine* e) { return vf::solve_plan(solve_inputs(e)); }
-int vf_engine_assemble(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+static int assemble(vf_engine* e) {
     const vf::K3 k3 = solve_plan(e).k3;
     if (k3 == vf::K3::none) return VF_OK;
     if (k3 == vf::K3::partitioned) {
@@ -44,16 +40,7 @@ int vf_engine_assemble(vf_engine* e) {
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
-static int not_sharded(vf_engine* e, const char* what) {
-    if (e->v.sh_G > 1)
-        return fail(VF_ERR_INVALID, "%s works on whole windows; this engine holds shard %d of %d (use the staged calls, "
-                    "include/vilfusion.h \"time-sharded windows\")", what, e->v.sh_r, e->v.sh_G);
-    return VF_OK;
-}
-int vf_engine_solve(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+static int solve(vf_engine* e) {
     if (int rc = not_sharded(e, "vf_engine_solve")) return rc;
     const vf::SolvePlan plan = solve_plan(e);
     auto band_solve = [&](double* gvec, double* delta, const int* skip = nullptr) {      // the engine's K4 form on another right-hand side / increment buffer
@@ -164,9 +151,8 @@ int vf_engine_refine_count(vf_engine* e, int* iterations) {
     return VF_OK;
 }
 int vf_engine_refine_begin(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
-    cold(e);
+    VF_ENTER(e, Entry::reads);
+    e->mem.rewritten();
     if (int rc = e->ensure_refine()) return rc;
     vf::launch_refine_begin(e->v, e->rq, e->stream);
     HIPCHK(hipGetLastError());
@@ -174,14 +160,14 @@ int vf_engine_refine_begin(vf_engine* e) {
     return VF_OK;
 }
 int vf_engine_refine_step(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e || !e->refine_open) return fail(VF_ERR_INVALID, "no refinement open (vf_engine_refine_begin)");
     vf::launch_refine_step(e->v, e->rq, e->refine_stop(), e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
 int vf_engine_refine_end(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e || !e->refine_open) return fail(VF_ERR_INVALID, "no refinement open (vf_engine_refine_begin)");
     vf::launch_refine_end(e->v, e->rq, e->stream);
     HIPCHK(hipGetLastError());
@@ -191,7 +177,7 @@ int vf_engine_refine_end(vf_engine* e) {
 // corrections the last refined solve of `window` applied before its stopping rule (or the count) ended it; the ratio of the
 // preconditioned residual res . M^-1 res at the end to its first value
 int vf_engine_read_refine(vf_engine* e, int window, int* corrections, double* reduction) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
     int it = 0;
@@ -206,10 +192,7 @@ int vf_engine_read_refine(vf_engine* e, int window, int* corrections, double* re
     if (reduction) *reduction = rz0 > 0.0 ? rz / rz0 : 0.0;
     return VF_OK;
 }
-int vf_engine_retract(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+static int retract(vf_engine* e) {
     vf::launch_retract(e->v, e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
@@ -225,9 +208,7 @@ static int relinearize_restored(vf_engine* e) {
 }
 // ... and an excursion still open when a solve's trials run out is undone (vf_engine_iterate does this itself; callers that
 // stage their trials -- time-sharded windows -- call it after the last one)
-int vf_engine_close_excursions(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+static int close_excursions(vf_engine* e) {
     if (!e->v.x_best) return VF_OK;
     vf::launch_close_excursions(e->v, e->stream);
     if (int rc = relinearize_restored(e)) return rc;
@@ -239,10 +220,7 @@ int vf_engine_close_excursions(vf_engine* e) {
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
-int vf_engine_decide(vf_engine* e, int init) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+static int decide(vf_engine* e, int init) {
     e->v.nm_W = e->excursion();
     if (e->v.nm_W > 0)
         if (int rc = e->ensure_excursion()) return rc;
@@ -257,20 +235,25 @@ int vf_engine_decide(vf_engine* e, int init) {
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
+int vf_engine_linearize(vf_engine* e, int which) { VF_ENTER(e, Entry::rewrites); return linearize(e, which); }
+int vf_engine_assemble(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return assemble(e); }
+int vf_engine_solve(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return solve(e); }
+int vf_engine_retract(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return retract(e); }
+int vf_engine_decide(vf_engine* e, int init) { VF_ENTER(e, Entry::rewrites); return decide(e, init); }
+int vf_engine_close_excursions(vf_engine* e) { VF_ENTER(e, Entry::reads); return close_excursions(e); }
 static int iterate_sequence(vf_engine* e, int iterations) {
     // every solve starts from lambda0, as a fresh LevenbergMarquardtOptimizer would (k_reset_lambda: but for a window whose
     // previous solve ended inside an excursion)
     int rc;
-    const int tail = e->slid + e->redo;
-    const int slid = (e->warm && e->v.sh_G <= 1 && tail >= 1 && tail <= 8) ? tail : 0;
+    const int slid = e->mem.tail();
     vf::launch_reset_lambda(e->v, e->lambda0_dev, slid ? 1 : 0, e->stream);
     if (slid) {
         // nothing but slides since the last solve: only the appended keyframes' factors and the priors need linearising
         // (no window is converged yet: the flags were cleared with the damping)
         vf::launch_linearize_tail(e->v, slid, e->stream);
         HIPCHK(hipGetLastError());
-    } else if ((rc = vf_engine_linearize(e, 0))) return rc;
-    if ((rc = vf_engine_decide(e, 1))) return rc;
+    } else if ((rc = linearize(e, 0))) return rc;
+    if ((rc = decide(e, 1))) return rc;
     // One window under the termination rule (the GraphManager's solve): a trial the rule has made unnecessary is eight launches
     // that do nothing (2-4 us each).  Two trials are enqueued blind -- the rule needs two to see convergence, and that is what
     // a steady update takes --; before each further one the window's flag is read (one small synchronisation, paid only by the
@@ -280,7 +263,7 @@ static int iterate_sequence(vf_engine* e, int iterations) {
     // (also with far factors alive, where the staging itself is synchronous: a trial is 21 launches there)
     const bool adaptive = e->v.B == 1 && e->v.stop_on && e->async_on && e->own_stream && e->res_host && capturing == hipStreamCaptureStatusNone;
     // Without excursions to close behind the loop, the read is of the whole result block and comes after the FIRST trial already (a
-    // steady update converges in one: what used to follow was an empty trial, 15-21 launches): vf_engine::res_cached.
+    // steady update converges in one: what used to follow was an empty trial, 15-21 launches): SolveMemory::result_cached.
     const bool early = adaptive && e->excursion() == 0;
     bool finished = false;
     for (int it = 0; it < iterations; it++) {
@@ -288,8 +271,7 @@ static int iterate_sequence(vf_engine* e, int iterations) {
             vf::launch_read_result(e->v, 0, e->h_hi[0] - 1, 0, e->sticky_dev, e->res_host, e->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(e->stream));
-            e->res_carry[0] |= e->res_host->sticky[0];        // (consumed by the read: handed on with the final result, cached or not)
-            e->res_carry[1] |= e->res_host->sticky[1];
+            e->mem.sticky_consumed(e->res_host->sticky[0], e->res_host->sticky[1]);        // (handed on with the final result, cached or not)
             e->res_host->sticky[0] = e->res_host->sticky[1] = 0;
             if (e->res_host->pad) { finished = true; break; }
         } else if (adaptive && it >= 2) {
@@ -297,63 +279,57 @@ static int iterate_sequence(vf_engine* e, int iterations) {
             HIPCHK(hipStreamSynchronize(e->stream));
             if (e->res_host->pad) break;
         }
-        if ((rc = vf_engine_assemble(e))) return rc;
-        if ((rc = vf_engine_solve(e))) return rc;
+        if ((rc = assemble(e))) return rc;
+        if ((rc = solve(e))) return rc;
         if (e->v.min_fidelity > 0.0) vf::launch_model_change(e->v, e->stream);     // GTSAM's accept rule: what the linearised problem predicts
-        if ((rc = vf_engine_retract(e))) return rc;
-        if ((rc = vf_engine_linearize(e, 1))) return rc;
-        if ((rc = vf_engine_decide(e, 0))) return rc;
+        if ((rc = retract(e))) return rc;
+        if ((rc = linearize(e, 1))) return rc;
+        if ((rc = decide(e, 0))) return rc;
     }
-    if (iterations > 0 && e->excursion() > 0 && (rc = vf_engine_close_excursions(e))) return rc;
-    if (finished) { e->res_cached = true; e->res_slot = e->h_hi[0] - 1; }
+    if (iterations > 0 && e->excursion() > 0 && (rc = close_excursions(e))) return rc;
+    if (finished) e->mem.result_cached(e->h_hi[0] - 1);
     return VF_OK;
 }
-// the solve leaves every record, H row and g entry consistent with the current states: the next one may start warm.
-// (set by vf_engine_iterate, not by iterate_sequence: a hipGraph replay never runs the sequence's host code)
-static void mark_solved(vf_engine* e) {
-    e->warm = !e->no_warm && e->x_used == 0;     // (engines holding far between factors start every solve cold)
-    e->slid = 0;
-    e->redo = 0;
+// the sequence as plain launches (or under the capture of a caller's stream); on failure the engine is as after any call the
+// bookkeeping cannot follow
+static int iterate_plain(vf_engine* e, int iterations) {
+    const int rc = iterate_sequence(e, iterations);
+    if (rc) e->mem.rewritten();
+    else e->mem.solve_ended(e->x_used > 0, false);
+    return rc;
 }
 int vf_engine_iterate(vf_engine* e, int iterations) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (iterations < 0) return fail(VF_ERR_INVALID, "iterations < 0");
     if (int rc0 = not_sharded(e, "vf_engine_iterate")) return rc0;
     // (asynchronous, like the stages: every read-back synchronises the stream)
-    if (e->graph_off || !e->own_stream || e->refine_iters() > 0 || e->excursion() > 0) {
-        const int rc = iterate_sequence(e, iterations);
-        if (!rc) mark_solved(e);
-        return rc;
-    }
-    const int mode = (e->warm && e->v.sh_G <= 1 && e->slid + e->redo >= 1 && e->slid + e->redo <= 8) ? e->slid + e->redo : 0;
+    if (e->graph_off || !e->own_stream || e->refine_iters() > 0 || e->excursion() > 0) return iterate_plain(e, iterations);
+    const int mode = e->mem.tail();      // (baked into the captured sequence: a warm tail of another length is another graph)
+    bool replayed = true;                // ... nothing but the replay ran: no host code of the stages
     if (!e->graph_exec || e->graph_iters != iterations || e->graph_epoch != e->epoch || e->graph_mode != mode) {
         e->drop_graph();
         if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             e->graph_off = true;
-            const int rc = iterate_sequence(e, iterations);
-            if (!rc) mark_solved(e);
-            return rc;
+            return iterate_plain(e, iterations);
         }
         const int rc = iterate_sequence(e, iterations);
         const hipError_t ce = hipStreamEndCapture(e->stream, &e->graph);
-        if (rc) { e->drop_graph(); return rc; }
+        if (rc) { e->drop_graph(); e->mem.rewritten(); return rc; }
         if (ce != hipSuccess || hipGraphInstantiate(&e->graph_exec, e->graph, nullptr, nullptr, 0) != hipSuccess) {
             e->drop_graph();
             e->graph_off = true;          // this runtime cannot capture the sequence: plain launches from now on
             (void)hipGetLastError();
-            const int rc2 = iterate_sequence(e, iterations);
-            if (!rc2) mark_solved(e);
-            return rc2;
+            return iterate_plain(e, iterations);
         }
         e->graph_iters = iterations;
         e->graph_epoch = e->epoch;
         e->graph_mode = mode;
         e->graph_captures++;
+        replayed = false;
     }
     HIPCHK(hipGraphLaunch(e->graph_exec, e->stream));
     e->graph_replays++;
-    mark_solved(e);
+    e->mem.solve_ended(e->x_used > 0, replayed);
     return VF_OK;
 }
 int vf_engine_solve_form(vf_engine* e, int* form) {

@@ -1,36 +1,15 @@
-// engine/engine_staging.inc -- warm-start / incremental bookkeeping (touch), host -> device staging of states and factors, asynchronous staging, ingest.
+// engine/engine_staging.inc -- host -> device staging of states and factors, asynchronous staging, ingest.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 // Warm start across the GraphManager's call sequence (vf_solve: preintegrate / predict / set_between for the NEW keyframes,
 // marginalize + drop_oldest for the ones that leave, set_range): a call that only touches keyframe slots at or beyond the
 // window's current end leaves every existing record, H row and g entry those of the current states, exactly as
-// vf_engine_slide does -- the next vf_engine_iterate then linearises only what was appended (k_linearize_tail).  Engines
-// with one window only (`slid` is one count for the whole engine); anything else makes the next solve a cold start.
-// A factor record written a few slots INSIDE the window's end (late odometry for a keyframe an earlier solve already
-// covered) lengthens the tail that is linearised again (`redo`), up to the 8 keyframes k_linearize_tail handles.
-static void touch(vf_engine* e, int window, int first_slot) {
-    if (!e) return;
-    // (a record written within a factor's reach of the window's first keyframe may be one of the factors a marginalisation of
-    // that keyframe reads: what was computed ahead of time no longer stands)
-    if (window == 0 && first_slot <= e->h_lo[0] + VF_MAX_BANDWIDTH) e->ahead_valid = false;
-    if (e->inc_valid && e->v.B == 1 && window == 0 && first_slot > e->h_lo[0]) {
-        // (incremental engines follow a write anywhere behind the window's first keyframe: the update starts in front of it)
-        if (first_slot < e->inc_first_dirty) e->inc_first_dirty = first_slot;
-        if (!e->warm) return;
-        const int inside = e->h_hi[0] - first_slot;
-        if (inside > e->redo) e->redo = inside;
-        if (e->redo > 8) e->warm = false;
-        return;
-    }
-    if (e->warm && e->v.B == 1 && window == 0 && first_slot > e->h_lo[0]) {
-        const int inside = e->h_hi[0] - first_slot;          // <= 0: beyond the current end
-        if (inside > e->redo) e->redo = inside;
-        if (e->redo <= 8) return;
-    }
-    cold(e);
-}
-static int not_sharded_(vf_engine* e, const char* what) {
-    if (e && e->v.sh_G > 1) return fail(VF_ERR_INVALID, "%s: not for time-sharded engines", what);
+// vf_engine_slide does -- the next vf_engine_iterate then linearises only what was appended (k_linearize_tail).  Such calls
+// enter with Entry::appends(window, first slot); the rule itself is SolveMemory::written_from.
+static int not_sharded(vf_engine* e, const char* what) {
+    if (e->v.sh_G > 1)
+        return fail(VF_ERR_INVALID, "%s works on whole windows; this engine holds shard %d of %d (use the staged calls, "
+                    "include/vilfusion.h \"time-sharded windows\")", what, e->v.sh_r, e->v.sh_G);
     return VF_OK;
 }
 static int check_window(vf_engine* e, int window) {
@@ -46,20 +25,12 @@ static int check_range(vf_engine* e, int window, int k0, int n) {
 }
 
 int vf_engine_set_range(vf_engine* e, int window, int lo, int hi) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
+    // (inherited order: a bad argument is a rewrite, like any call the bookkeeping cannot follow)
     int rc = check_window(e, window);
-    if (rc) { if (e) cold(e); return rc; }
-    if (lo < 0 || hi < lo || hi > e->v.M) { cold(e); return fail(VF_ERR_BAD_KEY, "bad range [%d,%d)", lo, hi); }
-    // growing the end of the one window of a warm engine = appending keyframes (see touch()); its start is moved by
-    // vf_engine_drop_oldest only
-    const bool grows = e->v.B == 1 && lo == e->h_lo[0] && hi >= e->h_hi[0] && e->h_hi[0] > e->h_lo[0];
-    const bool inc_keeps = grows && e->inc_valid;
-    if (e->warm && grows) e->slid += hi - e->h_hi[0];
-    else cold(e);
-    if (inc_keeps) {
-        e->inc_valid = true;
-        if (hi > e->h_hi[0] && e->h_hi[0] < e->inc_first_dirty) e->inc_first_dirty = e->h_hi[0];
-    }
+    if (rc) { if (e) e->mem.rewritten(); return rc; }
+    if (lo < 0 || hi < lo || hi > e->v.M) { e->mem.rewritten(); return fail(VF_ERR_BAD_KEY, "bad range [%d,%d)", lo, hi); }
+    e->mem.range_set(lo, hi, e->h_lo[window], e->h_hi[window]);
     if (e->async_base()) {
         vf::launch_set_range(e->v, window, lo, hi, e->stream);
         HIPCHK(hipGetLastError());
@@ -73,16 +44,16 @@ int vf_engine_set_range(vf_engine* e, int window, int lo, int hi) {
     return VF_OK;
 }
 int vf_engine_set_async(vf_engine* e, int on) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (on) { int rc; if ((rc = e->ensure_async()) || (rc = e->ensure_side())) return rc; }
     e->async_on = on != 0;
     return VF_OK;
 }
 int vf_engine_read_result(vf_engine* e, int window, int slot, int estimate, double* state16, double* cost, int* accepted, int* rejected,
                           int* solve_failures, int* device_flags) {
-    const bool cached = e && e->res_cached && window == 0 && slot == e->res_slot && !estimate;     // (the guard below voids the cache)
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads, Entry::leaves_result);
+    const bool cached = e && e->mem.result_cached_for(window, slot, estimate != 0);
+    if (e) e->mem.entry_ran(false);      // (this read, like any other call, ends the cache)
     int rc = check_range(e, window, slot, 1);
     if (rc) return rc;
     if ((rc = e->ensure_async())) return rc;
@@ -92,9 +63,7 @@ int vf_engine_read_result(vf_engine* e, int window, int slot, int estimate, doub
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     vf::SolveResult& r = *e->res_host;
-    r.sticky[0] |= e->res_carry[0];
-    r.sticky[1] |= e->res_carry[1];
-    e->res_carry[0] = e->res_carry[1] = 0;
+    e->mem.sticky_handed_on(&r.sticky[0], &r.sticky[1]);
     if (state16) memcpy(state16, r.state, sizeof(r.state));
     if (cost) *cost = r.cost;
     if (accepted) *accepted = r.n_acc;
@@ -105,8 +74,7 @@ int vf_engine_read_result(vf_engine* e, int window, int slot, int estimate, doub
 }
 
 int vf_engine_set_states(vf_engine* e, int window, int k0, int n, const double* s) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (!s) return fail(VF_ERR_INVALID, "null states");
@@ -124,7 +92,7 @@ int vf_engine_set_states(vf_engine* e, int window, int k0, int n, const double* 
 }
 
 int vf_engine_get_states(vf_engine* e, int window, int k0, int n, double* s) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (!s) return fail(VF_ERR_INVALID, "null states");
@@ -140,8 +108,7 @@ int vf_engine_get_states(vf_engine* e, int window, int k0, int n, double* s) {
 }
 
 int vf_engine_set_imu(vf_engine* e, int window, int k0, int n, const double* rec) {
-    DeviceGuard dev_guard_(e);
-    touch(e, window, k0);
+    Entry entry_(e, Entry::appends(window, k0));
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (!rec) return fail(VF_ERR_INVALID, "null records");
@@ -156,12 +123,9 @@ int vf_engine_set_imu(vf_engine* e, int window, int k0, int n, const double* rec
 }
 
 int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec) {
-    DeviceGuard dev_guard_(e, true);
-    {
-        int first = 1 << 30;
-        for (int i = 0; i < n && b; i++) first = b[i] < first ? b[i] : first;
-        touch(e, window, n > 0 ? first : 0);
-    }
+    int first = n > 0 ? 1 << 30 : 0;
+    for (int i = 0; i < n && b; i++) first = b[i] < first ? b[i] : first;
+    Entry entry_(e, Entry::appends(window, first), Entry::overlaps);
     int rc = check_window(e, window);
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!a || !b || !rec))) return fail(VF_ERR_INVALID, "null argument");
@@ -201,11 +165,10 @@ int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, con
 }
 
 int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_window(e, window);
     if (rc) return rc;
-    if (int rs = not_sharded_(e, "vf_engine_set_extra_between")) return rs;
+    if (int rs = not_sharded(e, "vf_engine_set_extra_between")) return rs;
     if (n < 0 || n + e->h_ln(window) > e->x_cap)
         return fail(VF_ERR_CAPACITY, "at most %d far between factors per window (got %d, and %d carried on from keyframes that have been marginalised; "
                     "vf_engine_opts.max_far_factors raises the bound to %d)", e->x_cap, n, e->h_ln(window), VF_MAX_FAR_LIMIT);
@@ -283,8 +246,7 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
 }
 
 int vf_engine_clear_between(vf_engine* e, int window, int k0, int n) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0) return VF_OK;
@@ -294,8 +256,7 @@ int vf_engine_clear_between(vf_engine* e, int window, int k0, int n) {
 }
 
 int vf_engine_set_prior(vf_engine* e, int window, int k, const double* rec) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
+    Entry entry_(e, Entry::rewrites);
     int rc = check_range(e, window, k, 1);
     if (rc) return rc;
     if (!rec) return fail(VF_ERR_INVALID, "null record");
@@ -317,8 +278,7 @@ int vf_engine_set_prior(vf_engine* e, int window, int k, const double* rec) {
 
 int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_t* off, const double* steps,
                            const double* bhat, const vf_imu_params* p) {
-    DeviceGuard dev_guard_(e, true);
-    touch(e, window, k0);
+    Entry entry_(e, Entry::appends(window, k0), Entry::overlaps);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (!off || !bhat || !p) return fail(VF_ERR_INVALID, "null argument");
@@ -374,7 +334,7 @@ int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_
 
 int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* steps, const vf_imu_params* p,
                           const int32_t* btw_a, const double* btw_rec) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e || !step_off || !p || !btw_a || !btw_rec) return fail(VF_ERR_INVALID, "null argument");
     const int B = e->v.B, M = e->v.M, W = e->opts.bandwidth;
     const int total = step_off[B];
@@ -415,8 +375,7 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
 }
 
 int vf_engine_ingest_status(vf_engine* e, float* h2d_ms, float* k0_ms) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (h2d_ms) *h2d_ms = 0.f;
     if (k0_ms) *k0_ms = 0.f;
     if (!e->in_pending) return VF_OK;
@@ -434,7 +393,7 @@ int vf_engine_ingest_status(vf_engine* e, float* h2d_ms, float* k0_ms) {
 }
 
 int vf_engine_get_imu(vf_engine* e, int window, int k0, int n, double* rec) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_range(e, window, k0, n);
     if (rc) return rc;
     if (n == 0 || !rec) return VF_OK;

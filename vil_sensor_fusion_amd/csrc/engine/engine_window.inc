@@ -1,20 +1,18 @@
 // engine/engine_window.inc -- the fixed-lag window: marginalisation (and ahead of time), far factors across a slide, slide, compaction, growth.
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
-// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, DeviceGuard, cold) are in vf_engine.hip.
+// compiled by itself.  struct vf_engine and the helpers every section uses (fail, HIPCHK, Entry) are in vf_engine.hip.
 int vf_engine_marginalize(vf_engine* e) {
-    DeviceGuard dev_guard_(e, e && e->async_now());
+    VF_ENTER(e, Entry::reads, Entry::overlaps_if(e && e->async_now()));
     // (reads the current linearisation, writes the marginal prior: what a warm start expects to have changed)
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
     if (int rc = not_sharded(e, "vf_engine_marginalize")) return rc;
     for (int w = 0; w < e->v.B; w++)
         if (e->h_hi[w] - e->h_lo[w] < 4) return fail(VF_ERR_INVALID, "window %d: marginalisation needs >= 4 keyframes", w);
-    if (e->async_now() && e->ahead_valid && e->ahead_lo == e->h_lo[0]) {
+    if (e->async_now() && e->mem.stash_fits(e->h_lo[0])) {
         // computed behind the previous solve (vf_engine_marginalize_ahead, on the side stream): put in place
         if (e->side_open) { if (int rj = e->join_side()) return rj; }
         vf::launch_marg_commit(e->v, e->marg_stash, e->stream);
         HIPCHK(hipGetLastError());
-        e->ahead_valid = false;
-        e->ahead_used++;
+        e->mem.stash_committed();
         e->marg_since_drop = true;
         return VF_OK;
     }
@@ -180,11 +178,10 @@ int vf_engine_get_extra_between(vf_engine* e, int window, int* n, int32_t* a, in
 }
 
 int vf_engine_marginalize_ahead(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     // (a warm engine: its records are those of the current states -- what a marginalisation reads -- and stay so while only
-    // appends follow; anything else voids the stash through cold())
-    if (!e->async_now() || !e->warm || e->h_hi[0] - e->h_lo[0] < 4) return VF_OK;
+    // appends follow; anything else voids the stash: SolveMemory)
+    if (!e->async_now() || !e->mem.is_warm() || e->h_hi[0] - e->h_lo[0] < 4) return VF_OK;
     if (int rc = e->ensure_async()) return rc;
     if (!e->marg_stash) {
         HIPCHK(hipMalloc((void**)&e->marg_stash, (size_t)e->v.B * vf::MARG_STASH_DOUBLES * sizeof(double)));
@@ -198,14 +195,11 @@ int vf_engine_marginalize_ahead(vf_engine* e) {
     e->side_open = true;
     vf::launch_marginalize_ahead(e->v, e->sticky_dev + 1, e->marg_stash, e->stream2);
     HIPCHK(hipGetLastError());
-    e->ahead_valid = true;
-    e->ahead_lo = e->h_lo[0];
-    e->ahead_made++;
+    e->mem.stashed(e->h_lo[0]);
     return VF_OK;
 }
 int vf_engine_drop_oldest(vf_engine* e) {
-    DeviceGuard dev_guard_(e, e && e->async_now());
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads, Entry::overlaps_if(e && e->async_now()));
     if (e->async_now()) {
         for (int w = 0; w < e->v.B; w++)
             if (e->h_hi[w] - e->h_lo[w] < 2) return fail(VF_ERR_INVALID, "window %d too short", w);
@@ -235,7 +229,7 @@ int vf_engine_drop_oldest(vf_engine* e) {
 }
 
 int vf_engine_slide(vf_engine* e, const double* prior_sigma15, int marginalize) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     if (!e || !prior_sigma15) return fail(VF_ERR_INVALID, "null argument");
     for (int w = 0; w < e->v.B; w++)
         if (e->h_hi[w] >= e->v.M) return fail(VF_ERR_CAPACITY, "window %d has no free keyframe slot", w);
@@ -245,8 +239,7 @@ int vf_engine_slide(vf_engine* e, const double* prior_sigma15, int marginalize) 
     }
     if (int rc = transport_far(e, marginalize != 0)) return rc;
     e->marg_since_drop = false;
-    if (e->warm) e->slid++;   // a slide is a change a warm start knows how to follow
-    if (e->inc_valid) e->inc_slid++;
+    e->mem.slid_by_one();
     // the sigmas are a caller temporary: uploaded (and waited for) only when they differ from what the device already holds, so
     // that a run of updates with the same sigmas -- every fixed-lag loop -- enqueues without a host synchronisation
     const bool fresh_sigma = !e->sigma_valid || memcmp(e->sigma_host, prior_sigma15, sizeof(e->sigma_host)) != 0;
@@ -263,7 +256,7 @@ int vf_engine_slide(vf_engine* e, const double* prior_sigma15, int marginalize) 
 }
 
 int vf_engine_read_marginal(vf_engine* e, int window, int* on, double* xbar48, double* L729, double* eta27) {
-    DeviceGuard dev_guard_(e);
+    Entry entry_(e, Entry::reads);
     int rc = check_window(e, window);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -277,12 +270,10 @@ int vf_engine_read_marginal(vf_engine* e, int window, int* on, double* xbar48, d
 // Move the live keyframes [shift, M) of every window to [0, M - shift): frees `shift` slots at the
 // end.  shift must be a multiple of 64 (whole AoSoA tiles) and <= every window's lo.
 int vf_engine_compact(vf_engine* e, int shift) {
-    DeviceGuard dev_guard_(e);
-    if (e) cold(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::rewrites);
     vf::View& v = e->v;
     if (shift <= 0 || shift % 64 != 0 || shift >= v.M) return fail(VF_ERR_INVALID, "shift must be a positive multiple of 64 below the capacity");
-    e->sig_valid = false;       // (the covariance blocks stay in the slots they were computed for)
+    e->mem.compacted();
     for (int w = 0; w < v.B; w++)
         if (e->h_lo[w] < shift) return fail(VF_ERR_BAD_KEY, "window %d: lo %d < shift %d (live keyframes would be lost)", w, e->h_lo[w], shift);
     const size_t keepk = (size_t)(v.M - shift);              // slots kept per window
@@ -365,8 +356,7 @@ int vf_engine_compact(vf_engine* e, int shift) {
 // handle the caller holds stays valid).  Inputs and states only: every linearisation, H, g and panel is recomputed by
 // the next (cold) solve.
 int vf_engine_grow(vf_engine* e, int new_capacity) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     if (int rc0 = not_sharded(e, "vf_engine_grow")) return rc0;
     const int M0 = e->v.M, M1 = (new_capacity + 63) / 64 * 64;
     if (M1 <= M0) return fail(VF_ERR_INVALID, "new capacity %d does not exceed the current %d", new_capacity, M0);
@@ -378,7 +368,8 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
     const vf::View &a = e->v, &b = n->v;
     const int B = a.B;
     const size_t G0 = (size_t)a.G, G1 = (size_t)b.G;
-    // every copy through one lambda that remembers the first failure: the new engine is destroyed on any error path
+    // every copy through one of two lambdas that remember the first failure; `copied` waits for them: the new engine is destroyed
+    // on any error path
     hipError_t herr = hipStreamSynchronize(e->stream);
     auto cp = [&](void* dst, const void* src, size_t bytes) {
         if (herr == hipSuccess) herr = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, n->stream);
@@ -388,6 +379,12 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
     auto cp2 = [&](void* dst, const void* src, size_t unit) {
         if (herr == hipSuccess)
             herr = hipMemcpy2DAsync(dst, (size_t)M1 * unit, src, (size_t)M0 * unit, (size_t)M0 * unit, (size_t)B, hipMemcpyDeviceToDevice, n->stream);
+    };
+    auto copied = [&]() -> int {
+        if (herr == hipSuccess) herr = hipStreamSynchronize(n->stream);
+        if (herr == hipSuccess) return VF_OK;
+        vf_engine_destroy(n);
+        return fail(VF_ERR_DEVICE, "vf_engine_grow: device copy failed: %s", hipGetErrorString(herr));
     };
     for (int pl = 0; pl < 32; pl++) cp2(b.x + (size_t)pl * G1, a.x + (size_t)pl * G0, sizeof(double));     // state planes [2][16][G]
     cp2(b.imu_in, a.imu_in, vf::IMU_IN * sizeof(double));        // AoSoA tiles of 64 slots: whole tiles move (M0, M1 are multiples of 64)
@@ -402,11 +399,7 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
         {b.n_acc, a.n_acc, B * sizeof(int)}, {b.n_rej, a.n_rej, B * sizeof(int)}, {b.n_fail, a.n_fail, B * sizeof(int)},
         {n->lambda0_dev, e->lambda0_dev, B * sizeof(double)}};
     for (auto& c : per_window) cp(c.d, c.s, c.bytes);
-    if (herr == hipSuccess) herr = hipStreamSynchronize(n->stream);
-    if (herr != hipSuccess) {
-        vf_engine_destroy(n);
-        return fail(VF_ERR_DEVICE, "vf_engine_grow: device copy failed: %s", hipGetErrorString(herr));
-    }
+    if ((rc = copied())) return rc;
     n->h_lo = e->h_lo;
     n->h_hi = e->h_hi;
     if (e->v.stop_on && (rc = vf_engine_set_convergence(n, e->v.rel_tol, e->v.abs_tol))) { vf_engine_destroy(n); return rc; }
@@ -419,13 +412,12 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
         if (linear) {
             if ((rc = n->ensure_far(e->x_used))) { vf_engine_destroy(n); return rc; }
             const size_t Bx = (size_t)B * e->x_cap;       // (n is made from e->opts: the same x_cap)
-            hipError_t he = hipMemcpyAsync(n->v.xl_n, e->v.xl_n, B * sizeof(int), hipMemcpyDeviceToDevice, n->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(n->v.xl_b, e->v.xl_b, Bx * sizeof(int), hipMemcpyDeviceToDevice, n->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(n->v.xl_U, e->v.xl_U, Bx * 6 * (27 + 6 * (size_t)e->x_cap) * sizeof(double), hipMemcpyDeviceToDevice, n->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(n->v.xl_r0, e->v.xl_r0, Bx * 6 * sizeof(double), hipMemcpyDeviceToDevice, n->stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(n->v.xl_bx, e->v.xl_bx, Bx * 7 * sizeof(double), hipMemcpyDeviceToDevice, n->stream);
-            if (he == hipSuccess) he = hipStreamSynchronize(n->stream);
-            if (he != hipSuccess) { vf_engine_destroy(n); return fail(VF_ERR_DEVICE, "vf_engine_grow: device copy failed: %s", hipGetErrorString(he)); }
+            cp(n->v.xl_n, e->v.xl_n, B * sizeof(int));
+            cp(n->v.xl_b, e->v.xl_b, Bx * sizeof(int));
+            cp(n->v.xl_U, e->v.xl_U, Bx * 6 * (27 + 6 * (size_t)e->x_cap) * sizeof(double));
+            cp(n->v.xl_r0, e->v.xl_r0, Bx * 6 * sizeof(double));
+            cp(n->v.xl_bx, e->v.xl_bx, Bx * 7 * sizeof(double));
+            if ((rc = copied())) return rc;
             n->attach_far();
             n->h_lb = e->h_lb;
         }
@@ -437,40 +429,20 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
         n->recount_far();
     }
     // what the solver remembers from solve to solve: the non-monotone rule's damping / excursion state (a whole-history handle
-    // grows again and again: each solve after a grow would otherwise restart from lambda0) and the far factors' counters
+    // grows again and again: each solve after a grow would otherwise restart from lambda0)
     if (e->v.x_best) {
         if ((rc = n->ensure_excursion())) { vf_engine_destroy(n); return rc; }
-        hipError_t he = hipSuccess;
-        auto cpx = [&](void* dst, const void* src, size_t bytes) { if (he == hipSuccess) he = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, n->stream); };
-        cpx(n->v.carry, e->v.carry, B * sizeof(int));
-        cpx(n->v.n_prov, e->v.n_prov, B * sizeof(int));
-        cpx(n->v.prov, e->v.prov, B * sizeof(int));
-        cpx(n->v.ref_cost, e->v.ref_cost, B * sizeof(double));
-        for (int pl = 0; pl < 16 && he == hipSuccess; pl++)
-            he = hipMemcpy2DAsync(n->v.x_best + (size_t)pl * G1, (size_t)M1 * sizeof(double), e->v.x_best + (size_t)pl * G0, (size_t)M0 * sizeof(double),
-                                  (size_t)M0 * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, n->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(n->stream);
-        if (he != hipSuccess) { vf_engine_destroy(n); return fail(VF_ERR_DEVICE, "vf_engine_grow: device copy failed: %s", hipGetErrorString(he)); }
+        cp(n->v.carry, e->v.carry, B * sizeof(int));
+        cp(n->v.n_prov, e->v.n_prov, B * sizeof(int));
+        cp(n->v.prov, e->v.prov, B * sizeof(int));
+        cp(n->v.ref_cost, e->v.ref_cost, B * sizeof(double));
+        for (int pl = 0; pl < 16; pl++) cp2(n->v.x_best + (size_t)pl * G1, e->v.x_best + (size_t)pl * G0, sizeof(double));
+        if ((rc = copied())) return rc;
     }
-    n->far_transported = e->far_transported;
-    n->far_ended = e->far_ended;
-    n->far_absorbed = e->far_absorbed;
-    n->marg_since_drop = e->marg_since_drop;
-    n->inc_updates = e->inc_updates;
-    n->inc_full = e->inc_full;
-    n->own_stream = e->own_stream;
-    std::swap(*e, *n);             // *e: the grown engine; *n: the old buffers
-    n->own_stream = false;         // (the stream lives on in *e)
-    // the asynchronous-staging resources (second stream, events, sticky words, pinned result block) move with the handle too
-    std::swap(e->async_on, n->async_on);
-    std::swap(e->stream2, n->stream2);
-    std::swap(e->ev_fork, n->ev_fork);
-    std::swap(e->ev_join, n->ev_join);
-    std::swap(e->sticky_dev, n->sticky_dev);
-    std::swap(e->res_host, n->res_host);
+    // the arrays change places; the handle -- stream, asynchronous-staging resources, the counters -- stays (EngineHandle)
+    e->swap_arrays(*n);
     vf_engine_destroy(n);
-    cold(e);
-    e->slid = e->redo = 0;
+    e->mem.grown();
     e->epoch++;
     // the linearisation of the current states is part of the state other entry points rely on (vf_engine_marginalize reads
     // the Jacobians of the oldest keyframe's factors): recompute it in the new buffers
@@ -482,8 +454,7 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
 }
 
 int vf_engine_sync(vf_engine* e) {
-    DeviceGuard dev_guard_(e);
-    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    VF_ENTER(e, Entry::reads);
     HIPCHK(hipStreamSynchronize(e->stream));
     return VF_OK;
 }

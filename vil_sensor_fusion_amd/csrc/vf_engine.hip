@@ -20,6 +20,7 @@
 
 #include "../../include/vilfusion.h"
 #include "vf_kernels.hpp"
+#include "vf_engine_memory.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -42,24 +43,56 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace
 
 struct vf_engine;
-// HIP's current device is per host thread: every entry point that takes an engine makes the engine's device current for
-// the duration of the call (allocations, copies and launches would otherwise go to whatever device the calling thread
-// last used -- e.g. a ROS spinner thread driving a GraphManager on device 1) and restores the caller's on return.
-struct DeviceGuard {
+// The head of every entry point that takes an engine, in one line: the engine (null: nothing happens, the entry point refuses
+// it next), whether the call may overlap the side stream's work (see EngineHandle::side_open), what it does to what the device
+// holds from the last solve (vf_engine_memory.hpp), and whether it leaves the cached result block alone.  From these it joins
+// the side stream, voids the cached result, fires the event, and makes the engine's device current for the duration of the
+// call -- HIP's current device is per host thread: allocations, copies and launches would otherwise go to whatever device
+// the calling thread last used (e.g. a ROS spinner thread driving a GraphManager on device 1) -- restoring the caller's on return.
+struct Entry {
+    struct Effect { int kind, window, slot; };
+    static constexpr Effect reads{0, 0, 0}, rewrites{2, 0, 0};
+    static constexpr Effect appends(int window, int slot) { return {1, window, slot}; }
+    enum { overlaps = 1, leaves_result = 2 };
+    static constexpr int overlaps_if(bool yes) { return yes ? overlaps : 0; }
+    Entry(vf_engine* e, Effect does, int flags = 0);
+    ~Entry() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
+    Entry(const Entry&) = delete;
+    Entry& operator=(const Entry&) = delete;
+    vf_engine* const engine;
     int prev = -1, want = -1;
-    // overlap_ok: the entry point touches nothing the side stream's work does (see vf_engine::side_open)
-    explicit DeviceGuard(const vf_engine* e, bool overlap_ok = false);
-    ~DeviceGuard() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+// ... and the refusal of a null engine with it
+#define VF_ENTER(...) Entry entry_(__VA_ARGS__); if (!entry_.engine) return fail(VF_ERR_INVALID, "engine is null")
 
-struct vf_engine {
-    vf::View v{};
-    vf_engine_opts opts{};
-    vf_engine_tuning tune{};
+// What belongs to the HANDLE the caller holds: it stays when vf_engine_grow replaces the arrays behind it.
+struct EngineHandle {
     hipStream_t stream = nullptr;
     bool own_stream = true;   // false once the caller has handed in its own stream (vf_engine_set_stream)
+    // Asynchronous staging (vf_engine_set_async; the GraphManager's engine): the staging calls of a vf_solve -- preintegrate,
+    // set_between, marginalize, drop_oldest, set_range -- enqueue and return; what the device finds wrong (a preintegrated
+    // covariance or a marginalisation pivot that is not positive definite) is OR-ed into two sticky words that
+    // vf_engine_read_result hands back with the solve's result, in the one synchronisation a solve needs.  The marginalisation
+    // of the keyframe that leaves runs on a second stream beside K0 / prediction / staging of the one that arrives (they
+    // touch opposite ends of the window): side_open until the main stream has been made to wait for it (join_side, at
+    // every entry point that is not one of those three).
+    bool async_on = false, side_open = false;
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int* sticky_dev = nullptr;
+    vf::SolveResult* res_host = nullptr;
+    long far_transported = 0, far_ended = 0, far_absorbed = 0;   // far factors moved on to the next keyframe when theirs left the window /
+                                                                 // dropped without a marginalisation / absorbed into the marginal prior
+    bool marg_since_drop = false;   // vf_engine_marginalize ran since the last vf_engine_drop_oldest (the GraphManager's call pair)
+    long inc_updates = 0, inc_full = 0;      // incremental updates so far; those that eliminated from the window's first keyframe
+};
+
+// ... and everything else belongs to the device ARRAYS (and what the host knows about them), which a grown engine replaces whole
+struct vf_engine : EngineHandle {
+    vf::View v{};
+    vf::SolveMemory mem;     // what the arrays still hold from the last solve
+    vf_engine_opts opts{};
+    vf_engine_tuning tune{};
     // vf_engine_opts.use_hip_graph: vf_engine_iterate replays its launch sequence (6 + 9 K kernels / memsets) from a captured
     // hipGraph; re-captured when the trial count or any scalar baked into the kernel arguments changes
     hipGraph_t graph = nullptr;
@@ -86,33 +119,9 @@ struct vf_engine {
     bool sigma_valid = false;
     int* status_dev = nullptr;
     std::vector<int> h_lo, h_hi;  // host mirror of the active ranges
-    // Warm start of vf_engine_iterate: true from the end of a solve until any entry point other than vf_engine_slide
-    // touches the engine; `slid` counts the slides since.  See k_linearize_tail.
-    bool warm = false;
-    int slid = 0;             // keyframes appended since the last solve
-    int redo = 0;             // slots in front of the old window end whose factors changed since (see touch())
-    bool no_warm = false;     // vf_engine_opts.cold_start: every solve starts cold (tests compare the two)
-    // Incremental updates (vf_engine_opts.incremental; vf_kernels.hpp "Incremental Gauss-Newton updates"): inc_valid = the panels
-    // and checkpoints on the device are those of the problem as it was after the last vf_engine_isam_step, and everything
-    // that changed since is an append -- inc_slid slides, or (one-window engines) writes at or beyond slot inc_first_dirty.
-    // Any other entry point that writes (cold()) voids it: the next update eliminates the whole window.
-    // Asynchronous staging (vf_engine_set_async; the GraphManager's engine): the staging calls of a vf_solve -- preintegrate,
-    // set_between, marginalize, drop_oldest, set_range -- enqueue and return; what the device finds wrong (a preintegrated
-    // covariance or a marginalisation pivot that is not positive definite) is OR-ed into two sticky words that
-    // vf_engine_read_result hands back with the solve's result, in the one synchronisation a solve needs.  The marginalisation
-    // of the keyframe that leaves runs on a second stream beside K0 / prediction / staging of the one that arrives (they
-    // touch opposite ends of the window): side_open until the main stream has been made to wait for it (join_side, at
-    // every entry point that is not one of those three).
-    bool async_on = false, side_open = false;
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int* sticky_dev = nullptr;
-    vf::SolveResult* res_host = nullptr;
     // The adaptive trial loop of vf_engine_iterate reads the whole result block where it used to read the `done` flag: when the flag
-    // is up the solve is over and the block IS the result -- the vf_engine_read_result that follows finds it here (res_cached, until
-    // any other entry point runs) and costs no second synchronisation.  Sticky words an early read has consumed wait in res_carry.
-    bool res_cached = false;
-    int res_slot = -1, res_carry[2] = {0, 0};
+    // is up the solve is over and the block IS the result -- the vf_engine_read_result that follows finds it in res_host
+    // (SolveMemory::result_cached_for, until any other entry point runs) and costs no second synchronisation.
     int ensure_async() {          // the sticky words and the pinned result block (every engine may be asked for a vf_engine_read_result)
         if (res_host) return VF_OK;
         HIPCHK(hipMalloc((void**)&sticky_dev, 2 * sizeof(int)));
@@ -141,15 +150,8 @@ struct vf_engine {
     bool async_now() const { return async_base() && x_used == 0; }
     bool async_far() const { return async_base() && x_used > 0; }
     // vf_engine_marginalize_ahead: the marginal prior the next vf_engine_marginalize will need, computed behind the solve that has
-    // just ended (the linearisation it reads is final by then) into marg_stash; valid while nothing but appends has happened
-    // since and the window's first keyframe is still ahead_lo
+    // just ended (the linearisation it reads is final by then) into marg_stash (SolveMemory::stash_fits)
     double* marg_stash = nullptr;
-    bool ahead_valid = false;
-    int ahead_lo = -1;
-    long ahead_used = 0, ahead_made = 0;
-    bool inc_valid = false;
-    int inc_slid = 0, inc_first_dirty = 0x7fffffff;
-    long inc_updates = 0, inc_full = 0;      // incremental updates so far; those that eliminated from the window's first keyframe
     // hybrid K4 (vf_kernels.hpp "View::gate"): buffers and chunk count of the partitioned form for a sweep engine, allocated
     // when the termination rule is first switched on
     bool hybrid = false;
@@ -250,9 +252,6 @@ struct vf_engine {
     double* x_gtmp = nullptr;
     double* x_Z = nullptr;
     size_t x_zstride = 0;
-    long far_transported = 0, far_ended = 0, far_absorbed = 0;   // far factors moved on to the next keyframe when theirs left the window /
-                                                                 // dropped without a marginalisation / absorbed into the marginal prior
-    bool marg_since_drop = false;   // vf_engine_marginalize ran since the last vf_engine_drop_oldest (the GraphManager's call pair)
     int x_zslots = 0;          // slots x_Z holds columns for (6 columns each); grown on demand, never beyond x_cap
     int x_cap = VF_MAX_EXTRA;  // far factors a window may hold (vf_engine_opts.max_far_factors): the width of the device lists
     // the device lists are allocated once (they stay in `allocs`); a failure half way leaves what exists in place and a
@@ -266,6 +265,7 @@ struct vf_engine {
     vf_engine* far_columns = nullptr;
     bool is_far_columns = false;
     bool far_columns_off = false;   // a column engine could not be made: the columns are solved one after the other
+                                    // (with the arrays, so a grown engine tries again: ADVICE round 6, "far_columns_off is not carried")
     // linear far factors (View::xl_*; made and kept by k_marginalize): the host mirrors only their number and far ends
     std::vector<std::vector<int>> h_lb;
     int h_ln(int w) const { return h_lb.empty() ? 0 : (int)h_lb[w].size(); }
@@ -361,17 +361,18 @@ struct vf_engine {
     }
     // marginal covariances (engine/engine_marginals.inc): [G][SIG_SLOT] blocks + per-window failure flags, a zero lambda and
     // all-ones `fresh` flags for the undamped factorisation, one allocation made by the first vf_engine_marginals; sig_lo /
-    // sig_hi: the ranges the blocks were computed for
+    // sig_hi: the ranges the blocks were computed for (SolveMemory::covariances_valid)
     double* sig = nullptr;
     double* sig_zero = nullptr;
     int *sig_fail = nullptr, *sig_ones = nullptr;
     long sig_G = 0;
-    bool sig_valid = false;
     std::vector<int> sig_lo, sig_hi;
     // vf_engine_marginals_ex with VF_MARGINALS_FAR: Z = A^-1 U and the m x m systems of a group of windows (vf::FarCov), allocated
     // on first use and grown when a later call needs more; FARCOV_BUDGET bounds it, more windows than fit are done in groups
     double* fc_scratch = nullptr;
     size_t fc_doubles = 0;
+    // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
+    void swap_arrays(vf_engine& o) { std::swap(*this, o), std::swap<EngineHandle>(*this, o); }
     int ensure_stage(size_t bytes) {
         if (bytes <= stage_bytes) return VF_OK;
         if (stage) HIPCHK(hipFree(stage));
@@ -383,17 +384,12 @@ struct vf_engine {
     }
 };
 
-// anything the warm start / the incremental update do not know how to follow: the next solve starts from nothing
-static inline void cold(vf_engine* e) {
-    e->warm = false;
-    e->inc_valid = false;
-    e->ahead_valid = false;
-}
-
-DeviceGuard::DeviceGuard(const vf_engine* e, bool overlap_ok) {
+Entry::Entry(vf_engine* e, Effect does, int flags) : engine(e) {
     if (!e) return;
-    if (!overlap_ok && e->side_open) (void)const_cast<vf_engine*>(e)->join_side();
-    const_cast<vf_engine*>(e)->res_cached = false;
+    if (!(flags & overlaps) && e->side_open) (void)e->join_side();
+    e->mem.entry_ran(flags & leaves_result);
+    if (does.kind == 2) e->mem.rewritten();
+    else if (does.kind == 1) e->mem.written_from(does.window, does.slot, e->h_lo[0], e->h_hi[0]);
     want = e->opts.device;
     if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipSetDevice(want); return; }
     if (prev != want) (void)hipSetDevice(want);

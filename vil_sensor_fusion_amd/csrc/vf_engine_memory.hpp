@@ -1,0 +1,114 @@
+// vf_engine_memory.hpp -- what the device still holds from the last solve, and what voids it: one account, kept here and
+// nowhere else.  Host code without HIP (tests/native/engine_memory.cpp checks it on the CPU).
+//
+// Five things outlive a solve on the device and let the next call do less: the linearisation of the current states (warm
+// start: the next solve linearises only a tail), the panels and checkpoints of the incremental update, a marginal prior
+// computed ahead of time, the result block an adaptive solve has already read, and the covariance blocks.  Every entry point
+// of the engine says what it did through one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
+#pragma once
+
+#include <algorithm>
+#include <climits>
+
+#include "../../include/vilfusion.h"
+
+namespace vf {
+
+// keyframes at a window's end that k_linearize_tail linearises again (one thread per keyframe, a handful of them): the
+// longest tail a warm solve takes; a longer one is a cold start
+constexpr int LINEARIZE_TAIL_MAX = 8;
+
+class SolveMemory {
+  public:
+    // the facts about the engine the rules need: `slid` is one count for the whole engine, so appends are followed on
+    // one-window engines only; time-sharded engines and vf_engine_opts.cold_start never start warm
+    bool one_window = true, sharded = false, no_warm = false;
+
+    // ---- events.  lo / hi: window 0's range as it is when the event fires (the engine's own mirror, passed in, not kept here)
+    // something the bookkeeping cannot follow was written: the next solve / update / marginalisation starts from nothing
+    void rewritten() { warm_ = inc_valid_ = ahead_valid_ = false; }
+    // records were written from slot k of window w onwards.  At or beyond the end it is an append; up to LINEARIZE_TAIL_MAX slots
+    // inside it (late odometry for a keyframe an earlier solve covered) the warm tail grows; the incremental update follows
+    // a write anywhere behind the window's first keyframe.  Everything else is rewritten().
+    void written_from(int w, int k, int lo, int hi) {
+        // (within a factor's reach of the first keyframe: it may be a factor the marginalisation of that keyframe reads)
+        if (w == 0 && k <= lo + VF_MAX_BANDWIDTH) ahead_valid_ = false;
+        if (!behind_first(w, k, lo) || !(warm_ || inc_valid_)) return rewritten();
+        if (inc_valid_) inc_first_dirty_ = std::min(inc_first_dirty_, k);
+        if (!warm_) return;
+        redo_ = std::max(redo_, hi - k);          // (<= 0: beyond the current end)
+        if (redo_ > LINEARIZE_TAIL_MAX) warm_ = false, ahead_valid_ = ahead_valid_ && inc_valid_;   // (inherited: an incremental engine keeps its stash here)
+    }
+    // the range of a window became [lo, hi); it was [old_lo, old_hi).  Growing the end of the one window of an engine is an
+    // append of hi - old_hi keyframes (its start is moved by slid_by_one / vf_engine_drop_oldest only).
+    void range_set(int lo, int hi, int old_lo, int old_hi) {
+        if (!(one_window && lo == old_lo && hi >= old_hi && old_hi > old_lo)) return rewritten();
+        if (warm_) slid_ += hi - old_hi;
+        else ahead_valid_ = false;
+        if (inc_valid_ && hi > old_hi) inc_first_dirty_ = std::min(inc_first_dirty_, old_hi);
+    }
+    // every window slid by one keyframe (vf_engine_slide): a change both the warm start and the incremental update follow
+    void slid_by_one() { slid_ += warm_, inc_slid_ += inc_valid_; }
+    // a solve ended: every record, H row and g entry is that of the current states.  Engines holding far factors start every
+    // solve cold.  replayed: the solve was a hipGraph replay, which runs no host code of the stages -- the panels of the
+    // incremental update and the stash survive it ("ahead_valid is voided only through cold()": the fix is
+    // to drop the condition below).
+    void solve_ended(bool far_alive, bool replayed) {
+        if (!replayed) rewritten();
+        warm_ = !no_warm && !far_alive;
+        slid_ = redo_ = 0;
+    }
+    // an incremental update ended: its panels and checkpoints are those of the problem as it stands, or (failed) of nothing
+    void inc_update_ended(bool ok) { rewritten(), inc_slid_ = 0, inc_first_dirty_ = INT_MAX, inc_valid_ = ok; }
+    // states from slot k of window w onwards were predicted from the estimate: a rewrite for the warm start and the stash,
+    // an append for the incremental update if it lies behind the first keyframe of a one-window engine
+    void predicted_from_estimate(int w, int k, int lo) {
+        if (inc_valid_ && behind_first(w, k, lo)) inc_first_dirty_ = std::min(inc_first_dirty_, k);
+        else inc_valid_ = false;
+        warm_ = ahead_valid_ = false;
+    }
+    // the window was compacted: the covariance blocks stay in the slots they were computed for
+    void compacted() { rewritten(), sig_valid_ = false; }
+    // the engine was grown: new arrays, nothing linearised in them yet
+    void grown() { rewritten(), slid_ = redo_ = 0; }
+    // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
+    void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
+    void stash_committed() { ahead_valid_ = false; }
+    // the result block of window 0, slot s is in the pinned buffer; sticky words an early read consumed wait for the final one
+    void result_cached(int slot) { res_cached_ = true, res_slot_ = slot; }
+    void sticky_consumed(int s0, int s1) { res_carry_[0] |= s0, res_carry_[1] |= s1; }
+    void sticky_handed_on(int* s0, int* s1) {
+        *s0 |= res_carry_[0], *s1 |= res_carry_[1];
+        res_carry_[0] = res_carry_[1] = 0;
+    }
+    // an entry point ran: the cached result is void, unless the entry point leaves the result block alone
+    void entry_ran(bool leaves_result) { res_cached_ = res_cached_ && leaves_result; }
+    void covariances_computed() { sig_valid_ = true; }
+
+    // ---- queries
+    // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
+    // vf_engine_iterate and the key of its captured graph both take it from here.
+    int tail() const { return warm_ && !sharded && slid_ + redo_ >= 1 && slid_ + redo_ <= LINEARIZE_TAIL_MAX ? slid_ + redo_ : 0; }
+    bool is_warm() const { return warm_; }
+    // the next incremental update eliminates the whole window / how many keyframes at the end of [lo, hi) are new to it
+    bool inc_whole_window() const { return !inc_valid_; }
+    int inc_appended(int hi) const { return one_window && inc_first_dirty_ != INT_MAX ? std::max(inc_slid_, hi - inc_first_dirty_) : inc_slid_; }
+    bool inc_slid() const { return inc_slid_ > 0; }
+    bool stash_fits(int lo) const { return ahead_valid_ && ahead_lo_ == lo; }
+    bool result_cached_for(int window, int slot, bool estimate) const { return res_cached_ && window == 0 && slot == res_slot_ && !estimate; }
+    bool covariances_valid() const { return sig_valid_; }
+
+  private:
+    bool behind_first(int w, int k, int lo) const { return one_window && w == 0 && k > lo; }
+    bool warm_ = false;
+    int slid_ = 0, redo_ = 0;     // keyframes appended since the last solve / slots in front of the old end whose factors changed
+    bool inc_valid_ = false;      // the panels are those of the problem after the last update, and all that changed since is an append:
+    int inc_slid_ = 0, inc_first_dirty_ = INT_MAX;      // ... that many slides, or writes at or beyond this slot
+    bool ahead_valid_ = false;
+    int ahead_lo_ = -1;
+    bool res_cached_ = false;
+    int res_slot_ = -1, res_carry_[2] = {0, 0};
+    bool sig_valid_ = false;
+};
+
+}  // namespace vf
