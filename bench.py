@@ -16,11 +16,16 @@ environment), or, when bench.py is started directly with --gpus N and no WORLD_S
 starts N fresh child ranks BEFORE anything touches the GPU and exits with their status.  Windows are independent,
 so ranks share nothing on the data path ("scaling": "weak", windows per GPU fixed).
 
-Beside the contract fields the line carries, all measured outside the timed region of `value`:
+A plain run does what `value` needs and no more: it makes the sequences and the engine, warms up, times the steps, writes
+--dump-outputs and prints the line (the contract fields, `config`, `ingest`).  --full adds the sections below, all measured
+outside the timed region of `value`, on the same inputs and the same engine (--full changes neither); each has a --no-...
+switch of its own:
+  accuracy               GPU windows 0 .. 3 after the timed updates against the CPU oracle and the independent QR optimiser
   roofline               K1 (the Jacobian kernel) from HIP events on the engine's stream, PMC traffic from profiles/
   roofline_solve         the same for K4, the kernel that takes most of a step
   stage_ms               one launch of every hot-path kernel
   with_convergence_exit  the same update with GTSAM's LM termination rule on (windows stop taking trials)
+  incremental_update     the update as one incremental Gauss-Newton update per keyframe, on an engine of its own
   time_sharded_window    ONE 10 000-pose window spread in time over all ranks (BASELINE configs[4])
   single_window          latency of the update for one window (what one vehicle sees)
   degeneracy_k6          the 6x6 degeneracy metrics, f64 / f32, beside the reference's per-matrix numpy calls (N = 1)
@@ -52,6 +57,9 @@ IMU_BYTES_DENSE = 5496
 EXIT_SHARDED_SECTION_HUNG = 75   # the headline line was printed, the time-sharded (collective) section did not finish
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
+# the sections a run without --full leaves out, by the name of the --no-... switch that leaves each out of a --full run
+PLAIN_RUN_SKIPS = ("accuracy", "cpu_baseline", "single_window", "sharded", "convergence_exit", "incremental", "degeneracy",
+                   "graph_manager")
 
 
 def _make_seq(job):
@@ -101,11 +109,12 @@ def updates_per_engine(args):
     return (args.steps + args.warmup) * (1 if args.no_convergence_exit else 2)
 
 
-def make_engine(args, local_rank, windows, seqs, updates, all_resident=False, **engine_opts):
+def make_engine(args, local_rank, windows, seqs, updates, all_resident=False, fed_updates=None, **engine_opts):
     """Synthetic Carla-like factors for `windows` windows.  Only the FIRST window's factors are made resident here (K0 on
     the device, bias estimate 0: GraphManager's bias before the first solve); the factors of the keyframes the updates
     append stay on the host as what a driver receives per keyframe -- raw IMU samples + the between record -- and go in
     through vf_engine_ingest_tail inside the timed step (`feed[u]` = update u's packed arguments for all windows).
+    `updates` sizes the engine; fed_updates (default: all of them) is how many of them the caller will really ingest.
     all_resident (timing probes under tools/ only): every factor preintegrated up front, no feed."""
     from vil_sensor_fusion_amd import Engine, EngineOpts, synth
     from vil_sensor_fusion_amd.engine import REFERENCE_PRIOR_SIGMAS
@@ -139,7 +148,7 @@ def make_engine(args, local_rank, windows, seqs, updates, all_resident=False, **
             d[int(seq.btw_b[i])] = (int(seq.btw_a[i]), recs[si][i])
         by_end.append(d)
     feed, none_rec = [], np.zeros(28)
-    for u in range(updates):
+    for u in range(updates if fed_updates is None else fed_updates):
         k = n + u
         off, steps, a, rec = [0], [], [], []
         for w in range(windows):
@@ -584,6 +593,122 @@ def roofline_k1(eng):
                 "note": "counts the 159 structurally zero Jacobian entries that are no longer written"}}
 
 
+def kernel_figures(args, eng, out, ingest_ms):
+    """--full, rank 0: one launch of every hot-path kernel (`stage_ms`), what the committed trace says of K1 beside its live
+    roofline, and the roofline of the band solve with its matrix-instruction and issue views -- added to the report `out`.
+    ingest_ms: (h2d, K0 + staging) of the last timed ingest."""
+    counts = eng.counts()
+    alg_bytes = counts["imu"] * IMU_BYTES
+    stages = {s: eng.time_stage(s, reps=5) for s in
+              ("linearize_imu", "linearize_between", "assemble", "assemble_idle", "solve", "retract", "decide")}
+    solve_form = eng.solve_form()
+    if solve_form == "assembling":
+        # K3 is not part of this engine's LM trial (the forward sweep of `solve` forms H itself): what the stage timer
+        # launched above is the stand-alone kernel, kept for comparison only
+        stages["assemble_k3_not_in_the_step"] = stages.pop("assemble")
+        stages.pop("assemble_idle")
+        stages["assemble"] = 0.0
+    out["stage_ms"] = dict(stages, h2d=ingest_ms[0], preintegrate_tail=ingest_ms[1])
+    prof = profiled_kernels()
+    if prof is not None and "vf::k_linearize_imu" in prof.get("kernels", {}):
+        # the committed rocprofv3 trace of this same command: the launch duration inside a whole step (other
+        # kernels' traffic still draining), usually a few % above the isolated back-to-back figure
+        pk = prof["kernels"]["vf::k_linearize_imu"]
+        out["roofline"]["profiled"] = {"avg_launch_ms": pk["avg_ms"], "launches": pk["calls"], "source": prof["source"],
+                                       "achieved": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9,
+                                       "frac": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+        # the same as flat keys (a parser that keeps only scalars of `roofline` still carries the committed trace's figure)
+        out["roofline"].update({"profiled_avg_launch_ms": pk["avg_ms"], "profiled_launches": pk["calls"],
+                                "profiled_achieved": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9,
+                                "profiled_frac": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                "profiled_source": prof["source"]})
+        if out["roofline"]["traffic"]:
+            out["roofline"]["traffic_over_algorithmic"] = out["roofline"]["traffic"] / alg_bytes
+    # the kernel that takes most of a step: K4 (banded Cholesky solve), HBM-bound under a full batch.  Algorithmic
+    # bytes per keyframe: the band of H it needs (H[k][k-1]: 225, lower triangle of H[k][k]: 120, two 6x6 strips:
+    # 432 doubles) + g + the panel written by the forward sweep and read back by the backward one (547 doubles
+    # each way: 27 sub-diagonal rows + the rhs row x 15, and the 120 + 7 entries of L^-T its column pairs keep) + the
+    # increment.
+    k4_bytes_per_kf = 8 * (432 + 15 + 547 + 547 + 15)
+    k4_name = "k_band_solve (K4: damped block-banded Cholesky factorisation + both substitutions)"
+    if solve_form == "assembling":
+        # the assembling sweep reads the Jacobians instead of H and g: the J stream (292 doubles per factor: the 291 entries
+        # that are not structurally zero + padding), the residual (15), the between linearisation (78); panel, increment as above
+        k4_bytes_per_kf = 8 * (292 + 15 + 78 + 547 + 547 + 15)
+        from vil_sensor_fusion_amd import _lib as _vl
+        _o = _vl.EngineTuningC()
+        _vl.lib().vf_engine_default_tuning(_vl.C.byref(_o))
+        asm_waves = args.solve_assemble_waves if args.solve_assemble_waves in (1, 2) else (2 if _o.solve_assemble_waves != 1 else 1)
+        k4_name = (("k_band_forward_asm2 (two waves per window: eliminator + assembler on one LDS image)" if asm_waves == 2 else "k_band_forward_asm")
+                   + " + k_band_backward (K3 + K4 in one pass: block rows of J^T J formed on the matrix cores "
+                   "inside the forward sweep, damped block-banded Cholesky factorisation, both substitutions)")
+    n_kf = args.windows * args.window
+    k4_ach = n_kf * k4_bytes_per_kf / (stages["solve"] * 1e-3) / 1e9
+    out["solve_form"] = solve_form
+    out["roofline_solve"] = {"kernel": k4_name,
+                             "bound": "hbm", "achieved": k4_ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": k4_ach / HBM_PEAK_GBPS, "avg_launch_ms": stages["solve"],
+                             "algorithmic_bytes_per_keyframe": k4_bytes_per_kf,
+                             "irreducible_io_bytes_per_keyframe": 8 * (432 + 15 + 15),
+                             "algorithmic_bytes_per_launch": n_kf * k4_bytes_per_kf,
+                             "frac_of_measured_copy_peak_6290": k4_ach / 6290.0,
+                             "note": "8.8 of the 12.4 KB per keyframe are the Cholesky panel written by the forward sweep and "
+                                     "read back by the backward one; against H + g + delta alone (3.7 KB) the kernel moves 3.4x",
+                             "what_bounds_it": "not HBM: the per-window dependency chain at one wave per SIMD.  SQ counters "
+                                               "(profiles/*_sq_counters.md): the wave issues vector instructions 33 % and LDS "
+                                               "instructions 16 % of its cycles, is stalled on a dependent result 31 % and in "
+                                               "s_waitcnt 15 %; matrix pipes 11 % busy (DESIGN.md 7.9).  The HBM fraction is "
+                                               "quoted because it is what the kernel's traffic amounts to, not as its roofline",
+                             "traffic_note": "profiles/*_pmc_summary.md: k_band_solve read 2*FETCH_SIZE + WRITE_SIZE per launch"}
+    if solve_form == "assembling":
+        out["roofline_solve"]["irreducible_io_bytes_per_keyframe"] = 8 * (292 + 15 + 78 + 15)
+        out["roofline_solve"]["note"] = ("8.8 of the 12.0 KB per keyframe are the Cholesky panel written by the forward sweep and read "
+                                         "back by the backward one; the rest is the Jacobians K1 / K2 wrote (H is never stored)")
+        out["roofline_solve"]["what_bounds_it"] = (
+            "not HBM: the float64 units of a SIMD.  One window-step is the pivot chain of the 15 x 15 block (vector instructions "
+            "at 7 cycles each) plus 26 v_mfma_f64_16x16x4 (12 of the Schur update, 14 that form the row of J^T J); a single wave "
+            "gets one matrix instruction through every ~143 cycles, its vector instructions do not run under it, and the part's "
+            "float64 matrix rate saturates at 47 TFLOP/s (tools/probes/mfma_f64_rate.hip); as two waves per window sharing the "
+            "window's LDS the two jobs overlap each other's waits.  DESIGN.md 7.13, 7.15")
+        out["roofline_solve"]["waves_per_window"] = asm_waves
+        mfma_flop = 26 * 2048.0 * n_kf           # per launch of the forward sweep: 12 (Schur update) + 14 (rows of J^T J) tiles per keyframe
+        out["roofline_solve"]["matrix_instruction_view"] = {
+            "bound": "mfma", "unit": "TFLOP/s", "flop_per_launch": mfma_flop,
+            "achieved": mfma_flop / (stages["solve"] * 1e-3) / 1e12,
+            "peak_measured_one_wave_per_simd": 34.7, "peak_measured_two_waves_per_simd": 45.8, "peak_measured_saturated": 47.3,
+            "peak_data_sheet_f64_matrix": 78.6,
+            "frac_of_measured_peak_at_this_occupancy": mfma_flop / (stages["solve"] * 1e-3) / 1e12 / (45.8 if asm_waves == 2 else 34.7),
+            "note": "the time is that of forward sweep + back substitution (the stage timer's `solve`); the back substitution "
+                    "(0.92 ms of it) issues no matrix instruction; peaks measured by tools/probes/mfma_f64_rate.hip "
+                    "(profiles/r04_mfma_f64_rate.log)"}
+    # The issue view (VERDICT r4 next-5): the forward sweep is bound by what one SIMD can ISSUE in float64, not by HBM.  From
+    # the committed counter passes of this same command (profiles/*_sq_counters.md -> kernel_durations.json): every wave64
+    # vector instruction occupies the SIMD's 16 lanes for 4 cycles (float64 FMA at full rate: 78.6 TFLOP/s = 16 lanes x 2 x
+    # 1024 SIMDs x 2.4 GHz), a v_mfma_f64_16x16x4 (2048 flop) the matrix pipe for 64 cycles at the data-sheet rate and 106
+    # at the rate this part saturates at (47.3 TFLOP/s, tools/probes/mfma_f64_rate.hip); a SIMD has launch x 2.4e9 cycles.
+    fwd_key = next((k for k in ("vf::k_band_forward_asm2", "vf::k_band_forward_asm", "vf::k_band_solve") if prof and k in prof.get("kernels", {})), None)
+    if fwd_key and "sq" in prof["kernels"][fwd_key] and "valu_insts_per_launch" in prof["kernels"][fwd_key]["sq"]:
+        pk, sqc = prof["kernels"][fwd_key], prof["kernels"][fwd_key]["sq"]
+        simd_cycles = pk["full_avg_ms"] * 1e-3 * 2.4e9 * 1024 / n_kf
+        valu_c = (sqc["valu_insts_per_launch"] - sqc["mfma_f64_insts_per_launch"]) * 4.0 / n_kf
+        f64_c = sqc["valu_f64_insts_per_launch"] * 4.0 / n_kf
+        mf = sqc["mfma_f64_insts_per_launch"] / n_kf
+        out["roofline_solve"]["issue_view"] = {
+            "kernel": fwd_key, "bound": "float64 issue of a SIMD (vector unit + matrix pipe)", "unit": "SIMD cycles per keyframe",
+            "available": simd_cycles, "vector_instructions_issue": valu_c, "of_which_float64": f64_c,
+            "matrix_instructions_per_keyframe": mf, "matrix_pipe_at_data_sheet_rate": mf * 64.0, "matrix_pipe_at_measured_saturation": mf * 2048.0 / (47.3e12 / 1024 / 2.4e9),
+            "matrix_pipe_busy_measured": sqc["mfma_busy_cycles_per_launch"] / n_kf,
+            "frac_issue_serial": (valu_c + mf * 2048.0 / (47.3e12 / 1024 / 2.4e9)) / simd_cycles,
+            "frac_issue_overlapped": max(valu_c, mf * 2048.0 / (47.3e12 / 1024 / 2.4e9)) / simd_cycles,
+            "note": "frac_issue_serial: vector and matrix work of a SIMD one after the other (what ONE wave per SIMD can do: its "
+                    "vector instructions do not issue under its own matrix instruction); frac_issue_overlapped: both units busy "
+                    "at once (two waves per SIMD, perfectly interleaved).  The kernel sits between the two; the rest is the pivot "
+                    "chain's dependent-result latency (wait / issue-stall columns of the counter table)",
+            "source": prof["source"]}
+    if prof is not None:
+        out["profiled_kernels"] = prof
+
+
 LINE_LIMIT = 4096        # the driver keeps the tail of stdout: the ONE JSON line must fit well inside it
 
 
@@ -755,6 +880,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed (rank 0's windows) as DIR/<name>.npy, float64, at "
                          "most 64 MB: every window's LM summary and the states of a seeded sample of the windows")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (accuracy against the CPU oracle, CPU "
+                         "baselines, rooflines and per-kernel times, the convergence-exit and incremental updates, the "
+                         "time-sharded window, one-window latency, K6, GraphManager); without it every --no-... switch is moot")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -780,12 +909,17 @@ def main():
     if world_env > 1:
         args.no_cpu_baseline = True      # the CPU legs are timed at N = 1 only; at N > 1 just the updates the accuracy figure needs
     seq_len = args.window + max(updates, 0 if (args.no_cpu_baseline or args.no_accuracy) else args.cpu_steps) + 1
+    if not args.full:
+        # the sizes above are those of the --full run with the same arguments, so both runs time the same engine on the same
+        # sequences; a plain run then skips every section beside the headline
+        for section in PLAIN_RUN_SKIPS:
+            setattr(args, "no_" + section, True)
     if rank_env == 0 and not args.no_accuracy:
         cpu_one, cpu_all, reference = cpu_baseline(args, seq_len)
     nseq = args.sequences if args.sequences > 0 else args.windows
     seqs = make_sequences(args, rank_env, max(1, min(nseq, args.windows)), seq_len)
     one_updates = 7
-    one_seq = make_sequences(args, rank_env, 1, args.window + one_updates + 1, base_seed=7777)
+    one_seq = None if args.no_single_window else make_sequences(args, rank_env, 1, args.window + one_updates + 1, base_seed=7777)
 
     import torch
     from vil_sensor_fusion_amd import distributed as D
@@ -802,6 +936,7 @@ def main():
     dev = torch.device("cuda", gpu)
 
     eng, feed = make_engine(args, gpu, args.windows, seqs, updates,
+                            fed_updates=(args.steps + args.warmup) * (1 if args.no_convergence_exit else 2),
                             **({} if args.solve_assemble_min is None else {"solve_assemble_min": args.solve_assemble_min}),
                             **({} if args.solve_assemble_waves is None else {"solve_assemble_waves": args.solve_assemble_waves}))
     fed = {id(eng): 0}
@@ -903,7 +1038,7 @@ def main():
 
     # K1's roofline is measured before the one section that holds collectives, so that the fallback line of a stalled
     # multi-rank run carries it too
-    roofline = roofline_k1(eng) if info.rank == 0 else None
+    roofline = roofline_k1(eng) if (args.full and info.rank == 0) else None
 
     sharded = None
     if not args.no_sharded and 96 % info.world == 0:
@@ -947,19 +1082,6 @@ def main():
     if info.rank == 0:
         counts = eng.counts()
         kf_per_s = D.whole_job_throughput(summaries, dt)
-        # roofline of the Jacobian-evaluation kernel K1, measured live with HIP events on the
-        # engine's own stream: algorithmic bytes of one launch / average launch duration
-        alg_bytes = counts["imu"] * IMU_BYTES
-        stages = {s: eng.time_stage(s, reps=5) for s in
-                  ("linearize_imu", "linearize_between", "assemble", "assemble_idle", "solve", "retract", "decide")}
-        solve_form = eng.solve_form()
-        if solve_form == "assembling":
-            # K3 is not part of this engine's LM trial (the forward sweep of `solve` forms H itself): what the stage timer
-            # launched above is the stand-alone kernel, kept for comparison only
-            stages["assemble_k3_not_in_the_step"] = stages.pop("assemble")
-            stages.pop("assemble_idle")
-            stages["assemble"] = 0.0
-        prof = profiled_kernels()
         out = {
             "metric": "keyframes/sec fixed-lag update, 1k-pose window; ATE vs GTSAM ref",
             "value": kf_per_s, "unit": "keyframes/s", "n_gpus": info.world, "steps": args.steps,
@@ -975,7 +1097,6 @@ def main():
                        "parallelism": f"independent windows sharded over {info.world} rank(s), no data-path collective"},
             # (short objects first: a reader of the line's head sees the result, its accuracy and where the step's time goes)
             "accuracy": accuracy,
-            "stage_ms": dict(stages, h2d=ingest_ms[0], preintegrate_tail=ingest_ms[1]),
             "roofline": roofline,
             "ingest": {"in_timed_step": True,
                        "what": "per update and window: the new keyframe's raw IMU samples (7 doubles each) + its 28-double between "
@@ -985,103 +1106,8 @@ def main():
                        "bytes_per_update": int(feed[0][1].nbytes + feed[0][4].nbytes + feed[0][0].nbytes + feed[0][3].nbytes)},
             "lm_state_window0": lm_after_timed,
         }
-        if prof is not None and "vf::k_linearize_imu" in prof.get("kernels", {}):
-            # the committed rocprofv3 trace of this same command: the launch duration inside a whole step (other
-            # kernels' traffic still draining), usually a few % above the isolated back-to-back figure
-            pk = prof["kernels"]["vf::k_linearize_imu"]
-            out["roofline"]["profiled"] = {"avg_launch_ms": pk["avg_ms"], "launches": pk["calls"], "source": prof["source"],
-                                           "achieved": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9,
-                                           "frac": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
-            # the same as flat keys (a parser that keeps only scalars of `roofline` still carries the committed trace's figure)
-            out["roofline"].update({"profiled_avg_launch_ms": pk["avg_ms"], "profiled_launches": pk["calls"],
-                                    "profiled_achieved": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9,
-                                    "profiled_frac": alg_bytes / (pk["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                    "profiled_source": prof["source"]})
-            if out["roofline"]["traffic"]:
-                out["roofline"]["traffic_over_algorithmic"] = out["roofline"]["traffic"] / alg_bytes
-        # the kernel that takes most of a step: K4 (banded Cholesky solve), HBM-bound under a full batch.  Algorithmic
-        # bytes per keyframe: the band of H it needs (H[k][k-1]: 225, lower triangle of H[k][k]: 120, two 6x6 strips:
-        # 432 doubles) + g + the panel written by the forward sweep and read back by the backward one (547 doubles
-        # each way: 27 sub-diagonal rows + the rhs row x 15, and the 120 + 7 entries of L^-T its column pairs keep) + the
-        # increment.
-        k4_bytes_per_kf = 8 * (432 + 15 + 547 + 547 + 15)
-        k4_name = "k_band_solve (K4: damped block-banded Cholesky factorisation + both substitutions)"
-        if solve_form == "assembling":
-            # the assembling sweep reads the Jacobians instead of H and g: the J stream (292 doubles per factor: the 291 entries
-            # that are not structurally zero + padding), the residual (15), the between linearisation (78); panel, increment as above
-            k4_bytes_per_kf = 8 * (292 + 15 + 78 + 547 + 547 + 15)
-            from vil_sensor_fusion_amd import _lib as _vl
-            _o = _vl.EngineTuningC()
-            _vl.lib().vf_engine_default_tuning(_vl.C.byref(_o))
-            asm_waves = args.solve_assemble_waves if args.solve_assemble_waves in (1, 2) else (2 if _o.solve_assemble_waves != 1 else 1)
-            k4_name = (("k_band_forward_asm2 (two waves per window: eliminator + assembler on one LDS image)" if asm_waves == 2 else "k_band_forward_asm")
-                       + " + k_band_backward (K3 + K4 in one pass: block rows of J^T J formed on the matrix cores "
-                       "inside the forward sweep, damped block-banded Cholesky factorisation, both substitutions)")
-        n_kf = args.windows * args.window
-        k4_ach = n_kf * k4_bytes_per_kf / (stages["solve"] * 1e-3) / 1e9
-        out["solve_form"] = solve_form
-        out["roofline_solve"] = {"kernel": k4_name,
-                                 "bound": "hbm", "achieved": k4_ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                 "frac": k4_ach / HBM_PEAK_GBPS, "avg_launch_ms": stages["solve"],
-                                 "algorithmic_bytes_per_keyframe": k4_bytes_per_kf,
-                                 "irreducible_io_bytes_per_keyframe": 8 * (432 + 15 + 15),
-                                 "algorithmic_bytes_per_launch": n_kf * k4_bytes_per_kf,
-                                 "frac_of_measured_copy_peak_6290": k4_ach / 6290.0,
-                                 "note": "8.8 of the 12.4 KB per keyframe are the Cholesky panel written by the forward sweep and "
-                                         "read back by the backward one; against H + g + delta alone (3.7 KB) the kernel moves 3.4x",
-                                 "what_bounds_it": "not HBM: the per-window dependency chain at one wave per SIMD.  SQ counters "
-                                                   "(profiles/*_sq_counters.md): the wave issues vector instructions 33 % and LDS "
-                                                   "instructions 16 % of its cycles, is stalled on a dependent result 31 % and in "
-                                                   "s_waitcnt 15 %; matrix pipes 11 % busy (DESIGN.md 7.9).  The HBM fraction is "
-                                                   "quoted because it is what the kernel's traffic amounts to, not as its roofline",
-                                 "traffic_note": "profiles/*_pmc_summary.md: k_band_solve read 2*FETCH_SIZE + WRITE_SIZE per launch"}
-        if solve_form == "assembling":
-            out["roofline_solve"]["irreducible_io_bytes_per_keyframe"] = 8 * (292 + 15 + 78 + 15)
-            out["roofline_solve"]["note"] = ("8.8 of the 12.0 KB per keyframe are the Cholesky panel written by the forward sweep and read "
-                                             "back by the backward one; the rest is the Jacobians K1 / K2 wrote (H is never stored)")
-            out["roofline_solve"]["what_bounds_it"] = (
-                "not HBM: the float64 units of a SIMD.  One window-step is the pivot chain of the 15 x 15 block (vector instructions "
-                "at 7 cycles each) plus 26 v_mfma_f64_16x16x4 (12 of the Schur update, 14 that form the row of J^T J); a single wave "
-                "gets one matrix instruction through every ~143 cycles, its vector instructions do not run under it, and the part's "
-                "float64 matrix rate saturates at 47 TFLOP/s (tools/probes/mfma_f64_rate.hip); as two waves per window sharing the "
-                "window's LDS the two jobs overlap each other's waits.  DESIGN.md 7.13, 7.15")
-            out["roofline_solve"]["waves_per_window"] = asm_waves
-            mfma_flop = 26 * 2048.0 * n_kf           # per launch of the forward sweep: 12 (Schur update) + 14 (rows of J^T J) tiles per keyframe
-            out["roofline_solve"]["matrix_instruction_view"] = {
-                "bound": "mfma", "unit": "TFLOP/s", "flop_per_launch": mfma_flop,
-                "achieved": mfma_flop / (stages["solve"] * 1e-3) / 1e12,
-                "peak_measured_one_wave_per_simd": 34.7, "peak_measured_two_waves_per_simd": 45.8, "peak_measured_saturated": 47.3,
-                "peak_data_sheet_f64_matrix": 78.6,
-                "frac_of_measured_peak_at_this_occupancy": mfma_flop / (stages["solve"] * 1e-3) / 1e12 / (45.8 if asm_waves == 2 else 34.7),
-                "note": "the time is that of forward sweep + back substitution (the stage timer's `solve`); the back substitution "
-                        "(0.92 ms of it) issues no matrix instruction; peaks measured by tools/probes/mfma_f64_rate.hip "
-                        "(profiles/r04_mfma_f64_rate.log)"}
-        # The issue view: the forward sweep is bound by what one SIMD can ISSUE in float64, not by HBM.  From
-        # the committed counter passes of this same command (profiles/*_sq_counters.md -> kernel_durations.json): every wave64
-        # vector instruction occupies the SIMD's 16 lanes for 4 cycles (float64 FMA at full rate: 78.6 TFLOP/s = 16 lanes x 2 x
-        # 1024 SIMDs x 2.4 GHz), a v_mfma_f64_16x16x4 (2048 flop) the matrix pipe for 64 cycles at the data-sheet rate and 106
-        # at the rate this part saturates at (47.3 TFLOP/s, tools/probes/mfma_f64_rate.hip); a SIMD has launch x 2.4e9 cycles.
-        fwd_key = next((k for k in ("vf::k_band_forward_asm2", "vf::k_band_forward_asm", "vf::k_band_solve") if prof and k in prof.get("kernels", {})), None)
-        if fwd_key and "sq" in prof["kernels"][fwd_key] and "valu_insts_per_launch" in prof["kernels"][fwd_key]["sq"]:
-            pk, sqc = prof["kernels"][fwd_key], prof["kernels"][fwd_key]["sq"]
-            simd_cycles = pk["full_avg_ms"] * 1e-3 * 2.4e9 * 1024 / n_kf
-            valu_c = (sqc["valu_insts_per_launch"] - sqc["mfma_f64_insts_per_launch"]) * 4.0 / n_kf
-            f64_c = sqc["valu_f64_insts_per_launch"] * 4.0 / n_kf
-            mf = sqc["mfma_f64_insts_per_launch"] / n_kf
-            out["roofline_solve"]["issue_view"] = {
-                "kernel": fwd_key, "bound": "float64 issue of a SIMD (vector unit + matrix pipe)", "unit": "SIMD cycles per keyframe",
-                "available": simd_cycles, "vector_instructions_issue": valu_c, "of_which_float64": f64_c,
-                "matrix_instructions_per_keyframe": mf, "matrix_pipe_at_data_sheet_rate": mf * 64.0, "matrix_pipe_at_measured_saturation": mf * 2048.0 / (47.3e12 / 1024 / 2.4e9),
-                "matrix_pipe_busy_measured": sqc["mfma_busy_cycles_per_launch"] / n_kf,
-                "frac_issue_serial": (valu_c + mf * 2048.0 / (47.3e12 / 1024 / 2.4e9)) / simd_cycles,
-                "frac_issue_overlapped": max(valu_c, mf * 2048.0 / (47.3e12 / 1024 / 2.4e9)) / simd_cycles,
-                "note": "frac_issue_serial: vector and matrix work of a SIMD one after the other (what ONE wave per SIMD can do: its "
-                        "vector instructions do not issue under its own matrix instruction); frac_issue_overlapped: both units busy "
-                        "at once (two waves per SIMD, perfectly interleaved).  The kernel sits between the two; the rest is the pivot "
-                        "chain's dependent-result latency (wait / issue-stall columns of the counter table)",
-                "source": prof["source"]}
-        if prof is not None:
-            out["profiled_kernels"] = prof
+        if args.full:
+            kernel_figures(args, eng, out, ingest_ms)
         if conv is not None:
             out["with_convergence_exit"] = conv
         if incr is not None:

@@ -128,3 +128,17 @@ def test_dumped_outputs_fit_the_budget_and_are_the_same_sample_every_time(tmp_pa
     np.testing.assert_array_equal(lm[:, 0], 0.5 * np.arange(windows))
     np.testing.assert_array_equal(states[:, 0, 0], 100.0 * idx + 12)
     np.testing.assert_array_equal(idx, bench.dump_sample(windows, n))
+
+
+def test_every_section_a_plain_run_skips_has_its_switch():
+    """A run without --full sets the --no-... switch of every extra section: each name must be a real option (a misspelt one
+    would be set and never read, and the section would run)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "--full" in res.stdout
+    for section in bench.PLAIN_RUN_SKIPS:
+        assert "--no-" + section.replace("_", "-") in res.stdout, section
+    assert {"accuracy", "cpu_baseline", "convergence_exit", "incremental", "sharded", "single_window", "degeneracy",
+            "graph_manager"} <= set(bench.PLAIN_RUN_SKIPS)

@@ -160,7 +160,7 @@ def test_bench_gpus_flag_starts_that_many_ranks(tmp_path):
     env = dict(os.environ, VF_BENCH_BACKEND="gloo", VF_BENCH_SHARE_GPU="1", VF_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--windows", "8", "--window", "96", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--windows", "8", "--window", "96", "--steps", "2",
            "--warmup", "1", "--sharded-window", "1200", "--no-single-window"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -184,7 +184,7 @@ def test_bench_abandons_a_stalled_sharded_section():
     env = dict(os.environ, VF_BENCH_BACKEND="gloo", VF_BENCH_SHARE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--windows", "8", "--window", "96", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--windows", "8", "--window", "96", "--steps", "2",
            "--warmup", "1", "--sharded-window", "1200", "--no-single-window", "--sharded-timeout", "0"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 75, (res.returncode, res.stderr[-2000:])

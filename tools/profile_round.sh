@@ -24,7 +24,7 @@ echo "sq_b done" >> $OUT/progress.txt
 rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_BUSY_CU_CYCLES --output-format csv -d $OUT/sq_c -o c -- python3 $R/bench.py $PMCRUN > /dev/null 2> $OUT/sq_c.err
 echo "sq_c done" >> $OUT/progress.txt
 cd $R
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench done" >> $OUT/progress.txt
 # summarise on the box (the per-dispatch counter CSVs of six passes exceed what gpurun carries back), keep the summaries, the
 # rocprofv3 --stats CSV and the bench lines
