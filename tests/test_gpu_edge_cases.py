@@ -3,7 +3,7 @@ flags, determinism), each against the oracle on the same inputs."""
 import numpy as np
 import pytest
 
-from tests import helpers
+from tests import helpers, marg_cases, mp_marg
 from vil_sensor_fusion_amd import synth
 from vil_sensor_fusion_amd.engine import REFERENCE_PRIOR_SIGMAS
 
@@ -188,7 +188,15 @@ def test_marginal_prior_and_fixed_lag_slides_match_oracle(oracle, N, S, chunks):
     win.lm(iterations=4)
     states[:N] = win.states
     marg = None
+    got = None
     for s in range(1, S + 1):
+        if s <= 3:
+            # the first slides: L and eta entry by entry against the extended-precision reference of the device's own
+            # linearisation, within the bound derived in tests/mp_marg.py (1e-9 of the largest entry would let every pose and
+            # velocity entry be wrong in its leading digit beside the 1e14 of the bias prior)
+            spans = [int(b - a) for a, b in zip(prob["btw_a"], prob["btw_b"]) if a == s - 1 and b < N + s - 1]
+            case = marg_cases.device_case(eng, 0, s - 1, f"slide {s}", spans, prob["prior"] if s == 1 else None,
+                                          None if s == 1 else dict(L=got["L"], eta=got["eta"], xbar=got["xbar"]), N)
         eng.slide(REFERENCE_PRIOR_SIGMAS, marginalize=True)
         got = eng.read_marginal(0)
         prev = _oracle_window(oracle, prob, states, s - 1, N + s - 1, marg, s == 1)
@@ -196,7 +204,13 @@ def test_marginal_prior_and_fixed_lag_slides_match_oracle(oracle, N, S, chunks):
         exp = marg.arrays()
         assert got["on"] == 1
         scale = np.abs(exp["L"]).max()
-        np.testing.assert_allclose(got["L"], exp["L"], atol=1e-9 * scale)
+        if s <= 3:
+            ref = mp_marg.reference(case)
+            lift, ext, _, _ = mp_marg.floor_lift(ref, mp_marg.gauge_basis(case.states[1:4], case.gravity), oracle.prior_gauge_floor(N))
+            rl, re_ = mp_marg.check(case.name, got["L"], got["eta"], ref, what="device ", lift=lift, ext=ext)
+            assert rl <= 1.0 and re_ <= 1.0, (s, rl, re_)
+        else:
+            np.testing.assert_allclose(got["L"], exp["L"], atol=1e-9 * scale)
         if s <= 5:
             # eta = information x (state differences): once the two LM trajectories have drifted apart by 1e-10 m
             # (later slides of the long runs) it can only be compared through the trajectories themselves
