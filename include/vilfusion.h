@@ -491,6 +491,17 @@ int vf_engine_marginals(vf_engine* e);
  * the first such call and kept; it is bounded by 1 GiB: more windows than fit are done in groups.  Unknown
  * flags: VF_ERR_INVALID. */
 #define VF_MARGINALS_FAR 1u
+/* VF_MARGINALS_POSE (may be combined with VF_MARGINALS_FAR): behind the selected inversion, and the far downdate where there is
+ * one, the same call leaves three more device arrays for every keyframe of every window's range -- what the degeneracy metrics
+ * take (vf_engine_marginal_scores), allocated by the first call that carries the flag (624 B per keyframe slot):
+ *   cov36   the pose covariance in nav_msgs/Odometry order (x, y, z, rx, ry, rz), row-major: A Sigma_pp A^T with Sigma_pp the
+ *           leading 6 x 6 of the keyframe's block, A = diag(R, R) P, P the swap [omega, v] -> [v, omega] and R the rotation of the
+ *           state this very call linearised at (the states may move on afterwards while the covariances stay readable);
+ *   info36  its inverse, by a 6 x 6 Cholesky factorisation (NaN throughout where a pivot is not positive);
+ *   pose6   (x, y, z, roll, pitch, yaw) of that state, angles in the static x-y-z convention of tf.transformations.euler_from_quaternion.
+ * cov36 and info36 are symmetric to the bit.  A window whose factorisation failed holds NaN in all three.  Without the flag the
+ * call launches what it always launched, gives the same bits and allocates nothing more. */
+#define VF_MARGINALS_POSE 2u
 int vf_engine_marginals_ex(vf_engine* e, unsigned flags);
 /* ... read back (synchronises): for keyframes k0 .. k0+n-1 of the range the last vf_engine_marginals saw, Sigma_kk (full
  * symmetric 15x15, row-major) and the cross block Sigma_{k+1,k} (15x15, row = dof of k+1, column = dof of k; zero for the window's
@@ -498,6 +509,24 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags);
  * the window's undamped normal equations are not positive definite; VF_ERR_INVALID: no vf_engine_marginals since the engine was
  * made or compacted; VF_ERR_BAD_KEY: outside that range. */
 int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* cov225, double* cross225);
+/* ... and the records of VF_MARGINALS_POSE (synchronises): n x 36, n x 36 and n x 6 doubles; any pointer may be NULL.  Refusals as
+ * vf_engine_read_marginals; VF_ERR_INVALID also when the last vf_engine_marginals_ex did not carry VF_MARGINALS_POSE. */
+int vf_engine_read_pose_marginals(vf_engine* e, int window, int k0, int n, double* cov36, double* info36, double* pose6);
+/* Degeneracy scores of those records, on the device (K6 over windows; the reference's online node per message:
+ * vil_fusion/src/vil_fusion/degeneracy_detection.py:82-130).  Enqueues one launch over every window: `metric` (VF_METRIC_*) on the
+ * subsets of subset_mask (as vf_degeneracy_scores_batch), of the pose covariances (VF_SCORE_COVARIANCE) or their inverses
+ * (VF_SCORE_INFORMATION).  Each window's range is a time series of its own: the score of its first keyframe is 0 and no keyframe is
+ * compared with one of another window.  The values are bit for bit what vf_degeneracy_scores_batch returns for the window's
+ * records (vf_engine_read_pose_marginals) alone; kullback_leibler takes its poses from pose6.  The scores live in a device array
+ * sized for the rows asked for and grown on demand.  VF_ERR_INVALID: unknown source, metric or mask; no pose marginals (none
+ * computed, or the engine was compacted since). */
+#define VF_SCORE_COVARIANCE 0
+#define VF_SCORE_INFORMATION 1
+int vf_engine_marginal_scores(vf_engine* e, int source, int metric, unsigned subset_mask);
+/* ... read back (synchronises): popcount(subset_mask) rows of n values, in ascending subset id, of the last
+ * vf_engine_marginal_scores (its metric and mask), for keyframes k0 .. k0+n-1.  VF_ERR_INVALID: no scores since the last
+ * vf_engine_marginals_ex; VF_ERR_BAD_KEY: outside the range the marginals were computed for; VF_ERR_NOT_SPD: a failed window. */
+int vf_engine_read_marginal_scores(vf_engine* e, int window, int k0, int n, double* out);
 int vf_engine_read_lm(vf_engine* e, int window, double* cost, double* lambda, int* accepted,
                       int* rejected, int* solve_failures);
 /* non-monotone LM: trials kept provisionally so far (not counted in accepted / rejected), and whether an excursion is open */
@@ -692,6 +721,12 @@ int vf_set_callback(vf_graph* g, vf_callback cb, void* user);
  * VF_ERR_BAD_KEY for a key not solved yet or marginalised out of the window.  Takes the state lock like vf_get_state: never call it
  * from inside a callback. */
 int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
+/* Degeneracy scores of the fused estimate itself: `metric` on the subsets of subset_mask of the nav_msgs pose covariance
+ * (VF_SCORE_COVARIANCE) or information (VF_SCORE_INFORMATION) of keys key0 .. key0+n-1, the window as one time series (the score of
+ * its oldest key is 0).  out: popcount(subset_mask) rows of n values, in ascending subset id.  If the last solve has no covariances
+ * yet they are computed with VF_MARGINALS_POSE (and VF_MARGINALS_FAR under vf_graph_opts.far_covariance), then the scores
+ * (vf_engine_marginal_scores); vf_solve and vf_set_initial_state void them.  Refusals and lock rule as vf_get_marginal_covariance. */
+int vf_get_degeneracy_scores(vf_graph* g, int source, int metric, unsigned subset_mask, uint64_t key0, int n, double* out);
 /* the callback of vf_set_callback plus the marginal covariance of the solved keyframe */
 typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
                                 const double bias[6], const double cov225[225]);

@@ -267,6 +267,8 @@ void vf_engine_destroy(vf_engine* e) {
     if (e->x_Z) (void)hipFree(e->x_Z);
     if (e->sig) (void)hipFree(e->sig);
     if (e->fc_scratch) (void)hipFree(e->fc_scratch);
+    if (e->pm_cov) (void)hipFree(e->pm_cov);
+    if (e->sc) (void)hipFree(e->sc);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream && e->own_stream) (void)hipStreamDestroy(e->stream);

@@ -19,8 +19,8 @@ constexpr size_t FARCOV_BUDGET = (size_t)1 << 30;
 int vf_engine_marginals(vf_engine* e) { return vf_engine_marginals_ex(e, 0); }
 int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
-    if (flags & ~(unsigned)VF_MARGINALS_FAR) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
-    const bool far = (flags & VF_MARGINALS_FAR) != 0;
+    if (flags & ~(unsigned)(VF_MARGINALS_FAR | VF_MARGINALS_POSE)) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
+    const bool far = (flags & VF_MARGINALS_FAR) != 0, pose = (flags & VF_MARGINALS_POSE) != 0;
     Entry entry_(e, Entry::reads, Entry::leaves_result);      // (nothing here touches the result block of the last solve)
     if (int rc = not_sharded(e, "vf_engine_marginals")) return rc;
     e->recount_far();
@@ -56,6 +56,17 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
         HIPCHK(hipMemsetAsync(e->sig_zero, 0, B * sizeof(double), e->stream));
         HIPCHK(hipMemcpyAsync(e->sig_ones, ones.data(), B * sizeof(int), hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    if (pose && (!e->pm_cov || e->pm_G != e->v.G)) {
+        // allocated on first use as sig is (G x 624 B): only engines that ask for the nav_msgs records hold them
+        if (e->pm_cov) { HIPCHK(hipStreamSynchronize(e->stream)); (void)hipFree(e->pm_cov); e->pm_cov = nullptr; }
+        void* q = nullptr;
+        HIPCHK(hipMalloc(&q, G * (36 + 36 + 6) * sizeof(double) + 2 * B * sizeof(int) + 256));
+        e->pm_cov = (double*)q;
+        e->pm_info = e->pm_cov + G * 36;
+        e->pm_pose = e->pm_info + G * 36;
+        e->pm_range = (int*)(e->pm_pose + G * 6);
+        e->pm_G = e->v.G;
     }
     e->mem.rewritten();      // (inherited order: a refused call leaves the engine as it was)
     vf::View a = e->v;
@@ -93,6 +104,10 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
         fc.cwin = cwin;
         vf::launch_farcov(a, fc, std::min(group, e->v.B - w0), e->sig, e->stream);
     }
+    // the nav_msgs records of every keyframe, of the states this call linearised at (they may move before anyone reads)
+    if (pose) vf::launch_pose_marginals(a, e->sig_fail, e->sig, e->pm_cov, e->pm_info, e->pm_pose, e->pm_range, e->stream);
+    e->pm_on = pose;
+    e->sc_rows_used = 0;
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;
     e->sig_hi = e->h_hi;
@@ -122,5 +137,73 @@ int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* co
                 for (int c = 0; c < 15; c++) cov225[(size_t)k * 225 + a * 15 + c] = r[a >= c ? vf::h_tri(a, c) : vf::h_tri(c, a)];
         if (cross225) memcpy(cross225 + (size_t)k * 225, r + 120, 225 * sizeof(double));
     }
+    return VF_OK;
+}
+
+// the records VF_MARGINALS_POSE leaves: the refusals of vf_engine_read_marginals + the flag
+static int check_pose_marginals(vf_engine* e, int window, int k0, int n, const char* what) {
+    int rc = check_window(e, window);
+    if (rc) return rc;
+    if (!e->mem.covariances_valid() || e->sig_G != e->v.G) return fail(VF_ERR_INVALID, "no marginal covariances: call vf_engine_marginals_ex first");
+    if (!e->pose_marginals_valid()) return fail(VF_ERR_INVALID, "%s: the last vf_engine_marginals_ex did not carry VF_MARGINALS_POSE", what);
+    if (n < 0 || k0 < e->sig_lo[window] || k0 + n > e->sig_hi[window])
+        return fail(VF_ERR_BAD_KEY, "keyframes [%d,%d) outside the range [%d,%d) the covariances were computed for", k0, k0 + n,
+                    e->sig_lo[window], e->sig_hi[window]);
+    int failed = 0;
+    HIPCHK(hipMemcpyAsync(&failed, e->sig_fail + window, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (failed) return fail(VF_ERR_NOT_SPD, "window %d: the undamped normal equations are not positive definite", window);
+    return VF_OK;
+}
+
+int vf_engine_read_pose_marginals(vf_engine* e, int window, int k0, int n, double* cov36, double* info36, double* pose6) {
+    Entry entry_(e, Entry::reads);
+    if (int rc = check_pose_marginals(e, window, k0, n, "vf_engine_read_pose_marginals")) return rc;
+    if (n == 0) return VF_OK;
+    const size_t g = (size_t)window * e->v.M + k0;
+    if (cov36) HIPCHK(hipMemcpy(cov36, e->pm_cov + g * 36, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+    if (info36) HIPCHK(hipMemcpy(info36, e->pm_info + g * 36, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+    if (pose6) HIPCHK(hipMemcpy(pose6, e->pm_pose + g * 6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    return VF_OK;
+}
+
+// K6 on those records, every window's range a series of its own (vf_degeneracy.hip, k_degeneracy_scores_windows).  Enqueues.
+int vf_engine_marginal_scores(vf_engine* e, int source, int metric, unsigned subset_mask) {
+    VF_ENTER(e, Entry::reads, Entry::leaves_result);
+    if (source != VF_SCORE_COVARIANCE && source != VF_SCORE_INFORMATION)
+        return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: source must be VF_SCORE_COVARIANCE or VF_SCORE_INFORMATION");
+    if (metric < 0 || metric >= vf::K6_METRICS) return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: unknown metric %d", metric);
+    if (subset_mask == 0 || (subset_mask >> vf::K6_SUBSETS) != 0)
+        return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: subset_mask 0x%x: bits 0 .. 8, at least one", subset_mask);
+    if (!e->pose_marginals_valid())
+        return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: no pose marginals (vf_engine_marginals_ex with VF_MARGINALS_POSE; a compaction voids them)");
+    const int rows = __builtin_popcount(subset_mask);
+    if (rows > e->sc_rows || e->sc_G != e->v.G) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (e->sc) { (void)hipFree(e->sc); e->sc = nullptr; e->sc_rows = 0; }
+        HIPCHK(hipMalloc((void**)&e->sc, (size_t)rows * e->v.G * sizeof(double)));
+        e->sc_rows = rows;
+        e->sc_G = e->v.G;
+    }
+    e->sc_rows_used = 0;
+    vf::launch_degeneracy_scores_windows(metric, subset_mask, source == VF_SCORE_COVARIANCE ? e->pm_cov : e->pm_info, e->pm_pose, e->pm_range,
+                                         e->v.B, e->v.M, e->sc, e->stream);
+    HIPCHK(hipGetLastError());
+    e->sc_rows_used = rows;
+    e->sc_metric = metric;
+    e->sc_mask = subset_mask;
+    return VF_OK;
+}
+
+int vf_engine_read_marginal_scores(vf_engine* e, int window, int k0, int n, double* out) {
+    Entry entry_(e, Entry::reads);
+    if (int rc = check_window(e, window)) return rc;
+    if (!e->pose_marginals_valid() || e->sc_rows_used == 0 || e->sc_G != e->v.G)
+        return fail(VF_ERR_INVALID, "no scores: call vf_engine_marginal_scores after vf_engine_marginals_ex with VF_MARGINALS_POSE");
+    if (int rc = check_pose_marginals(e, window, k0, n, "vf_engine_read_marginal_scores")) return rc;
+    if (n == 0 || !out) return VF_OK;
+    // row r of the scores holds G values, a keyframe's at its slot: one strided copy of `rows` stretches of n
+    HIPCHK(hipMemcpy2D(out, (size_t)n * sizeof(double), e->sc + (size_t)window * e->v.M + k0, (size_t)e->v.G * sizeof(double),
+                       (size_t)n * sizeof(double), (size_t)e->sc_rows_used, hipMemcpyDeviceToHost));
     return VF_OK;
 }

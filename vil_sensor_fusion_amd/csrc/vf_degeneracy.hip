@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/vilfusion.h"
+#include "vf_kernels.hpp"
 
 extern "C" void vf_set_last_error_(const char* msg);
 
@@ -768,51 +769,49 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
     else if (i < count) out[i] = y;
 }
 
-// Several subsets of one metric in one launch (the online node's score_all / score_trans / score_rot of one message,
-// vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130): the wave's 64 matrices (and the one before them) are staged
-// into LDS ONCE, as k_degeneracy stages them, and every subset set in `mask` is then evaluated from that image, one
-// after another (subsets in sequence, not interleaved: the registers are those of the largest one).  out: one row of
-// `count` values per subset in the mask, in ascending subset id.  All 65 matrices stay in LDS for the whole launch
-// (19.2 KB per wave in float64), so all the loads are issued before the first is waited for.
-template <typename T, int METRIC>
-__global__ void __launch_bounds__(64) k_degeneracy_scores(const T* __restrict__ mats, const T* __restrict__ pose, int count,
-                                                          unsigned mask, T* __restrict__ out) {
-    __shared__ T lds[65 * MSTRIDE];
-    const int lane = threadIdx.x, base = blockIdx.x * 64;
-    const int i = base + lane;
-    constexpr bool PREV = metric_needs_prev(METRIC);
-    const bool active = i > 0 && i < count;
-    {
-        const int first = (PREV && base > 0) ? base - 1 : base;           // first matrix staged, local index first - base + 1
-        const int last = base + 64 < count ? base + 64 : count;
-        constexpr int V = 16 / (int)sizeof(T);
-        constexpr int PER = (65 * 36 / V + 63) / 64;                       // 16-byte loads per lane at most
-        const int nvec = (last - first) * 36 / V;
-        using vec_t = T __attribute__((ext_vector_type(V)));
-        const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
-        vec_t x[PER];
+// The staging of the two fused kernels below: the 64 matrices of the series from `base` on (those that exist: the series has
+// `count`), and with PREV the one in front of them, are ONE contiguous stretch of HBM; it is copied into the LDS image (matrix
+// base + l at local index l + 1, the one in front at 0) with 16-byte loads, all of them issued before the first is waited for.
+template <typename T, bool PREV>
+DI void stage_series_tile(T* __restrict__ lds, const T* __restrict__ mats, int base, int count, int lane) {
+    const int first = (PREV && base > 0) ? base - 1 : base;           // first matrix staged, local index first - base + 1
+    const int last = base + 64 < count ? base + 64 : count;
+    constexpr int V = 16 / (int)sizeof(T);
+    constexpr int PER = (65 * 36 / V + 63) / 64;                       // 16-byte loads per lane at most
+    const int nvec = (last - first) * 36 / V;
+    using vec_t = T __attribute__((ext_vector_type(V)));
+    const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
+    vec_t x[PER];
 #pragma unroll
-        for (int k = 0; k < PER; k++)
-            if (lane + 64 * k < nvec) x[k] = __builtin_nontemporal_load(src + lane + 64 * k);
+    for (int k = 0; k < PER; k++)
+        if (lane + 64 * k < nvec) x[k] = __builtin_nontemporal_load(src + lane + 64 * k);
 #pragma unroll
-        for (int k = 0; k < PER; k++) {
-            const int v = lane + 64 * k;
-            if (v < nvec) {
-                const int e = v * V, m = e / 36, r = e - m * 36;
-                T* dst = lds + (m + first - base + 1) * MSTRIDE + r;
+    for (int k = 0; k < PER; k++) {
+        const int v = lane + 64 * k;
+        if (v < nvec) {
+            const int e = v * V, m = e / 36, r = e - m * 36;
+            T* dst = lds + (m + first - base + 1) * MSTRIDE + r;
 #pragma unroll
-                for (int j = 0; j < V; j++) dst[j] = x[k][j];
-            }
+            for (int j = 0; j < V; j++) dst[j] = x[k][j];
         }
     }
-    __syncthreads();
+}
+
+// ... and what they do with the image: every subset set in `mask` for message i = base + lane of the series, one after
+// another (subsets in sequence, not interleaved: the registers are those of the largest one).  out: one row per subset in
+// the mask, in ascending subset id, `row` values apart; the lane's value goes to entry i of each.
+template <typename T, int METRIC>
+DI void scores_from_image(const T* __restrict__ lds, const T* __restrict__ pose, int i, int count, unsigned mask, T* __restrict__ out,
+                          size_t row, int lane) {
+    constexpr bool PREV = metric_needs_prev(METRIC);
+    const bool active = i > 0 && i < count;
     const T* mn = lds + (lane + 1) * MSTRIDE;
     const T* mp = lds + lane * MSTRIDE;
     T* o = out;
     auto put = [&](T y) {
         if (i == 0) o[0] = T(0);
         else if (i < count) o[i] = y;
-        o += count;
+        o += row;
     };
     if (mask & 1u) {
         T now[36], prev[36];
@@ -836,6 +835,42 @@ __global__ void __launch_bounds__(64) k_degeneracy_scores(const T* __restrict__ 
             pick_block<T, 1>(mp, subset_off(s), PREV && active, prev);
             put(degeneracy_metric<T, 1, METRIC>(now, prev, pose, i, count, subset_off(s), active, nullptr, nullptr));
         }
+}
+
+// Several subsets of one metric in one launch (the online node's score_all / score_trans / score_rot of one message,
+// vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130): the wave's 64 matrices (and the one before them) are staged
+// into LDS ONCE, as k_degeneracy stages them, and every subset set in `mask` is then evaluated from that image, one
+// after another.  out: one row of `count` values per subset in the mask, in ascending subset id.  All 65 matrices stay in
+// LDS for the whole launch (19.2 KB per wave in float64).
+template <typename T, int METRIC>
+__global__ void __launch_bounds__(64) k_degeneracy_scores(const T* __restrict__ mats, const T* __restrict__ pose, int count,
+                                                          unsigned mask, T* __restrict__ out) {
+    __shared__ T lds[65 * MSTRIDE];
+    const int lane = threadIdx.x, base = blockIdx.x * 64;
+    stage_series_tile<T, metric_needs_prev(METRIC)>(lds, mats, base, count, lane);
+    __syncthreads();
+    scores_from_image<T, METRIC>(lds, pose, base + lane, count, mask, out, (size_t)count, lane);
+}
+
+// The same over the windows of an engine, from records that are on the device already (the pose marginals vf_engine_marginals_ex
+// leaves with VF_MARGINALS_POSE: kernels/kpose.inc): grid (tiles of 64 keyframes, windows).  mats / pose hold one record per
+// keyframe slot, [windows x M]; the range [lo, hi) of window w (range[2 w], range[2 w + 1]) is a series of its own -- the
+// score of keyframe lo is 0, and `prev` never reaches into another window or in front of lo.  Tile t of a window is messages
+// 64 t .. 64 t + 63 of that series, so the wave-uniform decisions inside the metrics are taken over the same 64 messages as in
+// k_degeneracy_scores run on the window's records alone, and the bits are the same.  out: one row of windows x M values per
+// subset in the mask; the value of a keyframe sits at its slot.  float64 only (the records are).
+template <int METRIC>
+__global__ void __launch_bounds__(64) k_degeneracy_scores_windows(const double* __restrict__ mats, const double* __restrict__ pose,
+                                                                  const int* __restrict__ range, int M, size_t row, unsigned mask,
+                                                                  double* __restrict__ out) {
+    __shared__ double lds[65 * MSTRIDE];
+    const int w = blockIdx.y, lane = threadIdx.x, base = blockIdx.x * 64;
+    const int lo = range[2 * w], count = range[2 * w + 1] - lo;
+    if (base >= count || lo < 0 || lo + count > M) return;
+    const size_t g0 = (size_t)w * M + lo;
+    stage_series_tile<double, metric_needs_prev(METRIC)>(lds, mats + g0 * 36, base, count, lane);
+    __syncthreads();
+    scores_from_image<double, METRIC>(lds, pose + g0 * 6, base + lane, count, mask, out + g0, row, lane);
 }
 
 template <typename T, int N>
@@ -863,7 +898,20 @@ void launch_degeneracy_scores(int metric, dim3 grid, const T* m, const T* p, int
     }
 #undef VF_K6_CASE
 }
-static_assert(N_METRICS == 25, "launch_degeneracy and launch_degeneracy_scores list every metric");
+void launch_degeneracy_scores_windows(int metric, dim3 grid, const double* m, const double* p, const int* range, int M, size_t row, unsigned mask,
+                                      double* o, hipStream_t st) {
+#define VF_K6_CASE(K) case K: hipLaunchKernelGGL((k_degeneracy_scores_windows<K>), grid, dim3(64), 0, st, m, p, range, M, row, mask, o); break;
+    switch (metric) {
+        VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
+        VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
+        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
+        VF_K6_CASE(24)
+        default: break;
+    }
+#undef VF_K6_CASE
+}
+static_assert(N_METRICS == 25, "launch_degeneracy, launch_degeneracy_scores and launch_degeneracy_scores_windows list every metric");
+static_assert(N_METRICS == vf::K6_METRICS && N_SUBSETS == vf::K6_SUBSETS, "what vf_engine_marginal_scores checks its arguments against");
 
 template <typename T>
 int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_max, void* o_cond, int reps, float* kernel_ms);
@@ -1015,6 +1063,14 @@ int run_scores(const void* mats, const void* pose, int count, int metric, unsign
 }
 
 }  // namespace
+
+// what vf_engine.hip reaches the windows kernel through (vf_kernels.hpp; not part of the ABI).  The caller has checked metric and mask.
+namespace vf {
+void launch_degeneracy_scores_windows(int metric, unsigned mask, const double* mats, const double* pose, const int* range, int B, int M,
+                                      double* out, hipStream_t s) {
+    ::launch_degeneracy_scores_windows(metric, dim3((M + 63) / 64, B), mats, pose, range, M, (size_t)B * M, mask, out, s);
+}
+}  // namespace vf
 
 extern "C" {
 

@@ -371,6 +371,20 @@ struct vf_engine : EngineHandle {
     // on first use and grown when a later call needs more; FARCOV_BUDGET bounds it, more windows than fit are done in groups
     double* fc_scratch = nullptr;
     size_t fc_doubles = 0;
+    // VF_MARGINALS_POSE (kernels/kpose.inc): the pose marginals in nav_msgs order, their inverses and the poses, [G][36], [G][36] and
+    // [G][6] in one allocation made by the first call that carries the flag, with the range [B][2] each window's records are of;
+    // pm_on: the last vf_engine_marginals_ex carried it (with SolveMemory::covariances_valid: the records are there to be read)
+    double *pm_cov = nullptr, *pm_info = nullptr, *pm_pose = nullptr;
+    int* pm_range = nullptr;
+    long pm_G = 0;
+    bool pm_on = false;
+    bool pose_marginals_valid() const { return pm_on && pm_cov && pm_G == v.G && sig_G == v.G && mem.covariances_valid(); }
+    // vf_engine_marginal_scores: one row of G scores per subset asked for, grown on demand; what the last call computed (sc_rows_used
+    // = 0: nothing since the last vf_engine_marginals_ex)
+    double* sc = nullptr;
+    int sc_rows = 0, sc_rows_used = 0, sc_metric = -1;
+    unsigned sc_mask = 0;
+    long sc_G = 0;
     // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
     void swap_arrays(vf_engine& o) { std::swap(*this, o), std::swap<EngineHandle>(*this, o); }
     int ensure_stage(size_t bytes) {

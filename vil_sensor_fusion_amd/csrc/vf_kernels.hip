@@ -134,4 +134,5 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
 #include "kernels/launch.inc"
 #include "kernels/k4_selinv.inc"
 #include "kernels/k4_selinv_far.inc"
+#include "kernels/kpose.inc"
 }  // namespace vf

@@ -333,6 +333,15 @@ struct FarCov {
     size_t zwin, cwin;
 };
 void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStream_t s);
+// ... and behind both (VF_MARGINALS_POSE): every keyframe's pose marginal in nav_msgs order (A Sigma_pp A^T, [G][36]), its inverse
+// ([G][36]) and the pose as (x, y, z, roll, pitch, yaw) ([G][6]); pm_range: [B][2], the range [lo, hi) each window's records are of
+void launch_pose_marginals(const View& v, const int* failed, const double* sig, double* pm_cov, double* pm_info, double* pm_pose,
+                           int* pm_range, hipStream_t s);
+constexpr int K6_METRICS = 25, K6_SUBSETS = 9;     // metric ids 0 .. 24 (VF_METRIC_*) and subset ids 0 .. 8 (VF_SUBSET_*) of vf_degeneracy.hip
+// K6 over those records (vf_degeneracy.hip, k_degeneracy_scores_windows): one metric on the subsets of `mask`, every window's range a
+// series of its own; mats / pose: [B M][36] / [B M][6], range: [B][2], out: one row of B M values per subset in the mask
+void launch_degeneracy_scores_windows(int metric, unsigned mask, const double* mats, const double* pose, const int* range, int B, int M,
+                                      double* out, hipStream_t s);
 void launch_retract(const View& v, hipStream_t s);
 void launch_model_change(const View& v, hipStream_t s);     // View::model of every window, from g and the increment just solved
 void launch_decide(const View& v, int init, hipStream_t s);

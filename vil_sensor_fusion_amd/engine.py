@@ -90,6 +90,7 @@ class Engine:
         self.opts = opts
         self.capacity = (opts.capacity + 63) // 64 * 64
         self.windows = opts.windows
+        self._score_rows = [0]      # subset ids of the last marginal_scores (read_marginal_scores)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -371,15 +372,44 @@ class Engine:
         check(self._l.vf_engine_read_panels(self._h, window, k0, n, _d(p)))
         return p
 
-    def marginals(self, far=False):
+    def marginals(self, far=False, pose=False):
         """Enqueue the marginal covariances of every window's keyframes at the current states (vf_engine_marginals): undamped
         factorisation + selected inversion.  Leaves the LM state as it was; read them with read_marginals.  far=True
         (vf_engine_marginals_ex with VF_MARGINALS_FAR): far factors alive, linear ones included, correct the covariances by a
-        low-rank downdate instead of being refused."""
-        if far:
-            check(self._l.vf_engine_marginals_ex(self._h, _lib.MARGINALS_FAR))
+        low-rank downdate instead of being refused.  pose=True (VF_MARGINALS_POSE): the same call also leaves every keyframe's
+        pose covariance in nav_msgs order, its inverse and its pose on the device (read_pose_marginals, marginal_scores)."""
+        flags = (_lib.MARGINALS_FAR if far else 0) | (_lib.MARGINALS_POSE if pose else 0)
+        if flags:
+            check(self._l.vf_engine_marginals_ex(self._h, flags))
         else:
             check(self._l.vf_engine_marginals(self._h))
+
+    def read_pose_marginals(self, window, k0, n):
+        """(cov (n, 6, 6), info (n, 6, 6), pose (n, 6)) of keyframes k0 .. k0+n-1 as marginals(pose=True) left them: the pose
+        covariance over (x, y, z, rx, ry, rz) (covariance.ros_pose_covariance), its inverse, (x, y, z, roll, pitch, yaw)."""
+        cov, info, pose = np.zeros((n, 6, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6))
+        check(self._l.vf_engine_read_pose_marginals(self._h, window, k0, n, _d(cov), _d(info), _d(pose)))
+        return cov, info, pose
+
+    def marginal_scores(self, metric, subsets=("all", "trans", "rot"), information=False):
+        """Enqueue one degeneracy metric (a name of degeneracy.ALL_METRICS) on `subsets` of every keyframe's pose covariance (or,
+        information=True, its inverse), every window a time series of its own (vf_engine_marginal_scores; needs
+        marginals(pose=True)).  Read them with read_marginal_scores."""
+        from . import degeneracy
+        rows = sorted({degeneracy.SUBSETS[s] for s in subsets})
+        check(self._l.vf_engine_marginal_scores(self._h, _lib.SCORE_INFORMATION if information else _lib.SCORE_COVARIANCE,
+                                                degeneracy._metric_id(metric), sum(1 << r for r in rows)))
+        self._score_rows = rows
+
+    def read_marginal_scores(self, window, k0, n):
+        """{subset: (n,)} of the last marginal_scores for keyframes k0 .. k0+n-1 of a window: bit for bit what degeneracy.scores
+        gives for the window's read_pose_marginals alone."""
+        from . import degeneracy
+        rows = self._score_rows
+        out = np.zeros((len(rows), n))
+        check(self._l.vf_engine_read_marginal_scores(self._h, window, k0, n, _d(out)))
+        names = {v: k for k, v in degeneracy.SUBSETS.items()}
+        return {names[r]: out[i] for i, r in enumerate(rows)}
 
     def read_marginals(self, window, k0, n, cross=False):
         """Sigma_kk of keyframes k0 .. k0+n-1 as (n, 15, 15); with cross=True also Sigma_{k+1,k} (n, 15, 15), row = dof of k+1.

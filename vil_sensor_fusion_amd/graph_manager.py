@@ -148,6 +148,25 @@ class GraphManager:
         check(self._l.vf_get_marginal_covariance(self._h, C.c_uint64(key), _d(cov)))
         return cov
 
+    def degeneracy_scores(self, metric, subsets=("all", "trans", "rot"), information=False, key0=None, n=None):
+        """One degeneracy metric (a name of degeneracy.ALL_METRICS) on `subsets` of the nav_msgs pose covariance (or,
+        information=True, its inverse) of the solved keys key0 .. key0+n-1, computed on the device from the covariances of the
+        last solve (vf_get_degeneracy_scores): {subset: (n,)}.  The window is one time series, the score of its oldest key is 0.
+        Defaults: from the oldest key of the last solve's window to the last reserved key (which that solve must have covered)."""
+        from . import degeneracy
+        if key0 is None or n is None:
+            last = self.getMostRecentPoseTime()[1]
+            first = last - self.solverInfo()[0] + 1
+            key0 = first if key0 is None else key0
+            n = last - key0 + 1 if n is None else n
+        rows = sorted({degeneracy.SUBSETS[s] for s in subsets})
+        out = np.zeros((len(rows), n))
+        check(self._l.vf_get_degeneracy_scores(self._h, _lib.SCORE_INFORMATION if information else _lib.SCORE_COVARIANCE,
+                                               degeneracy._metric_id(metric), sum(1 << r for r in rows), C.c_uint64(key0), n,
+                                               out.ctypes.data_as(C.c_void_p)))
+        names = {v: k for k, v in degeneracy.SUBSETS.items()}
+        return {names[r]: out[i] for i, r in enumerate(rows)}
+
     def getState(self):
         q, t, v, b = np.zeros(4), np.zeros(3), np.zeros(3), np.zeros(6)
         check(self._l.vf_get_state(self._h, _d(q), _d(t), _d(v), _d(b)))
