@@ -507,7 +507,7 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags);
  * symmetric 15x15, row-major) and the cross block Sigma_{k+1,k} (15x15, row = dof of k+1, column = dof of k; zero for the window's
  * last keyframe).  Tangent order [omega, v] of Pose3, velocity, bias [acc, gyro].  Either pointer may be NULL.  VF_ERR_NOT_SPD:
  * the window's undamped normal equations are not positive definite; VF_ERR_INVALID: no vf_engine_marginals since the engine was
- * made or compacted; VF_ERR_BAD_KEY: outside that range. */
+ * made, compacted or grown; VF_ERR_BAD_KEY: outside that range. */
 int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* cov225, double* cross225);
 /* ... and the records of VF_MARGINALS_POSE (synchronises): n x 36, n x 36 and n x 6 doubles; any pointer may be NULL.  Refusals as
  * vf_engine_read_marginals; VF_ERR_INVALID also when the last vf_engine_marginals_ex did not carry VF_MARGINALS_POSE. */
@@ -519,7 +519,7 @@ int vf_engine_read_pose_marginals(vf_engine* e, int window, int k0, int n, doubl
  * compared with one of another window.  The values are bit for bit what vf_degeneracy_scores_batch returns for the window's
  * records (vf_engine_read_pose_marginals) alone; kullback_leibler takes its poses from pose6.  The scores live in a device array
  * sized for the rows asked for and grown on demand.  VF_ERR_INVALID: unknown source, metric or mask; no pose marginals (none
- * computed, or the engine was compacted since). */
+ * computed, or the engine was compacted or grown since). */
 #define VF_SCORE_COVARIANCE 0
 #define VF_SCORE_INFORMATION 1
 int vf_engine_marginal_scores(vf_engine* e, int source, int metric, unsigned subset_mask);

@@ -38,6 +38,13 @@ struct Rig {
                m.tail(), tail, m.is_warm(), warm, m.inc_whole_window(), whole, m.inc_appended(hi), appended, m.stash_fits(lo), stash,
                m.result_cached_for(0, hi - 1, false), cached, m.covariances_valid(), cov);
     }
+    // what the covariance calls left: the blocks, the pose records, rows of scores
+    void expect_cov(const char* step, bool cov, bool pose, int rows) {
+        if (m.covariances_valid() == cov && m.pose_records_valid() == pose && m.score_rows() == rows) return;
+        failures++;
+        printf("FAIL %s / %s: covariances %d (want %d) pose records %d (%d) score rows %d (%d)\n", name, step, m.covariances_valid(), cov,
+               m.pose_records_valid(), pose, m.score_rows(), rows);
+    }
     void write(int w, int k) { m.written_from(w, k, lo, hi); }
     void range(int nlo, int nhi) { m.range_set(nlo, nhi, lo, hi); lo = nlo; hi = nhi; }
     void slide() { m.slid_by_one(); lo++; hi++; }
@@ -232,6 +239,46 @@ int main() {
         r.m.grown();
         r.solved(false, true);       // slid / redo were reset (:473): a replayed solve's successor starts from a tail of 0
         r.expect("grown", 0, true, true, 1, false, false, false);
+    }
+    {   // what the covariance calls leave: the pose records only with the blocks and the flag of the LAST call, scores only of the
+        // records of that call (marginals.inc: pm_on, sc_rows_used and the sig_G / pm_G / sc_G comparisons of the commit "Degeneracy
+        // scores of the solved keyframes' pose marginals, on device")
+        Rig r = make("covariances", WARM);
+        r.expect_cov("solved, never asked", false, false, 0);
+        r.m.scores_computed(3);                    // (the engine refuses this call; the account does not depend on that)
+        r.expect_cov("scores of nothing", false, false, 0);
+        r.m.covariances_started();
+        r.m.covariances_computed(true);
+        r.expect_cov("marginals with the flag", true, true, 0);
+        r.m.scores_computed(0);
+        r.m.scores_computed(3);
+        r.expect_cov("scores", true, true, 3);
+        r.slide();
+        r.solved();
+        r.expect_cov("a solve keeps all three", true, true, 3);
+        r.m.covariances_started();
+        r.m.covariances_computed(true);
+        r.expect_cov("a covariance call voids the scores", true, true, 0);
+        r.m.scores_computed(2);
+        r.m.covariances_started();
+        r.m.covariances_computed(false);
+        r.expect_cov("without the flag: pose records and scores void", true, false, 0);
+        r.m.covariances_computed(true);
+        r.m.scores_computed(1);
+        r.m.covariances_started();                 // ... and the call fails on the way (an allocation, a launch)
+        r.expect_cov("started, never computed", false, false, 0);
+        r.m.scores_computed(1);
+        r.expect_cov("scores of void records", false, false, 0);
+        for (int grown = 0; grown < 2; grown++) {
+            r.m.covariances_started();
+            r.m.covariances_computed(true);
+            r.m.scores_computed(3);
+            if (grown) r.m.grown();
+            else r.m.compacted();
+            r.expect_cov(grown ? "grown" : "compacted", false, false, 0);
+            r.m.scores_computed(3);
+            r.expect_cov(grown ? "grown, scores" : "compacted, scores", false, false, 0);
+        }
     }
     {   // the cached result: set at the end of an adaptive solve (solve.inc:308), kept across vf_engine_marginals
         // (marginals.inc:24-26), void after any other entry point (vf_engine.hip:396), vf_engine_read_result included (staging.inc:84-85)

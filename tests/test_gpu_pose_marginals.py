@@ -220,6 +220,38 @@ def test_refusals(problems, oracle):
     one.close()
 
 
+def test_a_grow_voids_them_and_the_next_call_brings_them_back(oracle):
+    """vf_engine_grow puts new arrays behind the handle: what the covariance calls left went with the old ones, every reader
+    refuses.  Computed again they are, to the bit, those of an engine created at the new capacity that holds the same problem
+    at the same states (handed over, not solved for again: the form of a solve depends on the capacity, the marginals' does not)."""
+    n = 40
+    prob = helpers.build_problem(oracle, synth.make_sequence(seed=44, n_kf=n), perturb=0.01)
+    eng = Engine(EngineOpts(windows=1, capacity=128))
+    helpers.load_engine(eng, 0, prob)
+    eng.iterate(3)
+    eng.marginals(pose=True)
+    eng.marginal_scores("d_opt")
+    assert eng.read_marginal_scores(0, 0, n)["all"][0] == 0.0
+    eng.grow(192)
+    assert _code(eng.read_marginals, 0, 0, n) == -1
+    assert _code(eng.read_pose_marginals, 0, 0, n) == -1
+    assert _code(eng.marginal_scores, "d_opt") == -1
+    assert _code(eng.read_marginal_scores, 0, 0, n) == -1
+    ref = Engine(EngineOpts(windows=1, capacity=192))
+    helpers.load_engine(ref, 0, prob)
+    ref.set_states(0, 0, eng.get_states(0, 0, n))
+    got = []
+    for e in (eng, ref):
+        e.marginals(pose=True)
+        e.marginal_scores("d_opt")
+        scores = e.read_marginal_scores(0, 0, n)
+        got.append([*e.read_marginals(0, 0, n, cross=True), *e.read_pose_marginals(0, 0, n), *(scores[s] for s in SUBS3)])
+        e.close()
+    assert len(got[0]) == 8 and np.all(np.isfinite(got[0][0])) and got[0][5][0] == 0.0
+    for a, b in zip(*got):
+        np.testing.assert_array_equal(a, b)
+
+
 def test_with_a_far_factor_alive(problems):
     from tests.test_gpu_far_factors import _far_record
     rec28 = _far_record(problems[0][0], 12, 60, np.random.default_rng(5))

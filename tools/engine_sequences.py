@@ -1,11 +1,12 @@
 """Scripted engine-level call sequences that exercise what the engine remembers from solve to solve (csrc/vf_engine_memory.hpp):
 warm tails, late writes, set_range, several windows, cold_start, marginalise-ahead / commit, the cached result block,
-incremental updates, far factors, compact and grow in mid-run, each with vf_engine_opts.use_hip_graph off and on where it applies.
+incremental updates, far factors, compact and grow in mid-run, what the covariance calls leave across those two, each with
+vf_engine_opts.use_hip_graph off and on where it applies.
 
 After each call one line: the call, its return code, and what the ABI shows -- vf_engine_graph_info, vf_engine_solve_form,
-vf_engine_incremental_info, a digest of the window's states and the last state as hex.  Two builds of the library that do the
-same thing print the same bytes; under `rocprofv3 --kernel-trace -- python tools/engine_sequences.py` they launch the same
-kernels in the same order (a warm tail shows as k_linearize_tail, a committed stash as k_marg_commit, a cached result as a
+vf_engine_incremental_info, a digest of the window's states and the last state as hex; after a read of covariances, pose
+records or scores a digest of what it returned.  Two builds of the library that do the same thing print the same
+bytes; under `rocprofv3 --kernel-trace -- python tools/engine_sequences.py` they launch the same kernels in the same order (a warm tail shows as k_linearize_tail, a committed stash as k_marg_commit, a cached result as a
 missing k_read_result, a re-capture in graph_info).
 
     python tools/engine_sequences.py [scenario ...]        (default: all)
@@ -86,6 +87,26 @@ class Run:
         self.lo, self.hi = lo, hi
 
 
+def digest(*arrays):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()[:16]
+
+
+def marginals(r, compute=True, far=False):
+    """what the covariance calls leave, read back (a digest each): the blocks, the pose records, one set of scores.
+    compute=False: only the reads, of whatever the last calls left (after compact / grow: refusals)"""
+    e, n = r.eng, r.hi - r.lo
+    if compute:
+        r.call(f"marginals(far={far}, pose=True)", e.marginals, far, True, probe=False)
+    reads = [("read_marginals", lambda: digest(e.read_marginals(0, r.lo, n))),
+             ("read_pose_marginals", lambda: digest(*e.read_pose_marginals(0, r.lo, n))),
+             ("marginal_scores(d_opt)", lambda: e.marginal_scores("d_opt")),
+             ("read_marginal_scores", lambda: digest(*e.read_marginal_scores(0, r.lo, n).values()))]
+    for what, fn in reads if compute else reads[:2] + reads[3:]:
+        out = r.call(what, fn, probe=False)
+        if out:
+            print(f"    {out}")
+
+
 def fixed_lag(graph):
     r = Run(f"fixed_lag graph={int(graph)}", 256, 64, 40, use_hip_graph=graph, **SWEEP)
     r.iterate(3)
@@ -113,18 +134,23 @@ def fixed_lag(graph):
     r.call("set_range(bad)", r.eng.set_range, 0, 5, 4, probe=False)
     r.iterate(1)
     r.slide()
+    marginals(r)
     r.call("compact(64)", r.eng.compact, 64, probe=False)
     r.lo, r.hi, r.shift = r.lo - 64, r.hi - 64, 64
+    marginals(r, compute=False)
     r.iterate(2)
+    marginals(r)
     r.slide()
     r.iterate(2)
     r.slide()
     r.call("grow(512)", r.eng.grow, 512)
+    marginals(r, compute=False)
     r.iterate(2)
     r.slide()
     r.iterate(2)
     r.call("marginals", r.eng.marginals, probe=False)
-    r.call("read_marginals", lambda: hashlib.sha256(r.eng.read_marginals(0, r.lo, r.hi - r.lo).tobytes()).hexdigest()[:16], probe=False)
+    marginals(r, compute=False)                    # without the flag: the blocks, no pose records, no scores
+    marginals(r)
     r.iterate(2)
     r.eng.close()
 
@@ -218,8 +244,12 @@ def far(graph):
     r.iterate(2)
     r.slide()
     r.iterate(2)
+    r.call("marginals", r.eng.marginals, probe=False)         # refused: a far factor is alive
+    marginals(r, far=True)
     r.call("grow(256)", r.eng.grow, 256)
+    marginals(r, compute=False)
     r.iterate(2)
+    marginals(r, far=True)
     r.call("set_shard(0, 2)", r.eng.set_shard, 0, 2, probe=False)
     r.call("iterate on a shard", r.eng.iterate, 1, probe=False)
     r.eng.close()

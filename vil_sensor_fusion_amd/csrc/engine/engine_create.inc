@@ -250,27 +250,13 @@ void vf_engine_destroy(vf_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     e->drop_graph();
     for (void* p : e->allocs) (void)hipFree(p);
-    if (e->stage) (void)hipFree(e->stage);
-    if (e->pre_buf) (void)hipFree(e->pre_buf);
-    if (e->in_host) (void)hipHostFree(e->in_host);
-    if (e->rq_stop_host) (void)hipHostFree(e->rq_stop_host);
-    if (e->in_dev) (void)hipFree(e->in_dev);
-    if (e->in_status) (void)hipFree(e->in_status);
     for (auto ev : e->in_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->far_columns) { vf_engine_destroy(e->far_columns); e->far_columns = nullptr; }
     if (e->stream2) { (void)hipStreamSynchronize(e->stream2); (void)hipStreamDestroy(e->stream2); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    if (e->sticky_dev) (void)hipFree(e->sticky_dev);
-    if (e->res_host) (void)hipHostFree(e->res_host);
-    if (e->x_gtmp) (void)hipFree(e->x_gtmp);
-    if (e->x_Z) (void)hipFree(e->x_Z);
-    if (e->sig) (void)hipFree(e->sig);
-    if (e->fc_scratch) (void)hipFree(e->fc_scratch);
-    if (e->pm_cov) (void)hipFree(e->pm_cov);
-    if (e->sc) (void)hipFree(e->sc);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream && e->own_stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;      // (frees what owns itself, vf_device_buf.hpp, while entry_ still holds the engine's device current)
 }

@@ -27,59 +27,42 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (e->x_used > 0 && !far)
         return fail(VF_ERR_INVALID, "vf_engine_marginals: a window holds far factors (vf_engine_get_extra_between / vf_engine_get_linear_far); "
                     "their correction of the covariance needs vf_engine_marginals_ex(e, VF_MARGINALS_FAR)");
+    e->mem.covariances_started();      // (behind every refusal: a refused call leaves the engine as it was)
     const int m = 6 * e->x_used;
     const size_t zwin = (size_t)e->v.M * 15 * m, cwin = (size_t)m * m;
     int group = 0;
     if (m > 0) {
         const size_t per = (zwin + cwin) * sizeof(double);
         group = (int)std::max<size_t>(1, std::min<size_t>((size_t)e->v.B, FARCOV_BUDGET / per));
-        const size_t want = (size_t)group * (zwin + cwin);
-        if (want > e->fc_doubles) {
+        const size_t want = (size_t)group * per;
+        if (want > e->fc_scratch.bytes()) {
             HIPCHK(hipStreamSynchronize(e->stream));
-            if (e->fc_scratch) { (void)hipFree(e->fc_scratch); e->fc_scratch = nullptr; e->fc_doubles = 0; }
-            HIPCHK(hipMalloc((void**)&e->fc_scratch, want * sizeof(double)));
-            e->fc_doubles = want;
+            HIPCHK(e->fc_scratch.ensure(want));
         }
     }
     const size_t G = (size_t)e->v.G, B = (size_t)e->v.B;
-    if (!e->sig || e->sig_G != e->v.G) {
+    if (!e->sig) {
         // allocated on first use (G x 2.7 KB): engines that never ask for covariances do not grow
-        if (e->sig) { HIPCHK(hipStreamSynchronize(e->stream)); (void)hipFree(e->sig); e->sig = nullptr; }
-        void* q = nullptr;
-        HIPCHK(hipMalloc(&q, G * vf::SIG_SLOT * sizeof(double) + B * (sizeof(double) + 2 * sizeof(int)) + 256));
-        e->sig = (double*)q;
-        e->sig_G = e->v.G;
-        e->sig_zero = e->sig + G * vf::SIG_SLOT;
-        e->sig_fail = (int*)(e->sig_zero + B);
-        e->sig_ones = e->sig_fail + B;
+        HIPCHK(e->sig.ensure(G * vf::SIG_SLOT * sizeof(double) + B * (sizeof(double) + 2 * sizeof(int)) + 256));
         std::vector<int> ones(B, 1);
-        HIPCHK(hipMemsetAsync(e->sig_zero, 0, B * sizeof(double), e->stream));
-        HIPCHK(hipMemcpyAsync(e->sig_ones, ones.data(), B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(e->sig_zero(), 0, B * sizeof(double), e->stream));
+        HIPCHK(hipMemcpyAsync(e->sig_ones(), ones.data(), B * sizeof(int), hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
-    if (pose && (!e->pm_cov || e->pm_G != e->v.G)) {
-        // allocated on first use as sig is (G x 624 B): only engines that ask for the nav_msgs records hold them
-        if (e->pm_cov) { HIPCHK(hipStreamSynchronize(e->stream)); (void)hipFree(e->pm_cov); e->pm_cov = nullptr; }
-        void* q = nullptr;
-        HIPCHK(hipMalloc(&q, G * (36 + 36 + 6) * sizeof(double) + 2 * B * sizeof(int) + 256));
-        e->pm_cov = (double*)q;
-        e->pm_info = e->pm_cov + G * 36;
-        e->pm_pose = e->pm_info + G * 36;
-        e->pm_range = (int*)(e->pm_pose + G * 6);
-        e->pm_G = e->v.G;
-    }
-    e->mem.rewritten();      // (inherited order: a refused call leaves the engine as it was)
+    // allocated on first use as sig is (G x 624 B): only engines that ask for the nav_msgs records hold them
+    if (pose) HIPCHK(e->pm_cov.ensure(G * (36 + 36 + 6) * sizeof(double) + 2 * B * sizeof(int) + 256));
+    e->mem.rewritten();
     vf::View a = e->v;
-    a.lambda = e->sig_zero;          // undamped
-    a.fail = e->sig_fail;
-    a.fresh = e->sig_ones;           // every window assembled, whole
+    a.lambda = e->sig_zero();         // undamped
+    a.fail = e->sig_fail();
+    a.fresh = e->sig_ones();          // every window assembled, whole
     a.stop_on = 0;                   // ... whether or not the termination rule has finished it
     a.gate = 0;
     a.act = nullptr;
     a.inc_on = 0;
     a.relin_only = 0;
     a.P = 0;                         // whole-window sweep whatever form the engine's solves take (they may be partitioned)
-    HIPCHK(hipMemsetAsync(e->sig_fail, 0, B * sizeof(int), e->stream));
+    HIPCHK(hipMemsetAsync(e->sig_fail(), 0, B * sizeof(int), e->stream));
     // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
     vf::launch_linearize(a, 0, e->stream);
     if (m > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
@@ -91,12 +74,12 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
                                                                e->refine_iters() > 0 || e->v.min_fidelity > 0.0));
     if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
     vf::launch_band_factor(a, plan, e->stream);
-    vf::launch_selinv(a, e->sig_fail, e->sig, e->stream);
+    vf::launch_selinv(a, e->sig_fail(), e->sig, e->stream);
     for (int w0 = 0; w0 < e->v.B && m > 0; w0 += group) {
         vf::FarCov fc{};
         fc.Z = e->fc_scratch;
         fc.C = e->fc_scratch + (size_t)group * zwin;
-        fc.failed = e->sig_fail;
+        fc.failed = e->sig_fail();
         fc.w0 = w0;
         fc.m = m;
         fc.slots = e->x_used;
@@ -105,28 +88,36 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
         vf::launch_farcov(a, fc, std::min(group, e->v.B - w0), e->sig, e->stream);
     }
     // the nav_msgs records of every keyframe, of the states this call linearised at (they may move before anyone reads)
-    if (pose) vf::launch_pose_marginals(a, e->sig_fail, e->sig, e->pm_cov, e->pm_info, e->pm_pose, e->pm_range, e->stream);
-    e->pm_on = pose;
-    e->sc_rows_used = 0;
+    if (pose) vf::launch_pose_marginals(a, e->sig_fail(), e->sig, e->pm_cov, e->pm_info(), e->pm_pose(), e->pm_range(), e->stream);
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;
     e->sig_hi = e->h_hi;
-    e->mem.covariances_computed();
+    e->mem.covariances_computed(pose);
+    return VF_OK;
+}
+
+// What every reader of the results refuses, in this order: a window that is not there; results that are not (need 0: the
+// blocks, 1: the pose records too, 2: and scores of them); keyframes outside the range they were computed for; a window whose
+// factorisation failed (the one synchronisation of a read).
+static int check_marginals(vf_engine* e, int window, int k0, int n, int need, const char* what) {
+    if (int rc = check_window(e, window)) return rc;
+    if (need == 2 && e->mem.score_rows() == 0)
+        return fail(VF_ERR_INVALID, "%s: no scores: call vf_engine_marginal_scores after vf_engine_marginals_ex with VF_MARGINALS_POSE", what);
+    if (!e->mem.covariances_valid()) return fail(VF_ERR_INVALID, "%s: no marginal covariances: call vf_engine_marginals_ex first", what);
+    if (need && !e->mem.pose_records_valid()) return fail(VF_ERR_INVALID, "%s: the last vf_engine_marginals_ex did not carry VF_MARGINALS_POSE", what);
+    if (n < 0 || k0 < e->sig_lo[window] || k0 + n > e->sig_hi[window])
+        return fail(VF_ERR_BAD_KEY, "%s: keyframes [%d,%d) outside the range [%d,%d) the covariances were computed for", what, k0, k0 + n,
+                    e->sig_lo[window], e->sig_hi[window]);
+    int failed = 0;
+    HIPCHK(hipMemcpyAsync(&failed, e->sig_fail() + window, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (failed) return fail(VF_ERR_NOT_SPD, "window %d: the undamped normal equations are not positive definite", window);
     return VF_OK;
 }
 
 int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* cov225, double* cross225) {
     Entry entry_(e, Entry::reads);
-    int rc = check_window(e, window);
-    if (rc) return rc;
-    if (!e->mem.covariances_valid() || e->sig_G != e->v.G) return fail(VF_ERR_INVALID, "no marginal covariances: call vf_engine_marginals first");
-    if (n < 0 || k0 < e->sig_lo[window] || k0 + n > e->sig_hi[window])
-        return fail(VF_ERR_BAD_KEY, "keyframes [%d,%d) outside the range [%d,%d) the covariances were computed for", k0, k0 + n,
-                    e->sig_lo[window], e->sig_hi[window]);
-    int failed = 0;
-    HIPCHK(hipMemcpyAsync(&failed, e->sig_fail + window, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (failed) return fail(VF_ERR_NOT_SPD, "window %d: the undamped normal equations are not positive definite", window);
+    if (int rc = check_marginals(e, window, k0, n, 0, "vf_engine_read_marginals")) return rc;
     if (n == 0 || (!cov225 && !cross225)) return VF_OK;
     std::vector<double> raw((size_t)n * vf::SIG_SLOT);
     HIPCHK(hipMemcpy(raw.data(), e->sig + ((size_t)window * e->v.M + k0) * vf::SIG_SLOT, raw.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -140,30 +131,14 @@ int vf_engine_read_marginals(vf_engine* e, int window, int k0, int n, double* co
     return VF_OK;
 }
 
-// the records VF_MARGINALS_POSE leaves: the refusals of vf_engine_read_marginals + the flag
-static int check_pose_marginals(vf_engine* e, int window, int k0, int n, const char* what) {
-    int rc = check_window(e, window);
-    if (rc) return rc;
-    if (!e->mem.covariances_valid() || e->sig_G != e->v.G) return fail(VF_ERR_INVALID, "no marginal covariances: call vf_engine_marginals_ex first");
-    if (!e->pose_marginals_valid()) return fail(VF_ERR_INVALID, "%s: the last vf_engine_marginals_ex did not carry VF_MARGINALS_POSE", what);
-    if (n < 0 || k0 < e->sig_lo[window] || k0 + n > e->sig_hi[window])
-        return fail(VF_ERR_BAD_KEY, "keyframes [%d,%d) outside the range [%d,%d) the covariances were computed for", k0, k0 + n,
-                    e->sig_lo[window], e->sig_hi[window]);
-    int failed = 0;
-    HIPCHK(hipMemcpyAsync(&failed, e->sig_fail + window, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (failed) return fail(VF_ERR_NOT_SPD, "window %d: the undamped normal equations are not positive definite", window);
-    return VF_OK;
-}
-
 int vf_engine_read_pose_marginals(vf_engine* e, int window, int k0, int n, double* cov36, double* info36, double* pose6) {
     Entry entry_(e, Entry::reads);
-    if (int rc = check_pose_marginals(e, window, k0, n, "vf_engine_read_pose_marginals")) return rc;
+    if (int rc = check_marginals(e, window, k0, n, 1, "vf_engine_read_pose_marginals")) return rc;
     if (n == 0) return VF_OK;
     const size_t g = (size_t)window * e->v.M + k0;
     if (cov36) HIPCHK(hipMemcpy(cov36, e->pm_cov + g * 36, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
-    if (info36) HIPCHK(hipMemcpy(info36, e->pm_info + g * 36, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
-    if (pose6) HIPCHK(hipMemcpy(pose6, e->pm_pose + g * 6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (info36) HIPCHK(hipMemcpy(info36, e->pm_info() + g * 36, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+    if (pose6) HIPCHK(hipMemcpy(pose6, e->pm_pose() + g * 6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
     return VF_OK;
 }
 
@@ -175,35 +150,28 @@ int vf_engine_marginal_scores(vf_engine* e, int source, int metric, unsigned sub
     if (metric < 0 || metric >= vf::K6_METRICS) return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: unknown metric %d", metric);
     if (subset_mask == 0 || (subset_mask >> vf::K6_SUBSETS) != 0)
         return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: subset_mask 0x%x: bits 0 .. 8, at least one", subset_mask);
-    if (!e->pose_marginals_valid())
-        return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: no pose marginals (vf_engine_marginals_ex with VF_MARGINALS_POSE; a compaction voids them)");
+    if (!e->mem.pose_records_valid())
+        return fail(VF_ERR_INVALID, "vf_engine_marginal_scores: no pose marginals (vf_engine_marginals_ex with VF_MARGINALS_POSE; compact and grow void them)");
     const int rows = __builtin_popcount(subset_mask);
-    if (rows > e->sc_rows || e->sc_G != e->v.G) {
+    const size_t want = (size_t)rows * e->v.G * sizeof(double);
+    e->mem.scores_computed(0);
+    if (want > e->sc.bytes()) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->sc) { (void)hipFree(e->sc); e->sc = nullptr; e->sc_rows = 0; }
-        HIPCHK(hipMalloc((void**)&e->sc, (size_t)rows * e->v.G * sizeof(double)));
-        e->sc_rows = rows;
-        e->sc_G = e->v.G;
+        HIPCHK(e->sc.ensure(want));
     }
-    e->sc_rows_used = 0;
-    vf::launch_degeneracy_scores_windows(metric, subset_mask, source == VF_SCORE_COVARIANCE ? e->pm_cov : e->pm_info, e->pm_pose, e->pm_range,
+    vf::launch_degeneracy_scores_windows(metric, subset_mask, source == VF_SCORE_COVARIANCE ? e->pm_cov.get() : e->pm_info(), e->pm_pose(), e->pm_range(),
                                          e->v.B, e->v.M, e->sc, e->stream);
     HIPCHK(hipGetLastError());
-    e->sc_rows_used = rows;
-    e->sc_metric = metric;
-    e->sc_mask = subset_mask;
+    e->mem.scores_computed(rows);
     return VF_OK;
 }
 
 int vf_engine_read_marginal_scores(vf_engine* e, int window, int k0, int n, double* out) {
     Entry entry_(e, Entry::reads);
-    if (int rc = check_window(e, window)) return rc;
-    if (!e->pose_marginals_valid() || e->sc_rows_used == 0 || e->sc_G != e->v.G)
-        return fail(VF_ERR_INVALID, "no scores: call vf_engine_marginal_scores after vf_engine_marginals_ex with VF_MARGINALS_POSE");
-    if (int rc = check_pose_marginals(e, window, k0, n, "vf_engine_read_marginal_scores")) return rc;
+    if (int rc = check_marginals(e, window, k0, n, 2, "vf_engine_read_marginal_scores")) return rc;
     if (n == 0 || !out) return VF_OK;
     // row r of the scores holds G values, a keyframe's at its slot: one strided copy of `rows` stretches of n
     HIPCHK(hipMemcpy2D(out, (size_t)n * sizeof(double), e->sc + (size_t)window * e->v.M + k0, (size_t)e->v.G * sizeof(double),
-                       (size_t)n * sizeof(double), (size_t)e->sc_rows_used, hipMemcpyDeviceToHost));
+                       (size_t)n * sizeof(double), (size_t)e->mem.score_rows(), hipMemcpyDeviceToHost));
     return VF_OK;
 }

@@ -295,11 +295,11 @@ int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_
         const size_t off_b = ((size_t)(n + 1) * sizeof(int) + 7) & ~(size_t)7, bytes = steps_b + bias_b + off_b;
         if ((rc = e->ensure_ingest(bytes))) return rc;
         if (e->in_pending) HIPCHK(hipEventSynchronize(e->in_ev[1]));      // (the previous copy has left the pinned buffer: long done)
-        char* h = (char*)e->in_host;
+        char* h = e->in_host;
         if (total > 0) memcpy(h, steps, (size_t)total * 7 * sizeof(double));
         memcpy(h + steps_b, bhat, bias_b);
         memcpy(h + steps_b + bias_b, off, (size_t)(n + 1) * sizeof(int));
-        char* d = (char*)e->in_dev;
+        char* d = e->in_dev;
         HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipEventRecord(e->in_ev[1], e->stream));
         e->in_pending = true;
@@ -314,10 +314,10 @@ int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_
     const size_t steps_b = (size_t)(total > 0 ? total : 1) * 7 * sizeof(double), bias_b = (size_t)n * 6 * sizeof(double);
     const size_t off_b = ((size_t)(n + 1) * sizeof(int) + 7) & ~(size_t)7;
     if ((rc = e->ensure_pre(steps_b + bias_b + off_b + 8))) return rc;
-    double* d_steps = (double*)e->pre_buf;
-    double* d_bhat = (double*)((char*)e->pre_buf + steps_b);
-    int* d_off = (int*)((char*)e->pre_buf + steps_b + bias_b);
-    int* d_status = (int*)((char*)e->pre_buf + steps_b + bias_b + off_b);
+    double* d_steps = (double*)e->pre_buf.get();
+    double* d_bhat = (double*)(e->pre_buf + steps_b);
+    int* d_off = (int*)(e->pre_buf + steps_b + bias_b);
+    int* d_status = (int*)(e->pre_buf + steps_b + bias_b + off_b);
     HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * sizeof(int), hipMemcpyHostToDevice, e->stream));
     if (total > 0) HIPCHK(hipMemcpyAsync(d_steps, steps, (size_t)total * 7 * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(d_bhat, bhat, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -354,12 +354,12 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
     int rc = e->ensure_ingest(bytes);
     if (rc) return rc;
     if (e->in_pending) HIPCHK(hipEventSynchronize(e->in_ev[1]));      // the previous call's copy has left the pinned buffer
-    char* h = (char*)e->in_host;
+    char* h = e->in_host;
     memcpy(h, step_off, (size_t)(B + 1) * sizeof(int));
     memcpy(h + off_b, btw_a, (size_t)B * sizeof(int));
     memcpy(h + off_b + a_b, btw_rec, rec_b);
     memcpy(h + off_b + a_b + rec_b, steps, st_b);
-    char* d = (char*)e->in_dev;
+    char* d = e->in_dev;
     HIPCHK(hipEventRecord(e->in_ev[0], e->stream));
     HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->in_ev[1], e->stream));

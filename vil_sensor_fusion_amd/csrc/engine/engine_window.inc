@@ -183,10 +183,7 @@ int vf_engine_marginalize_ahead(vf_engine* e) {
     // appends follow; anything else voids the stash: SolveMemory)
     if (!e->async_now() || !e->mem.is_warm() || e->h_hi[0] - e->h_lo[0] < 4) return VF_OK;
     if (int rc = e->ensure_async()) return rc;
-    if (!e->marg_stash) {
-        HIPCHK(hipMalloc((void**)&e->marg_stash, (size_t)e->v.B * vf::MARG_STASH_DOUBLES * sizeof(double)));
-        e->allocs.push_back(e->marg_stash);
-    }
+    HIPCHK(e->marg_stash.ensure((size_t)e->v.B * vf::MARG_STASH_DOUBLES * sizeof(double)));
     // on the side stream, behind what the main stream holds now: the preintegration vf_reserve_node enqueues next (main stream)
     // then runs beside it when solves come back to back
     if (int rc = e->ensure_side()) return rc;
@@ -307,7 +304,7 @@ int vf_engine_compact(vf_engine* e, int shift) {
         }
     // between-factor source indices: move (as raw 4-byte ints, staged through the double buffer) then rebase
     {
-        int* stage_i = (int*)e->stage;
+        int* stage_i = (int*)e->stage.get();
         for (int w = 0; w < v.B; w++) {
             int* dst = v.btw_a + (size_t)w * v.M;
             HIPCHK(hipMemcpyAsync(stage_i, dst + shift, keepk * sizeof(int), hipMemcpyDeviceToDevice, e->stream));

@@ -8,18 +8,21 @@
 // node (vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130), and the shipped float32
 // D-optimality gate (gtsam_fusion/src/degerate_odometry_filter.cpp:29-47).
 //
-// Small-matrix kernels: cyclic Jacobi for symmetric eigenvalues, one-sided (Hestenes) Jacobi for
-// singular values, LU with partial pivoting for det / inverse, all with compile-time indices so
-// a 6x6 lives in 36 registers.  float64 and float32 instantiations (fp32 tolerance sweep).
+// Small-matrix kernels: Householder tridiagonalisation + implicit QL for symmetric eigenvalues, one-sided
+// (Hestenes) Jacobi for singular values, LU with partial pivoting for det / inverse, all with compile-time
+// indices so a 6x6 lives in 36 registers.  float64 and float32 instantiations (fp32 tolerance sweep).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vilfusion.h"
 #include "vf_kernels.hpp"
+#include "vf_device_buf.hpp"
 
 extern "C" void vf_set_last_error_(const char* msg);
 
@@ -63,49 +66,6 @@ DI void jacobi_cs(T alpha, T beta, T& t, T& c, T& s) {
     t = beta != T(0) ? beta * rcp_full(den) : T(0);
     c = rsq_full(fma(t, t, T(1)));
     s = t * c;
-}
-
-// symmetric eigenvalues, cyclic Jacobi on the UPPER TRIANGLE (a[p * N + q], p <= q; the strict lower triangle is neither
-// read nor written).  A sweep ends the iteration for the whole wave once every lane's off-diagonal mass has dropped to
-// rounding level, off^2 <= eps^2 * sum diag^2 (eigenvalue error ~ off^2 / gap: far below eps for any spectrum); a 6x6
-// takes 5-7 sweeps, the cap Lim<T>::sweeps is a safety net.  `active`: lanes without a matrix do not hold the wave back.
-template <typename T, int N>
-DI void jacobi_eig(T (&a)[N * N], T (&ev)[N], bool active) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < Lim<T>::sweeps; sweep++) {
-        T off2 = T(0), d2 = T(0);
-#pragma unroll
-        for (int p = 0; p < N; p++) {
-            d2 = fma(a[p * N + p], a[p * N + p], d2);
-#pragma unroll
-            for (int q = p + 1; q < N; q++) off2 = fma(a[p * N + q], a[p * N + q], off2);
-        }
-        const bool done = !active || !(off2 > Lim<T>::eps * Lim<T>::eps * d2);
-        if (__all(done)) break;
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int q = p + 1; q < N; q++) {
-                T t, c, s;
-                const T apq = a[p * N + q];
-                jacobi_cs<T>(T(0.5) * (a[q * N + q] - a[p * N + p]), apq, t, c, s);
-                a[p * N + p] = fma(-t, apq, a[p * N + p]);
-                a[q * N + q] = fma(t, apq, a[q * N + q]);
-                a[p * N + q] = T(0);
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    if (k == p || k == q) continue;
-                    // entry (k, p) and (k, q) of the symmetric matrix, wherever the upper triangle keeps them
-                    T& xp = k < p ? a[k * N + p] : a[p * N + k];
-                    T& xq = k < q ? a[k * N + q] : a[q * N + k];
-                    const T vp = xp, vq = xq;
-                    xp = fma(c, vp, -(s * vq));
-                    xq = fma(s, vp, c * vq);
-                }
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) ev[i] = a[i * N + i];
 }
 
 // Symmetric eigenvalues by Householder tridiagonalisation + implicit QL with Wilkinson shifts and deflation, all in registers
@@ -873,48 +833,16 @@ __global__ void __launch_bounds__(64) k_degeneracy_scores_windows(const double* 
     scores_from_image<double, METRIC>(lds, pose + g0 * 6, base + lane, count, mask, out + g0, row, lane);
 }
 
-template <typename T, int N>
-void launch_degeneracy(int metric, dim3 grid, const T* m, const T* p, int count, int off, T* o) {
-#define VF_K6_CASE(M) case M: hipLaunchKernelGGL((k_degeneracy<T, N, M>), grid, dim3(64), 0, 0, m, p, count, off, o); break;
-    switch (metric) {
-        VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
-        VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
-        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
-        VF_K6_CASE(24)
-        default: break;
+// metric id -> its instantiation: f(std::integral_constant<int, M>{}) for M = metric; an id out of range calls nothing
+template <int M = 0, typename F>
+void with_metric(int metric, F&& f) {
+    if constexpr (M < N_METRICS) {
+        if (metric == M) f(std::integral_constant<int, M>{});
+        else with_metric<M + 1>(metric, f);
     }
-#undef VF_K6_CASE
 }
-
-template <typename T>
-void launch_degeneracy_scores(int metric, dim3 grid, const T* m, const T* p, int count, unsigned mask, T* o) {
-#define VF_K6_CASE(M) case M: hipLaunchKernelGGL((k_degeneracy_scores<T, M>), grid, dim3(64), 0, 0, m, p, count, mask, o); break;
-    switch (metric) {
-        VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
-        VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
-        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
-        VF_K6_CASE(24)
-        default: break;
-    }
-#undef VF_K6_CASE
-}
-void launch_degeneracy_scores_windows(int metric, dim3 grid, const double* m, const double* p, const int* range, int M, size_t row, unsigned mask,
-                                      double* o, hipStream_t st) {
-#define VF_K6_CASE(K) case K: hipLaunchKernelGGL((k_degeneracy_scores_windows<K>), grid, dim3(64), 0, st, m, p, range, M, row, mask, o); break;
-    switch (metric) {
-        VF_K6_CASE(0) VF_K6_CASE(1) VF_K6_CASE(2) VF_K6_CASE(3) VF_K6_CASE(4) VF_K6_CASE(5) VF_K6_CASE(6) VF_K6_CASE(7)
-        VF_K6_CASE(8) VF_K6_CASE(9) VF_K6_CASE(10) VF_K6_CASE(11) VF_K6_CASE(12) VF_K6_CASE(13) VF_K6_CASE(14) VF_K6_CASE(15)
-        VF_K6_CASE(16) VF_K6_CASE(17) VF_K6_CASE(18) VF_K6_CASE(19) VF_K6_CASE(20) VF_K6_CASE(21) VF_K6_CASE(22) VF_K6_CASE(23)
-        VF_K6_CASE(24)
-        default: break;
-    }
-#undef VF_K6_CASE
-}
-static_assert(N_METRICS == 25, "launch_degeneracy, launch_degeneracy_scores and launch_degeneracy_scores_windows list every metric");
+static_assert(N_METRICS == 25, "the metric ids of include/vilfusion.h (with_metric reaches every one of them)");
 static_assert(N_METRICS == vf::K6_METRICS && N_SUBSETS == vf::K6_SUBSETS, "what vf_engine_marginal_scores checks its arguments against");
-
-template <typename T>
-int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_max, void* o_cond, int reps, float* kernel_ms);
 
 // degerate_odometry_filter.cpp:29-47 (float32): hessian (row-major floats) copied into a
 // column-major Eigen matrix, rotation = block(3,3), translation = block(0,0), log(det)
@@ -949,116 +877,99 @@ int derr(int code, const char* fmt, ...) {
         if (_e != hipSuccess) return derr(VF_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-template <typename T>
-int run_batch(const void* mats, const void* pose, int count, int subset, int metric, void* out, int reps, float* kernel_ms) {
-    T *d_m = nullptr, *d_p = nullptr, *d_o = nullptr;
-    const size_t mb = (size_t)count * 36 * sizeof(T), pb = (size_t)count * 6 * sizeof(T), ob = (size_t)count * sizeof(T);
-    HIPCHK(hipMalloc((void**)&d_m, mb));
-    HIPCHK(hipMalloc((void**)&d_o, ob));
+struct Event {       // a timing event that goes with its scope
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+};
+
+// The batch entry points: upload `count` matrices (and poses, if given), launch(mats, poses, out) once and wait, time `reps`
+// further launches if asked to, download `rows` rows of `count` values in equal shares to the host arrays of `outs`.
+template <typename T, typename Launch>
+int run_batch(const void* mats, const void* pose, int count, int rows, std::initializer_list<void*> outs, int reps, float* kernel_ms, Launch launch) {
+    vf::DeviceBuf<T> d_m, d_p, d_o;
+    const size_t mb = (size_t)count * 36 * sizeof(T), pb = (size_t)count * 6 * sizeof(T), ob = (size_t)rows / outs.size() * count * sizeof(T);
+    HIPCHK(d_m.ensure(mb));
+    HIPCHK(d_o.ensure(ob * outs.size()));
     HIPCHK(hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice));
     if (pose) {
-        HIPCHK(hipMalloc((void**)&d_p, pb));
+        HIPCHK(d_p.ensure(pb));
         HIPCHK(hipMemcpy(d_p, pose, pb, hipMemcpyHostToDevice));
     }
-    const int off = subset_off(subset);
-    const dim3 grid((count + 63) / 64);
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    auto launch = [&]() {
-        if (subset == 0) launch_degeneracy<T, 6>(metric, grid, d_m, d_p, count, off, d_o);
-        else if (subset < 3) launch_degeneracy<T, 3>(metric, grid, d_m, d_p, count, off, d_o);
-        else launch_degeneracy<T, 1>(metric, grid, d_m, d_p, count, off, d_o);
-    };
-    launch();
+    launch(d_m.get(), d_p.get(), d_o.get());
     HIPCHK(hipDeviceSynchronize());
     if (kernel_ms && reps > 0) {
-        HIPCHK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; r++) launch();
-        HIPCHK(hipEventRecord(e1, 0));
-        HIPCHK(hipEventSynchronize(e1));
+        Event e0, e1;
+        HIPCHK(hipEventCreate(&e0.ev));
+        HIPCHK(hipEventCreate(&e1.ev));
+        HIPCHK(hipEventRecord(e0.ev, 0));
+        for (int r = 0; r < reps; r++) launch(d_m.get(), d_p.get(), d_o.get());
+        HIPCHK(hipEventRecord(e1.ev, 0));
+        HIPCHK(hipEventSynchronize(e1.ev));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(hipEventElapsedTime(&ms, e0.ev, e1.ev));
         *kernel_ms = ms / reps;
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
-    (void)hipFree(d_m); (void)hipFree(d_o);
-    if (d_p) (void)hipFree(d_p);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    const char* from = (const char*)d_o.get();
+    for (void* o : outs) {
+        HIPCHK(hipMemcpy(o, from, ob, hipMemcpyDeviceToHost));
+        from += ob;
+    }
     return VF_OK;
+}
+
+// f(std::integral_constant<int, N>{}) for the block size of a subset (subset_off)
+template <typename F>
+void with_block(int subset, F&& f) {
+    if (subset == 0) f(std::integral_constant<int, 6>{});
+    else if (subset < 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
+template <typename T>
+int run_metric(const void* mats, const void* pose, int count, int subset, int metric, void* out, int reps, float* kernel_ms) {
+    const int off = subset_off(subset);
+    const dim3 grid((count + 63) / 64);
+    return run_batch<T>(mats, pose, count, 1, {out}, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
+        with_block(subset, [&](auto N) {
+            with_metric(metric, [&](auto M) { hipLaunchKernelGGL((k_degeneracy<T, N(), M()>), grid, dim3(64), 0, 0, m, p, count, off, o); });
+        });
+    });
 }
 
 template <typename T>
 int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_max, void* o_cond, int reps, float* kernel_ms) {
-    T *d_m = nullptr, *d_o = nullptr;
-    const size_t mb = (size_t)count * 36 * sizeof(T), ob = (size_t)count * sizeof(T);
-    HIPCHK(hipMalloc((void**)&d_m, mb));
-    HIPCHK(hipMalloc((void**)&d_o, 3 * ob));
-    HIPCHK(hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice));
     const int off = subset_off(subset);
     const dim3 grid((count + 63) / 64);
-    auto launch = [&]() {
-        if (subset == 0) hipLaunchKernelGGL((k_degeneracy<T, 6, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
-        else if (subset < 3) hipLaunchKernelGGL((k_degeneracy<T, 3, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
-        else hipLaunchKernelGGL((k_degeneracy<T, 1, SPECTRUM>), grid, dim3(64), 0, 0, d_m, (const T*)nullptr, count, off, d_o, d_o + count, d_o + 2 * (size_t)count);
-    };
-    launch();
-    HIPCHK(hipDeviceSynchronize());
-    if (kernel_ms && reps > 0) {
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; r++) launch();
-        HIPCHK(hipEventRecord(e1, 0));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *kernel_ms = ms / reps;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(o_min, d_o, ob, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(o_max, d_o + count, ob, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(o_cond, d_o + 2 * (size_t)count, ob, hipMemcpyDeviceToHost));
-    (void)hipFree(d_m); (void)hipFree(d_o);
-    return VF_OK;
+    return run_batch<T>(mats, nullptr, count, 3, {o_min, o_max, o_cond}, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
+        with_block(subset, [&](auto N) {
+            hipLaunchKernelGGL((k_degeneracy<T, N(), SPECTRUM>), grid, dim3(64), 0, 0, m, p, count, off, o, o + count, o + 2 * (size_t)count);
+        });
+    });
 }
 
 template <typename T>
 int run_scores(const void* mats, const void* pose, int count, int metric, unsigned mask, void* out, int reps, float* kernel_ms) {
-    T *d_m = nullptr, *d_p = nullptr, *d_o = nullptr;
-    const int rows = __builtin_popcount(mask);
-    const size_t mb = (size_t)count * 36 * sizeof(T), pb = (size_t)count * 6 * sizeof(T), ob = (size_t)rows * count * sizeof(T);
-    HIPCHK(hipMalloc((void**)&d_m, mb));
-    HIPCHK(hipMalloc((void**)&d_o, ob));
-    HIPCHK(hipMemcpy(d_m, mats, mb, hipMemcpyHostToDevice));
-    if (pose) {
-        HIPCHK(hipMalloc((void**)&d_p, pb));
-        HIPCHK(hipMemcpy(d_p, pose, pb, hipMemcpyHostToDevice));
-    }
     const dim3 grid((count + 63) / 64);
-    auto launch = [&]() { launch_degeneracy_scores<T>(metric, grid, d_m, d_p, count, mask, d_o); };
-    launch();
-    HIPCHK(hipDeviceSynchronize());
-    if (kernel_ms && reps > 0) {
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; r++) launch();
-        HIPCHK(hipEventRecord(e1, 0));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *kernel_ms = ms / reps;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost));
-    (void)hipFree(d_m); (void)hipFree(d_o);
-    if (d_p) (void)hipFree(d_p);
+    return run_batch<T>(mats, pose, count, __builtin_popcount(mask), {out}, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
+        with_metric(metric, [&](auto M) { hipLaunchKernelGGL((k_degeneracy_scores<T, M()>), grid, dim3(64), 0, 0, m, p, count, mask, o); });
+    });
+}
+
+// What the batch entry points refuse alike, in this order; *run: there are matrices, and a device to take them to
+int check_batch(bool null_argument, int count, int metric, int dtype, bool has_pose, bool* run) {
+    *run = false;
+    if (null_argument || count < 0) return derr(VF_ERR_INVALID, "null argument");
+    if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
+    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
+    if (metric == KULLBACK_LEIBLER && !has_pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
+    if (count == 0) return VF_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    *run = true;
     return VF_OK;
 }
 
@@ -1068,7 +979,9 @@ int run_scores(const void* mats, const void* pose, int count, int metric, unsign
 namespace vf {
 void launch_degeneracy_scores_windows(int metric, unsigned mask, const double* mats, const double* pose, const int* range, int B, int M,
                                       double* out, hipStream_t s) {
-    ::launch_degeneracy_scores_windows(metric, dim3((M + 63) / 64, B), mats, pose, range, M, (size_t)B * M, mask, out, s);
+    with_metric(metric, [&](auto K) {
+        hipLaunchKernelGGL((k_degeneracy_scores_windows<K()>), dim3((M + 63) / 64, B), dim3(64), 0, s, mats, pose, range, M, (size_t)B * M, mask, out);
+    });
 }
 }  // namespace vf
 
@@ -1076,40 +989,27 @@ extern "C" {
 
 int vf_degeneracy_spectrum_batch(const void* mats, int count, int dtype, int subset, void* e_opt, void* max_eigen, void* condition_number,
                                  int reps, float* kernel_ms) {
-    if (!mats || !e_opt || !max_eigen || !condition_number || count < 0) return derr(VF_ERR_INVALID, "null argument");
+    bool run;
     if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
-    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
-    if (count == 0) return VF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    if (int rc = check_batch(!mats || !e_opt || !max_eigen || !condition_number, count, E_OPT, dtype, false, &run); rc || !run) return rc;
     return dtype == 0 ? run_spectrum<double>(mats, count, subset, e_opt, max_eigen, condition_number, reps, kernel_ms)
                       : run_spectrum<float>(mats, count, subset, e_opt, max_eigen, condition_number, reps, kernel_ms);
 }
 
 int vf_degeneracy_batch(const void* mats, const void* pose, int count, int dtype, int subset, int metric, void* out,
                         int reps, float* kernel_ms) {
-    if (!mats || !out || count < 0) return derr(VF_ERR_INVALID, "null argument");
-    if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
+    bool run;
     if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
-    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
-    if (metric == KULLBACK_LEIBLER && !pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
-    if (count == 0) return VF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
-    return dtype == 0 ? run_batch<double>(mats, pose, count, subset, metric, out, reps, kernel_ms)
-                      : run_batch<float>(mats, pose, count, subset, metric, out, reps, kernel_ms);
+    if (int rc = check_batch(!mats || !out, count, metric, dtype, pose != nullptr, &run); rc || !run) return rc;
+    return dtype == 0 ? run_metric<double>(mats, pose, count, subset, metric, out, reps, kernel_ms)
+                      : run_metric<float>(mats, pose, count, subset, metric, out, reps, kernel_ms);
 }
 
 int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, int dtype, int metric, unsigned subset_mask, void* out,
                                int reps, float* kernel_ms) {
-    if (!mats || !out || count < 0) return derr(VF_ERR_INVALID, "null argument");
-    if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
+    bool run;
     if (subset_mask == 0 || (subset_mask >> N_SUBSETS) != 0) return derr(VF_ERR_INVALID, "subset_mask 0x%x: bits 0 .. 8, at least one", subset_mask);
-    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
-    if (metric == KULLBACK_LEIBLER && !pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
-    if (count == 0) return VF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    if (int rc = check_batch(!mats || !out, count, metric, dtype, pose != nullptr, &run); rc || !run) return rc;
     return dtype == 0 ? run_scores<double>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms)
                       : run_scores<float>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms);
 }
@@ -1120,19 +1020,18 @@ int vf_dopt_filter_f32(const float* hessians, int count, float rot_thr, float tr
     if (count == 0) return VF_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
-    float *d_h = nullptr, *d_r = nullptr, *d_t = nullptr;
-    unsigned char* d_k = nullptr;
-    HIPCHK(hipMalloc((void**)&d_h, (size_t)count * 36 * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&d_r, count * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&d_t, count * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&d_k, count));
+    vf::DeviceBuf<float> d_h, d_r, d_t;
+    vf::DeviceBuf<unsigned char> d_k;
+    HIPCHK(d_h.ensure((size_t)count * 36 * sizeof(float)));
+    HIPCHK(d_r.ensure(count * sizeof(float)));
+    HIPCHK(d_t.ensure(count * sizeof(float)));
+    HIPCHK(d_k.ensure(count));
     HIPCHK(hipMemcpy(d_h, hessians, (size_t)count * 36 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dopt_filter, dim3((count + 255) / 256), dim3(256), 0, 0, d_h, count, rot_thr, trans_thr, d_r, d_t, d_k);
+    hipLaunchKernelGGL(k_dopt_filter, dim3((count + 255) / 256), dim3(256), 0, 0, d_h.get(), count, rot_thr, trans_thr, d_r.get(), d_t.get(), d_k.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(rot_dopt, d_r, count * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(trans_dopt, d_t, count * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(keep, d_k, count, hipMemcpyDeviceToHost));
-    (void)hipFree(d_h); (void)hipFree(d_r); (void)hipFree(d_t); (void)hipFree(d_k);
     return VF_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "../../include/vilfusion.h"
 #include "vf_kernels.hpp"
+#include "vf_device_buf.hpp"
 #include "vf_engine_memory.hpp"
 
 namespace {
@@ -79,8 +80,8 @@ struct EngineHandle {
     bool async_on = false, side_open = false;
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int* sticky_dev = nullptr;
-    vf::SolveResult* res_host = nullptr;
+    vf::DeviceBuf<int> sticky_dev;
+    vf::PinnedBuf<vf::SolveResult> res_host;
     long far_transported = 0, far_ended = 0, far_absorbed = 0;   // far factors moved on to the next keyframe when theirs left the window /
                                                                  // dropped without a marginalisation / absorbed into the marginal prior
     bool marg_since_drop = false;   // vf_engine_marginalize ran since the last vf_engine_drop_oldest (the GraphManager's call pair)
@@ -112,8 +113,10 @@ struct vf_engine : EngineHandle {
     }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<void*> allocs;
-    double* stage = nullptr;  // device staging buffer (AoS)
-    size_t stage_bytes = 0;
+    // What is made after creation -- on first use, or grown on demand -- owns itself (vf_device_buf.hpp): `delete` frees it, and
+    // vf_engine_grow moves it with the arrays, or leaves it with the handle, like every other member
+    vf::DeviceBuf<double> stage;  // device staging buffer (AoS)
+    int ensure_stage(size_t bytes) { HIPCHK(stage.ensure(bytes)); return VF_OK; }
     double* sigma_dev = nullptr;
     double sigma_host[15] = {0};    // what sigma_dev holds (vf_engine_slide uploads only a changed set)
     bool sigma_valid = false;
@@ -124,9 +127,9 @@ struct vf_engine : EngineHandle {
     // (SolveMemory::result_cached_for, until any other entry point runs) and costs no second synchronisation.
     int ensure_async() {          // the sticky words and the pinned result block (every engine may be asked for a vf_engine_read_result)
         if (res_host) return VF_OK;
-        HIPCHK(hipMalloc((void**)&sticky_dev, 2 * sizeof(int)));
+        HIPCHK(sticky_dev.ensure(2 * sizeof(int)));
         HIPCHK(hipMemsetAsync(sticky_dev, 0, 2 * sizeof(int), stream));
-        HIPCHK(hipHostMalloc((void**)&res_host, sizeof(vf::SolveResult), hipHostMallocDefault));
+        HIPCHK(res_host.ensure(sizeof(vf::SolveResult)));
         return VF_OK;
     }
     int ensure_side() {           // the second stream (hipStreamCreate costs 9 ms: only engines that stage asynchronously get one)
@@ -151,7 +154,7 @@ struct vf_engine : EngineHandle {
     bool async_far() const { return async_base() && x_used > 0; }
     // vf_engine_marginalize_ahead: the marginal prior the next vf_engine_marginalize will need, computed behind the solve that has
     // just ended (the linearisation it reads is final by then) into marg_stash (SolveMemory::stash_fits)
-    double* marg_stash = nullptr;
+    vf::DeviceBuf<double> marg_stash;
     // hybrid K4 (vf_kernels.hpp "View::gate"): buffers and chunk count of the partitioned form for a sweep engine, allocated
     // when the termination rule is first switched on
     bool hybrid = false;
@@ -202,43 +205,29 @@ struct vf_engine : EngineHandle {
         return VF_OK;
     }
     // grow-only scratch of vf_engine_preintegrate (the GraphManager calls it once per solve: no hipMalloc / hipFree there)
-    void* pre_buf = nullptr;
-    size_t pre_bytes = 0;
+    vf::DeviceBuf<char> pre_buf;
     int ensure_pre(size_t bytes) {
-        if (bytes <= pre_bytes) return VF_OK;
-        if (pre_buf) HIPCHK(hipFree(pre_buf));
-        pre_buf = nullptr;
-        pre_bytes = 0;
-        const size_t want = bytes < (1u << 16) ? (1u << 16) : bytes * 2;
-        HIPCHK(hipMalloc(&pre_buf, want));
-        pre_bytes = want;
+        HIPCHK(pre_buf.ensure(bytes, [](size_t b) { return b < (1u << 16) ? (size_t)1 << 16 : b * 2; }));
         return VF_OK;
     }
     // vf_engine_ingest_tail: pinned host staging (so the one host->device copy of an update is asynchronous), its device
     // twin, the events that time the copy and the kernel, and the sticky status word the kernel reports into
-    void* in_host = nullptr;
-    void* in_dev = nullptr;
-    size_t in_bytes = 0;
-    int* in_status = nullptr;
+    vf::PinnedBuf<char> in_host;
+    vf::DeviceBuf<char> in_dev;
+    vf::DeviceBuf<int> in_status;
     hipEvent_t in_ev[3] = {nullptr, nullptr, nullptr};
     bool in_pending = false;
     int ensure_ingest(size_t bytes) {
         if (!in_ev[0])
             for (auto& ev : in_ev) HIPCHK(hipEventCreate(&ev));
         if (!in_status) {
-            HIPCHK(hipMalloc((void**)&in_status, sizeof(int)));
+            HIPCHK(in_status.ensure(sizeof(int)));
             HIPCHK(hipMemsetAsync(in_status, 0, sizeof(int), stream));
         }
-        if (bytes <= in_bytes) return VF_OK;
-        if (in_pending) HIPCHK(hipEventSynchronize(in_ev[1]));
-        if (in_host) HIPCHK(hipHostFree(in_host));
-        if (in_dev) HIPCHK(hipFree(in_dev));
-        in_host = in_dev = nullptr;
-        in_bytes = 0;
-        const size_t want = bytes * 2;
-        HIPCHK(hipHostMalloc(&in_host, want, hipHostMallocDefault));
-        HIPCHK(hipMalloc(&in_dev, want));
-        in_bytes = want;
+        if (bytes <= in_host.bytes() && bytes <= in_dev.bytes()) return VF_OK;
+        if (in_pending) HIPCHK(hipEventSynchronize(in_ev[1]));       // (the copy out of the block about to go)
+        HIPCHK(in_host.ensure(bytes, vf::twice));
+        HIPCHK(in_dev.ensure(bytes, vf::twice));
         return VF_OK;
     }
     // far between factors (View::x_*): host mirror of how many slots are in use (the low-rank correction solves 6 right-hand
@@ -249,10 +238,9 @@ struct vf_engine : EngineHandle {
     std::vector<char> h_xdirty;                        // the device's copy of a window's list may differ from the host's (k_marginalize has
                                                        // struck out entries the host has not yet): vf_engine_set_extra_between must re-send
     std::vector<std::vector<double>> h_xrec;
-    double* x_gtmp = nullptr;
-    double* x_Z = nullptr;
+    vf::DeviceBuf<double> x_gtmp;
+    vf::DeviceBuf<double> x_Z;   // 6 columns of x_zstride for every slot in use; grown on demand, never beyond x_cap slots
     size_t x_zstride = 0;
-    int x_zslots = 0;          // slots x_Z holds columns for (6 columns each); grown on demand, never beyond x_cap
     int x_cap = VF_MAX_EXTRA;  // far factors a window may hold (vf_engine_opts.max_far_factors): the width of the device lists
     // the device lists are allocated once (they stay in `allocs`); a failure half way leaves what exists in place and a
     // later call picks up from there (no second allocation, nothing leaked)
@@ -298,16 +286,13 @@ struct vf_engine : EngineHandle {
         // (the others: room for the solution of the Woodbury system, handed from k_extra_combine to k_extra_apply)
         if (!v.far_scratch && (rc = alloc(&v.far_scratch, B * (x_cap > vf::MAX_EXTRA ? vf::FAR_SCRATCH : (size_t)64)))) return rc;
         x_zstride = (size_t)v.G * 15 + B + 64;
-        if (!x_gtmp) HIPCHK(hipMalloc((void**)&x_gtmp, x_zstride * sizeof(double)));
-        if (slots > x_zslots) {
+        HIPCHK(x_gtmp.ensure(x_zstride * sizeof(double)));
+        const size_t zbytes = 6 * (size_t)slots * x_zstride * sizeof(double);
+        if (zbytes > x_Z.bytes()) {
             // the solved columns of the low-rank correction: 6 increment-shaped columns per slot IN USE (one far factor in
             // one window of a 1024 x 1088 batch engine is 0.8 GB, not the 6.4 GB that VF_MAX_EXTRA slots would be)
-            double* z = nullptr;
             HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMalloc((void**)&z, 6 * (size_t)slots * x_zstride * sizeof(double)));
-            if (x_Z) (void)hipFree(x_Z);
-            x_Z = z;
-            x_zslots = slots;
+            HIPCHK(x_Z.ensure(zbytes));
         }
         return VF_OK;
     }
@@ -315,12 +300,12 @@ struct vf_engine : EngineHandle {
     // vf_engine_refine_begin and vf_engine_refine_end, and vf_engine_solve_local / _global work on (nres, z)
     vf::Refine rq{};
     bool rq_ready = false, refine_open = false;
-    int* rq_stop_host = nullptr;     // [B] pinned: the stop flags, read back between corrections (vf_engine_solve)
+    vf::PinnedBuf<int> rq_stop_host;     // [B] pinned: the stop flags, read back between corrections (vf_engine_solve)
     int ensure_refine() {
         if (rq_ready) return VF_OK;
         const size_t G = (size_t)v.G, B = (size_t)v.B;
         int rc;
-        if (!rq_stop_host) HIPCHK(hipHostMalloc((void**)&rq_stop_host, B * sizeof(int), hipHostMallocDefault));
+        HIPCHK(rq_stop_host.ensure(B * sizeof(int)));
         if ((rc = alloc(&rq.x, G * 15)) || (rc = alloc(&rq.p, G * 15)) || (rc = alloc(&rq.Ap, G * 15)) ||
             (rc = alloc(&rq.nres, G * 15 + 64)) || (rc = alloc(&rq.z, G * 15 + B)) || (rc = alloc(&rq.u_imu, G * 15)) ||
             (rc = alloc(&rq.u_btw, G * 6)) || (rc = alloc(&rq.u_pri, B * 15)) || (rc = alloc(&rq.rz, B)) ||
@@ -360,42 +345,27 @@ struct vf_engine : EngineHandle {
         return VF_OK;
     }
     // marginal covariances (engine/engine_marginals.inc): [G][SIG_SLOT] blocks + per-window failure flags, a zero lambda and
-    // all-ones `fresh` flags for the undamped factorisation, one allocation made by the first vf_engine_marginals; sig_lo /
-    // sig_hi: the ranges the blocks were computed for (SolveMemory::covariances_valid)
-    double* sig = nullptr;
-    double* sig_zero = nullptr;
-    int *sig_fail = nullptr, *sig_ones = nullptr;
-    long sig_G = 0;
+    // all-ones `fresh` flags for the undamped factorisation, one allocation made by the first vf_engine_marginals.  What of all
+    // this is there to be read is SolveMemory's to say (covariances_valid, pose_records_valid, score_rows); sig_lo / sig_hi: the
+    // ranges the blocks were computed for, read only behind covariances_valid()
+    vf::DeviceBuf<double> sig;
+    double* sig_zero() const { return sig + (size_t)v.G * vf::SIG_SLOT; }
+    int* sig_fail() const { return (int*)(sig_zero() + v.B); }
+    int* sig_ones() const { return sig_fail() + v.B; }
     std::vector<int> sig_lo, sig_hi;
     // vf_engine_marginals_ex with VF_MARGINALS_FAR: Z = A^-1 U and the m x m systems of a group of windows (vf::FarCov), allocated
     // on first use and grown when a later call needs more; FARCOV_BUDGET bounds it, more windows than fit are done in groups
-    double* fc_scratch = nullptr;
-    size_t fc_doubles = 0;
+    vf::DeviceBuf<double> fc_scratch;
     // VF_MARGINALS_POSE (kernels/kpose.inc): the pose marginals in nav_msgs order, their inverses and the poses, [G][36], [G][36] and
-    // [G][6] in one allocation made by the first call that carries the flag, with the range [B][2] each window's records are of;
-    // pm_on: the last vf_engine_marginals_ex carried it (with SolveMemory::covariances_valid: the records are there to be read)
-    double *pm_cov = nullptr, *pm_info = nullptr, *pm_pose = nullptr;
-    int* pm_range = nullptr;
-    long pm_G = 0;
-    bool pm_on = false;
-    bool pose_marginals_valid() const { return pm_on && pm_cov && pm_G == v.G && sig_G == v.G && mem.covariances_valid(); }
-    // vf_engine_marginal_scores: one row of G scores per subset asked for, grown on demand; what the last call computed (sc_rows_used
-    // = 0: nothing since the last vf_engine_marginals_ex)
-    double* sc = nullptr;
-    int sc_rows = 0, sc_rows_used = 0, sc_metric = -1;
-    unsigned sc_mask = 0;
-    long sc_G = 0;
+    // [G][6] in one allocation made by the first call that carries the flag, with the range [B][2] each window's records are of
+    vf::DeviceBuf<double> pm_cov;
+    double* pm_info() const { return pm_cov + (size_t)v.G * 36; }
+    double* pm_pose() const { return pm_cov + (size_t)v.G * 72; }
+    int* pm_range() const { return (int*)(pm_cov + (size_t)v.G * 78); }
+    // vf_engine_marginal_scores: one row of G scores per subset asked for, grown on demand
+    vf::DeviceBuf<double> sc;
     // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
     void swap_arrays(vf_engine& o) { std::swap(*this, o), std::swap<EngineHandle>(*this, o); }
-    int ensure_stage(size_t bytes) {
-        if (bytes <= stage_bytes) return VF_OK;
-        if (stage) HIPCHK(hipFree(stage));
-        stage = nullptr;
-        stage_bytes = 0;
-        HIPCHK(hipMalloc((void**)&stage, bytes));
-        stage_bytes = bytes;
-        return VF_OK;
-    }
 };
 
 Entry::Entry(vf_engine* e, Effect does, int flags) : engine(e) {

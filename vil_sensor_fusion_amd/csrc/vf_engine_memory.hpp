@@ -3,8 +3,9 @@
 //
 // Five things outlive a solve on the device and let the next call do less: the linearisation of the current states (warm
 // start: the next solve linearises only a tail), the panels and checkpoints of the incremental update, a marginal prior
-// computed ahead of time, the result block an adaptive solve has already read, and the covariance blocks.  Every entry point
-// of the engine says what it did through one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
+// computed ahead of time, the result block an adaptive solve has already read, and what the covariance calls left (the blocks,
+// the pose records, the scores: each only with the one before it).  Every entry point of the engine says what it did through
+// one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
 #pragma once
 
 #include <algorithm>
@@ -68,9 +69,9 @@ class SolveMemory {
         warm_ = ahead_valid_ = false;
     }
     // the window was compacted: the covariance blocks stay in the slots they were computed for
-    void compacted() { rewritten(), sig_valid_ = false; }
-    // the engine was grown: new arrays, nothing linearised in them yet
-    void grown() { rewritten(), slid_ = redo_ = 0; }
+    void compacted() { rewritten(), covariances_started(); }
+    // the engine was grown: new arrays, nothing linearised in them yet, no covariances
+    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0; }
     // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
     void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
     void stash_committed() { ahead_valid_ = false; }
@@ -83,7 +84,13 @@ class SolveMemory {
     }
     // an entry point ran: the cached result is void, unless the entry point leaves the result block alone
     void entry_ran(bool leaves_result) { res_cached_ = res_cached_ && leaves_result; }
-    void covariances_computed() { sig_valid_ = true; }
+    // vf_engine_marginals_ex is about to free or overwrite what the last one left: void from here on, whether or not it gets through
+    void covariances_started() { sig_valid_ = pose_valid_ = false, score_rows_ = 0; }
+    // ... it got through, with the pose records (VF_MARGINALS_POSE) or, as the plain vf_engine_marginals, without; scores are of the
+    // records of one call: none yet
+    void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, score_rows_ = 0; }
+    // vf_engine_marginal_scores left `rows` rows of scores (0: it is about to overwrite them)
+    void scores_computed(int rows) { score_rows_ = rows; }
 
     // ---- queries
     // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
@@ -97,6 +104,8 @@ class SolveMemory {
     bool stash_fits(int lo) const { return ahead_valid_ && ahead_lo_ == lo; }
     bool result_cached_for(int window, int slot, bool estimate) const { return res_cached_ && window == 0 && slot == res_slot_ && !estimate; }
     bool covariances_valid() const { return sig_valid_; }
+    bool pose_records_valid() const { return sig_valid_ && pose_valid_; }
+    int score_rows() const { return pose_records_valid() ? score_rows_ : 0; }
 
   private:
     bool behind_first(int w, int k, int lo) const { return one_window && w == 0 && k > lo; }
@@ -108,7 +117,8 @@ class SolveMemory {
     int ahead_lo_ = -1;
     bool res_cached_ = false;
     int res_slot_ = -1, res_carry_[2] = {0, 0};
-    bool sig_valid_ = false;
+    bool sig_valid_ = false, pose_valid_ = false;
+    int score_rows_ = 0;
 };
 
 }  // namespace vf
