@@ -317,6 +317,29 @@ int vf_engine_get_imu(vf_engine* e, int window, int k0, int n, double* rec190);
 int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* steps7, const vf_imu_params* p,
                           const int32_t* btw_a, const double* btw_rec28);
 int vf_engine_ingest_status(vf_engine* e, float* h2d_ms, float* k0_ms);
+/* IMU-rate prediction: for every window, the state its raw samples since the last keyframe hi[w]-1 lead to, and (flag) the
+ * covariance the graph itself would assign to it.  Packed as vf_engine_ingest_tail (step_off: [B+1] offsets, steps7: 7 doubles per
+ * step); a window may have no samples.  The samples are integrated as K0 integrates them, with the bias of that keyframe in the
+ * current buffer; the state follows by the prediction vf_engine_predict makes; the bias is carried over.  One pinned copy (a buffer
+ * of this call's own) and one launch on the engine's stream, no host synchronisation.
+ *   VF_PROPAGATE_COVARIANCE     Sigma+ = B^-1 (A Sigma_ii A^T + P) B^-T: P the preintegrated covariance of the samples, A and B the
+ *       unwhitened Jacobians of the combined-IMU factor at the predicted state (zero residual), Sigma_ii the keyframe's block left
+ *       by the last vf_engine_marginals_ex -- the marginal of a keyframe attached to the window by this factor alone.  Tangent order
+ *       of vf_engine_read_marginals, symmetric to the bit.  A window whose factorisation failed gets NaN (and a valid state).
+ *   VF_PROPAGATE_FROM_ESTIMATE  start from the trial buffer's state of the keyframe (reference-compat engines: the estimate,
+ *       as vf_engine_predict_from_estimate).
+ * Without samples a window's result is the keyframe's state and Sigma_ii, bit for bit.  The call writes B x (16 + 225) doubles in a
+ * buffer of its own, made by the first call, and nothing else: the engine's states, records, linearisations, LM state and what it
+ * remembers of the last solve are untouched.  VF_ERR_INVALID: unknown flags; the covariance flag without marginal covariances, or
+ * with ones that do not cover the last keyframe; a time-sharded engine.  VF_ERR_BAD_KEY: an empty window.  Never VF_ERR_CAPACITY. */
+#define VF_PROPAGATE_COVARIANCE 1u
+#define VF_PROPAGATE_FROM_ESTIMATE 2u
+int vf_engine_propagate_tail(vf_engine* e, const int32_t* step_off, const double* steps7, const vf_imu_params* p, unsigned flags);
+/* ... read back (synchronises); either pointer may be NULL.  VF_ERR_INVALID: no propagation since the engine was made or grown;
+ * cov225 when the last propagation did not carry VF_PROPAGATE_COVARIANCE. */
+int vf_engine_read_propagated(vf_engine* e, int window, double* state16, double* cov225);
+/* ... and the last call's copy / kernel times from HIP events (synchronises on the kernel's event) */
+int vf_engine_propagate_status(vf_engine* e, float* h2d_ms, float* kernel_ms);
 
 /* ---- hot-path stages (asynchronous on the engine's HIP stream) ---- */
 /* K1+K2+priors: residual + whitened Jacobian of every factor, at the current (which=0) or
@@ -727,6 +750,15 @@ int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
  * yet they are computed with VF_MARGINALS_POSE (and VF_MARGINALS_FAR under vf_graph_opts.far_covariance), then the scores
  * (vf_engine_marginal_scores); vf_solve and vf_set_initial_state void them.  Refusals and lock rule as vf_get_marginal_covariance. */
 int vf_get_degeneracy_scores(vf_graph* g, int source, int metric, unsigned subset_mask, uint64_t key0, int n, double* out);
+/* The state at `time`, between two solves: predicted from the last solved key through the steps of every queued, not yet solved
+ * IMU factor and then what vf_reserve_node(time) would cut from the IMU buffer at this moment -- which is not consumed
+ * (vf_engine_propagate_tail; reference_compat handles predict from the estimate).  cov225 (may be NULL): the propagated covariance,
+ * tangent order of vf_get_marginal_covariance; if the last solve has no covariances yet they are computed first, as
+ * vf_get_marginal_covariance does (vf_graph_opts.far_covariance is honoured, its refusals apply).  `time` equal to the last key's time
+ * with nothing queued gives the solved state and its marginal.  VF_ERR_INVALID: before the first successful solve; a queued factor
+ * is a ready-made record (vf_add_imu_factor); `time` precedes the last reserved key's time.  Takes the graph, buffer and state
+ * locks in vf_reserve_node's order: never call it from inside a callback. */
+int vf_predict_state(vf_graph* g, double time, double q[4], double t[3], double v[3], double bias[6], double cov225[225]);
 /* the callback of vf_set_callback plus the marginal covariance of the solved keyframe */
 typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
                                 const double bias[6], const double cov225[225]);

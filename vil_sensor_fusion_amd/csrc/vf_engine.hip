@@ -230,6 +230,14 @@ struct vf_engine : EngineHandle {
         HIPCHK(in_dev.ensure(bytes, vf::twice));
         return VF_OK;
     }
+    // vf_engine_propagate_tail (engine/engine_propagate.inc): its own pinned staging block and device twin (the ingest block may be in
+    // flight on asynchronous engines), the events that time the copy and the kernel, and the output [B][16 + 225], all made by the
+    // first call.  Whether the output holds anything is SolveMemory's to say (propagation_valid).
+    vf::PinnedBuf<char> prop_host;
+    vf::DeviceBuf<char> prop_dev;
+    vf::DeviceBuf<double> prop_out;
+    hipEvent_t prop_ev[3] = {nullptr, nullptr, nullptr};
+    bool prop_pending = false;
     // far between factors (View::x_*): host mirror of how many slots are in use (the low-rank correction solves 6 right-hand
     // sides per slot in use), the right-hand-side scratch and the solved columns Z
     int x_used = 0;
@@ -389,4 +397,5 @@ extern "C" {
 #include "engine/engine_window.inc"
 #include "engine/engine_read.inc"
 #include "engine/engine_marginals.inc"
+#include "engine/engine_propagate.inc"
 }  // extern "C"

@@ -4,7 +4,8 @@
 // Five things outlive a solve on the device and let the next call do less: the linearisation of the current states (warm
 // start: the next solve linearises only a tail), the panels and checkpoints of the incremental update, a marginal prior
 // computed ahead of time, the result block an adaptive solve has already read, and what the covariance calls left (the blocks,
-// the pose records, the scores: each only with the one before it).  Every entry point of the engine says what it did through
+// the pose records, the scores: each only with the one before it).  A sixth outlives the arrays' next solve too: the last IMU-rate
+// propagation (vf_engine_propagate_tail), which only a grown engine loses.  Every entry point of the engine says what it did through
 // one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
 #pragma once
 
@@ -71,7 +72,7 @@ class SolveMemory {
     // the window was compacted: the covariance blocks stay in the slots they were computed for
     void compacted() { rewritten(), covariances_started(); }
     // the engine was grown: new arrays, nothing linearised in them yet, no covariances
-    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0; }
+    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = false; }
     // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
     void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
     void stash_committed() { ahead_valid_ = false; }
@@ -91,6 +92,9 @@ class SolveMemory {
     void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, score_rows_ = 0; }
     // vf_engine_marginal_scores left `rows` rows of scores (0: it is about to overwrite them)
     void scores_computed(int rows) { score_rows_ = rows; }
+    // vf_engine_propagate_tail left a propagation in its own buffer, with or without the covariance.  It is of the arrays it was
+    // enqueued on: nothing but grown() voids it
+    void propagated(bool cov) { prop_valid_ = true, prop_cov_ = cov; }
 
     // ---- queries
     // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
@@ -106,6 +110,8 @@ class SolveMemory {
     bool covariances_valid() const { return sig_valid_; }
     bool pose_records_valid() const { return sig_valid_ && pose_valid_; }
     int score_rows() const { return pose_records_valid() ? score_rows_ : 0; }
+    bool propagation_valid() const { return prop_valid_; }
+    bool propagated_covariance_valid() const { return prop_valid_ && prop_cov_; }
 
   private:
     bool behind_first(int w, int k, int lo) const { return one_window && w == 0 && k > lo; }
@@ -119,6 +125,7 @@ class SolveMemory {
     int res_slot_ = -1, res_carry_[2] = {0, 0};
     bool sig_valid_ = false, pose_valid_ = false;
     int score_rows_ = 0;
+    bool prop_valid_ = false, prop_cov_ = false;
 };
 
 }  // namespace vf

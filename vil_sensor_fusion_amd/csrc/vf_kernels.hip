@@ -16,6 +16,7 @@
 //   K-marg k_marginalize    fixed-lag marginalisation of the oldest keyframe into a dense prior
 //   K5 k_retract, k_decide  x (+) delta, cost reduction, LM accept/reject
 //   a2 k_predict, k_slide   PreintegrationBase::predict initial values (GraphManager.cpp:152-160)
+//   k_propagate             the state between two solves at IMU rate, with its propagated covariance (no reference code)
 //
 // Mapping: one lane per factor / keyframe for K1-K3,K5 (HBM-bound, coalesced AoSoA tiles of 64:
 // lane l of a wave reads word l of a 512-byte field row), one 64-lane wave per window or per
@@ -135,4 +136,5 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
 #include "kernels/k4_selinv.inc"
 #include "kernels/k4_selinv_far.inc"
 #include "kernels/kpose.inc"
+#include "kernels/kprop.inc"
 }  // namespace vf

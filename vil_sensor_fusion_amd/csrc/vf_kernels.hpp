@@ -337,6 +337,11 @@ void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStre
 // ([G][36]) and the pose as (x, y, z, roll, pitch, yaw) ([G][6]); pm_range: [B][2], the range [lo, hi) each window's records are of
 void launch_pose_marginals(const View& v, const int* failed, const double* sig, double* pm_cov, double* pm_info, double* pm_pose,
                            int* pm_range, hipStream_t s);
+// IMU-rate prediction (kernels/kprop.inc): for every window, the samples steps[off[w] .. off[w + 1]) integrated from its last keyframe
+// (current buffer, or the trial buffer's: from_estimate), and with_cov the covariance propagated from that keyframe's block of sig;
+// out: [B][16 + 225]
+void launch_propagate(const View& v, const int* off, const double* steps, const ImuCov& prm, int with_cov, int from_estimate,
+                      const double* sig, const int* sig_failed, double* out, hipStream_t s);
 constexpr int K6_METRICS = 25, K6_SUBSETS = 9;     // metric ids 0 .. 24 (VF_METRIC_*) and subset ids 0 .. 8 (VF_SUBSET_*) of vf_degeneracy.hip
 // K6 over those records (vf_degeneracy.hip, k_degeneracy_scores_windows): one metric on the subsets of `mask`, every window's range a
 // series of its own; mats / pose: [B M][36] / [B M][6], range: [B][2], out: one row of B M values per subset in the mask

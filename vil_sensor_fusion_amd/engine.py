@@ -185,6 +185,33 @@ class Engine:
         check(self._l.vf_engine_ingest_status(self._h, C.byref(h), C.byref(k)))
         return h.value, k.value
 
+    def propagate_tail(self, step_off, steps, imu_cov, covariance=False, from_estimate=False):
+        """IMU-rate prediction for all windows (vf_engine_propagate_tail): window w's state after the raw samples
+        steps[step_off[w]:step_off[w+1]] that follow its last keyframe (none: that keyframe), and with covariance=True the
+        covariance propagated from that keyframe's marginal (marginals() first).  Writes a buffer of its own, nothing else.
+        Asynchronous; read with read_propagated."""
+        off = np.ascontiguousarray(step_off, dtype=np.int32)
+        st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
+        assert off.size == self.windows + 1 and st.shape[0] >= off[-1]
+        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
+                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
+        flags = (_lib.PROPAGATE_COVARIANCE if covariance else 0) | (_lib.PROPAGATE_FROM_ESTIMATE if from_estimate else 0)
+        check(self._l.vf_engine_propagate_tail(self._h, _i(off), _d(st) if st.size else None, C.byref(p), flags))
+
+    def read_propagated(self, window, covariance=False):
+        """the state (16,) the last propagate_tail left for `window`; with covariance=True also its (15, 15) covariance, tangent
+        order of read_marginals.  Synchronises."""
+        st = np.zeros(16)
+        cov = np.zeros((15, 15)) if covariance else None
+        check(self._l.vf_engine_read_propagated(self._h, window, _d(st), _d(cov) if covariance else None))
+        return (st, cov) if covariance else st
+
+    def propagate_status(self):
+        """waits for the last propagate_tail, returns (h2d_ms, kernel_ms) of that call"""
+        h, k = C.c_float(), C.c_float()
+        check(self._l.vf_engine_propagate_status(self._h, C.byref(h), C.byref(k)))
+        return h.value, k.value
+
     def get_imu(self, window, k0, n):
         r = np.zeros((n, IMU_RECORD))
         check(self._l.vf_engine_get_imu(self._h, window, k0, n, _d(r)))

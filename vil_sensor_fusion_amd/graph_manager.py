@@ -148,6 +148,16 @@ class GraphManager:
         check(self._l.vf_get_marginal_covariance(self._h, C.c_uint64(key), _d(cov)))
         return cov
 
+    def predict(self, time, covariance=False):
+        """The state at `time`, between two solves (vf_predict_state): ((q_wxyz, t), v, bias) predicted from the last solved key
+        through the queued IMU factors' steps and what reserveNode(time) would cut from the IMU buffer now, which is not
+        consumed; with covariance=True also the propagated 15x15 covariance (tangent order of marginalCovariance; computes the
+        solve's covariances first if there are none yet).  Not from inside a callback."""
+        q, t, v, b = np.zeros(4), np.zeros(3), np.zeros(3), np.zeros(6)
+        cov = np.zeros((15, 15)) if covariance else None
+        check(self._l.vf_predict_state(self._h, C.c_double(time), _d(q), _d(t), _d(v), _d(b), _d(cov) if covariance else None))
+        return ((q, t), v, b, cov) if covariance else ((q, t), v, b)
+
     def degeneracy_scores(self, metric, subsets=("all", "trans", "rot"), information=False, key0=None, n=None):
         """One degeneracy metric (a name of degeneracy.ALL_METRICS) on `subsets` of the nav_msgs pose covariance (or,
         information=True, its inverse) of the solved keys key0 .. key0+n-1, computed on the device from the covariances of the

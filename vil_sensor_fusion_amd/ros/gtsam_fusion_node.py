@@ -13,7 +13,9 @@ solver/capacity (default lag + 192, or 4096 initial slots when lag = 0), solver/
 solver/abs_tol (LM termination, default 1e-5 / 1e-5 = gtsam's LevenbergMarquardtParams; 0 / 0 = always `iterations` trials),
 solver/device, solver/initial_state (16 doubles q t v bias: the anchor X(0), V(0), B(0) and the means of their priors; default =
 the reference's identity / at rest, GraphManager.cpp:20-35), reference_compat (poseDiff quirk), noise_order_compat
-(constant-covariance order quirk; both default to true = what the reference does).
+(constant-covariance order quirk; both default to true = what the reference does), publish_imu_rate (default
+false; true: every IMU message after the first solve also publishes the state predicted at its stamp, with the propagated
+covariance, as nav_msgs/Odometry on ~odometry_imu -- GraphManager.predict; ~odometry and TF stay as they are).
 NOTE the default solver/lag = 1000 is a deviation: the reference smooths an unbounded iSAM2 graph (= solver/lag 0 here).
 
 Threading: roscpp's ros::spin() runs every callback of the reference node on ONE thread (gtsam_fusion_node.cpp:101).
@@ -100,6 +102,8 @@ class FusionNode:
             self.graph.addCovarianceCallback(self.publish_with_covariance)
         else:
             self.graph.addOptimizationCallback(self.publish)                             # :64
+        # ~publish_imu_rate (no reference twin; default false: nothing more is advertised or published)
+        self.pub_imu = rospy.Publisher("~odometry_imu", msgs.Odometry, queue_size=1) if bool(P("publish_imu_rate", False)) else None
 
     def _serialised(self, fn):
         """fn under the node's lock.  VF_ERR_CAPACITY from a callback (no keyframe slot left with solver/capacity fixed, or a
@@ -127,6 +131,21 @@ class FusionNode:
     def imu_callback(self, m):                                                           # ImuManagerRos.cpp:38-52
         a, w = m.linear_acceleration, m.angular_velocity
         self.graph.addIMUMeasurement(m.header.stamp.to_sec(), [a.x, a.y, a.z], [w.x, w.y, w.z])
+        if self.pub_imu is not None:
+            self.publish_imu_rate(m.header.stamp.to_sec())
+
+    def publish_imu_rate(self, time):
+        """the state predicted at `time` from the last solved key, with its propagated covariance, on ~odometry_imu; nothing before
+        the first solve, or for a message older than the last reserved key (VF_ERR_INVALID)"""
+        from .._lib import VilFusionError
+        from ..covariance import ros_pose_covariance
+        try:
+            (q, p), v, _bias, cov15 = self.graph.predict(time, covariance=True)
+        except VilFusionError as exc:
+            if exc.code != -1:
+                raise
+            return
+        self.pub_imu.publish(self._odometry(time, q, p, v, ros_pose_covariance(q, cov15)))
 
     def publish_with_covariance(self, time, q, p, v, bias, cov15):
         """publish() with pose.covariance / twist.covariance from the keyframe's marginal covariance (covariance.py)"""
@@ -134,7 +153,7 @@ class FusionNode:
         pose36, twist36 = ros_pose_covariance(q, cov15)
         self.publish(time, q, p, v, bias, covariance=(pose36, twist36))
 
-    def publish(self, time, q, p, v, bias, covariance=None):                             # gtsam_fusion_node.cpp:64-98
+    def _odometry(self, time, q, p, v, covariance=None):
         stamp = self.rospy.Time.from_sec(time)
         o = self.msgs.Odometry()
         if covariance is not None:
@@ -145,7 +164,11 @@ class FusionNode:
         (o.pose.pose.orientation.w, o.pose.pose.orientation.x, o.pose.pose.orientation.y,
          o.pose.pose.orientation.z) = (float(x) for x in q)
         o.twist.twist.linear.x, o.twist.twist.linear.y, o.twist.twist.linear.z = (float(x) for x in v)
-        self.pub.publish(o)
+        return o
+
+    def publish(self, time, q, p, v, bias, covariance=None):                             # gtsam_fusion_node.cpp:64-98
+        stamp = self.rospy.Time.from_sec(time)
+        self.pub.publish(self._odometry(time, q, p, v, covariance))
         t = self.msgs.TransformStamped()
         t.header.stamp, t.header.frame_id, t.child_frame_id = stamp, self.static_frame, self.odom_frame
         t.transform.translation.x, t.transform.translation.y, t.transform.translation.z = (float(x) for x in p)
