@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage: tools/build_variant.sh <name> [-DFLAG ...]   -> tools/variants/libvilfusion_<name>.so
 # Builds vf_kernels.hip with extra defines against the current objects of the other translation
-# units; used to A/B tuning parameters on the GPU box (copy the variant over libvilfusion.so).
+# units.  The defines the kernels take: -DVF_RING_WITHHOLD, -DVF_ASM2_ROLES=2 (test builds), -DVF_SOLVE_STAMPS; a variant of edited
+# sources is A/B-ed on the GPU box the same way (copy it over libvilfusion.so).
 set -e
 name=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)

@@ -3,12 +3,7 @@
 // included from there, inside namespace vf, never compiled by itself.
 // ------------------------------------------------------------------------------------ K1
 // Algorithmic traffic per factor: 222 doubles in (2 states x 16, record 190), 465 out.
-#ifndef VF_K1_BLOCK
-#define VF_K1_BLOCK 256
-#endif
-#ifndef VF_K1_WAVES
-#define VF_K1_WAVES 1
-#endif
+constexpr int K1_BLOCK = 256, K1_WAVES = 1;     // launch bounds of the linearisation kernels: threads per block, waves per execution unit
 VF_DI const double* jtile_ptr(const double* base, long gk) { return base + (size_t)(gk >> JT_LOG) * JT_STRIDE; }
 // entry (row, col) of the Jacobian of the factor in slot gk of a J stream buffer (0 for a structural zero)
 VF_DI double jstream_entry(const double* jbuf, long gk, int row, int col) {
@@ -25,10 +20,10 @@ VF_DI double jstream_entry(const double* jbuf, long gk, int row, int col) {
 // `jac` = false (time-sharded windows, factors this rank does not assemble): residual only.
 struct HbmSink {
     // The 9x6 bias Jacobians of the record are used twice (bias-corrected delta, bias columns of J) and the second read
-    // misses L2 (18 % excess fetch traffic in the PMC counters).  Keeping them in registers (keep_h = true: 352 -> 406)
-    // removes that traffic (2.15 -> 1.71 GB read per launch) and makes K1 SLOWER, 0.80 -> 0.855 ms: with one wave per SIMD
-    // the kernel is paced by how early its first compute can start, not by its byte count.  Measured, left off.
-    static constexpr bool keep_h = false;
+    // misses L2 (18 % excess fetch traffic in the PMC counters).  Keeping them in registers (352 -> 406) removed that
+    // traffic (2.15 -> 1.71 GB read per launch) and made K1 SLOWER, 0.80 -> 0.855 ms: with one wave per SIMD the kernel is
+    // paced by how early its first compute can start, not by its byte count.  Measured, not kept:
+    // the core reads them where it uses them, IN(16 + i).
     double* out_r;      // imu_r row of this factor (+ a * TILE)
     double* slot;       // imu_j: tile base + 2 * slot
     bool jac;
@@ -54,19 +49,14 @@ struct HbmSink {
 constexpr int LJ_R = 2 * JS_PAIRS, LJ_ZERO = LJ_R + 15;
 constexpr int LJS = 310;        // LDS stride of one factor (even: the staging writes are 16-byte; 620 dwords = 12 mod 32 banks: the 8 slots of a pair hit 8 different bank groups)
 // CombinedImuFactor: residual and whitened 15x30 Jacobian of the factor in slot gk, at the states of buffer b.
-template <class Sink>
-__device__ __forceinline__ void linearize_imu_core(const View& v, const int b, const long gk, Sink& sink) {
+__device__ __forceinline__ void linearize_imu_core(const View& v, const int b, const long gk, HbmSink& sink) {
     const double* __restrict__ in = v.imu_in + (size_t)(gk >> 6) * IMU_IN * TILE + (gk & 63);
-#ifdef VF_K1_NTLOAD
-#define IN(f) __builtin_nontemporal_load(in + (size_t)(f) * TILE)
-#else
 #define IN(f) in[(size_t)(f) * TILE]
-#endif
     // the square-root information (120 of the 222 input words, read once) non-temporal: more of the bias Jacobians, which
     // are read twice, survive in L2 until their second use (PMC: 2.15 -> 2.00 GB read per launch; time unchanged)
 #define INR(f) __builtin_nontemporal_load(in + (size_t)(f) * TILE)
-    struct RRef { Sink& s; int a; VF_DI void operator=(double x) const { s.r(a, x); } };
-    struct JRef { Sink& s; int row, col; VF_DI void operator=(double x) const { s.j(row, col, x); } };
+    struct RRef { HbmSink& s; int a; VF_DI void operator=(double x) const { s.r(a, x); } };
+    struct JRef { HbmSink& s; int row, col; VF_DI void operator=(double x) const { s.j(row, col, x); } };
 #define OUT(f) (RRef{sink, (f)})
 #define JOUT(r, c) (JRef{sink, (r), (c)})
 
@@ -74,23 +64,17 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
     const double dt = IN(0);
     const V3 dba = si.ba - v3(IN(10), IN(11), IN(12));
     const V3 dbg = si.bg - v3(IN(13), IN(14), IN(15));
-    double Hb[54];
-    if constexpr (Sink::keep_h) {
-#pragma unroll
-        for (int i = 0; i < 54; i++) Hb[i] = IN(16 + i);
-    }
-#define HB(i) (Sink::keep_h ? Hb[i] : IN(16 + (i)))
     // bias-corrected preintegrated delta: d + H (b_i - bhat)   (biasCorrectedDelta)
     double xt[9];
 #pragma unroll
     for (int r = 0; r < 9; r++) {
         double s = IN(1 + r);
-        s = fma(HB(r * 6 + 0), dba.x, s);
-        s = fma(HB(r * 6 + 1), dba.y, s);
-        s = fma(HB(r * 6 + 2), dba.z, s);
-        s = fma(HB(r * 6 + 3), dbg.x, s);
-        s = fma(HB(r * 6 + 4), dbg.y, s);
-        s = fma(HB(r * 6 + 5), dbg.z, s);
+        s = fma(IN(16 + r * 6 + 0), dba.x, s);
+        s = fma(IN(16 + r * 6 + 1), dba.y, s);
+        s = fma(IN(16 + r * 6 + 2), dba.z, s);
+        s = fma(IN(16 + r * 6 + 3), dbg.x, s);
+        s = fma(IN(16 + r * 6 + 4), dbg.y, s);
+        s = fma(IN(16 + r * 6 + 5), dbg.z, s);
         xt[r] = s;
     }
     const V3 tht = v3(xt[0], xt[1], xt[2]), pt = v3(xt[3], xt[4], xt[5]), vt = v3(xt[6], xt[7], xt[8]);
@@ -191,9 +175,9 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
         double Rc[15];
 #pragma unroll
         for (int a = 0; a < 15; a++) Rc[a] = (a < n_rc) ? INR(70 + off15(a) + (9 + c - a)) : 0.0;
-        const V3 hth = v3(HB(0 * 6 + c), HB(1 * 6 + c), HB(2 * 6 + c));
-        const V3 hp = v3(HB(3 * 6 + c), HB(4 * 6 + c), HB(5 * 6 + c));
-        const V3 hv = v3(HB(6 * 6 + c), HB(7 * 6 + c), HB(8 * 6 + c));
+        const V3 hth = v3(IN(16 + 0 * 6 + c), IN(16 + 1 * 6 + c), IN(16 + 2 * 6 + c));
+        const V3 hp = v3(IN(16 + 3 * 6 + c), IN(16 + 4 * 6 + c), IN(16 + 5 * 6 + c));
+        const V3 hv = v3(IN(16 + 6 * 6 + c), IN(16 + 7 * 6 + c), IN(16 + 8 * 6 + c));
         const V3 u0 = mul(M5, hth), u1 = mul(Rji, hp), u2 = mul(Rji, hv);
         u[0] = u0.x; u[1] = u0.y; u[2] = u0.z; u[3] = u1.x; u[4] = u1.y; u[5] = u1.z; u[6] = u2.x; u[7] = u2.y; u[8] = u2.z;
         white9<0, 9>(R, u, o);
@@ -212,7 +196,6 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
     for (int a = 0; a < 15; a++) OUT(a) = rw[a];
 #undef IN
 #undef INR
-#undef HB
 #undef OUT
 #undef JOUT
 }
@@ -241,8 +224,8 @@ __device__ __forceinline__ void linearize_imu_factor(const View& v, int which, c
 
 // ------------------------------------------------------------------------------------ K2
 // Algorithmic traffic per factor: 42 doubles in (2 poses x 7, record 28), 78 out.
-__global__ void __launch_bounds__(VF_K1_BLOCK, VF_K1_WAVES) k_linearize_imu(View v, int which) {
-    linearize_imu_factor<false>(v, which, (long)blockIdx.x * VF_K1_BLOCK + threadIdx.x);
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_imu(View v, int which) {
+    linearize_imu_factor<false>(v, which, (long)blockIdx.x * K1_BLOCK + threadIdx.x);
 }
 
 // BetweenFactor<Pose3> between the keyframes in slots ga -> gk at the states of buffer b: whitened residual (6) and

@@ -78,9 +78,6 @@ __device__ __forceinline__ void linearize_prior_window(const View& v, int which,
         out[15 + (6 + i) * 15 + 6 + i] = 1.0 / sig[6 + i];
     }
 }
-__global__ void __launch_bounds__(64) k_linearize_prior(View v, int which) {   // launched with 64-lane blocks (launch.inc)
-    linearize_prior_window(v, which, blockIdx.x * blockDim.x + threadIdx.x);
-}
 // K2 + K2b in one launch (large batches): the prior linearisations are one lane per window, i.e. a handful of waves
 // running an 80 us latency chain; as the first workgroups of K2's grid they hide behind the between factors
 __global__ void __launch_bounds__(256) k_linearize_between_prior(View v, int which, int nb_pri) {
@@ -94,11 +91,11 @@ __global__ void __launch_bounds__(256) k_linearize_between_prior(View v, int whi
 // batches they stay separate (K2 would inherit K1's register footprint here).
 // (SH: the form time-sharded windows use, whatever the batch size)
 template <bool SH>
-__global__ void __launch_bounds__(VF_K1_BLOCK, VF_K1_WAVES) k_linearize_all(View v, int which, int nb_imu, int nb_btw) {
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_all(View v, int which, int nb_imu, int nb_btw) {
     const int bx = blockIdx.x;
-    if (bx < nb_imu) linearize_imu_factor<SH>(v, which, (long)bx * VF_K1_BLOCK + threadIdx.x);
-    else if (bx < nb_imu + nb_btw) linearize_between_factor<SH>(v, which, (long)(bx - nb_imu) * VF_K1_BLOCK + threadIdx.x);
-    else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * VF_K1_BLOCK + (int)threadIdx.x);
+    if (bx < nb_imu) linearize_imu_factor<SH>(v, which, (long)bx * K1_BLOCK + threadIdx.x);
+    else if (bx < nb_imu + nb_btw) linearize_between_factor<SH>(v, which, (long)(bx - nb_imu) * K1_BLOCK + threadIdx.x);
+    else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * K1_BLOCK + (int)threadIdx.x);
 }
 
 // Warm start of a fixed-lag update (vf_engine_slide directly after a solve): the linearisation of every factor that was
@@ -106,7 +103,7 @@ __global__ void __launch_bounds__(VF_K1_BLOCK, VF_K1_WAVES) k_linearize_all(View
 // rejected one left both alone), so only the factors of the `nslid` appended keyframes and the priors (the marginal prior
 // has just changed) are linearised.  H and g are then stale only at the two ends of a window whose last trial was
 // rejected: fresh[w] = 1 + nslid tells k_assemble to redo just those tiles (fresh[w] = 1: all of them).
-__global__ void __launch_bounds__(VF_K1_BLOCK, VF_K1_WAVES) k_linearize_tail(View v, int nslid) {
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_tail(View v, int nslid) {
     const int bx = blockIdx.x, t = threadIdx.x;
     if (bx < v.B) {
         if (t < nslid) linearize_imu_factor<false>(v, 0, (long)bx * v.M + v.hi[bx] - 1 - t);

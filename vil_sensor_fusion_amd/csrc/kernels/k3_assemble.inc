@@ -20,12 +20,6 @@ __host__ __device__ constexpr bool imu_field_is_zero(int f) {
     if (c < 18) return r >= 9 || (c >= 3 && c < 6 && r >= 6) || (c >= 12 && c < 15 && r > 3 + (c - 12));
     return r >= 10 + (c - 18) % 6;
 }
-#ifndef VF_K3_AT
-#define VF_K3_AT (1 << VF_JT_LOG)
-#endif
-#ifndef VF_K3_NT
-#define VF_K3_NT 256
-#endif
 // bit b of word w: field 32 w + b of a factor's (r | J) record exists and is not a structural zero
 __host__ __device__ constexpr unsigned imu_nz_word(int w) {
     unsigned m = 0;
@@ -35,8 +29,8 @@ __host__ __device__ constexpr unsigned imu_nz_word(int w) {
     }
     return m;
 }
-constexpr int AT = VF_K3_AT;    // keyframes per block
-constexpr int K3_NT = VF_K3_NT; // threads per block
+constexpr int AT = JT;         // keyframes per block (one tile of the J stream)
+constexpr int K3_NT = 256;     // threads per block
 constexpr int K3_KPW = AT / (K3_NT / 64);   // keyframes per wave
 static_assert(K3_KPW * (K3_NT / 64) == AT && K3_NT % AT == 0, "K3 tiling");
 constexpr int LBS = 79;         // LDS stride of one between linearisation (78 + pad), odd
@@ -231,10 +225,7 @@ __device__ __forceinline__ void assemble_tile(const View& v, const double* __res
 
 // Four waves per SIMD (128 VGPRs) = four workgroups per CU, which is also what the 40 KB of LDS allow: 2.23 -> 1.98 ms once
 // the staging code had come down to 132 VGPRs (at 176 it spilled and lost).
-#ifndef VF_K3_WPE
-#define VF_K3_WPE 4
-#endif
-__attribute__((amdgpu_waves_per_eu(VF_K3_WPE, VF_K3_WPE)))
+__attribute__((amdgpu_waves_per_eu(4, 4)))
 __global__ void __launch_bounds__(K3_NT) k_assemble(View v) {
     __shared__ __attribute__((aligned(16))) double LJ[(AT + 1) * LJS];
     __shared__ double LB[(AT + 3) * LBS];

@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(128) k_band_forward_asm2(View v, int w0) {
     // balanced, 3.10-3.20 ms not).  Which SIMDs the two waves of a workgroup land on follows the dispatcher's round-robin state,
     // i.e. whatever the PREVIOUS kernel left behind: after k_decide the four workgroups of a CU come out as (0, 2), (1, 3), (2, 1),
     // (3, 0) and "wave 0 eliminates" is balanced; after the gated-off K3 launch of the hybrid solve, or in another process, it
-    // is not (tools/hybrid_full_probe.py, trace_context.py; a placement kernel in front moved the step between 23.3 and 26.7 ms).
+    // is not (tools/archive/trace_context.py; a placement kernel in front moved the step between 23.3 and 26.7 ms).
     // So the workgroups of a CU agree among themselves: each claims, in a per-CU bit mask (View::place, cleared by the launch),
     // the SIMD of its wave 0 for its eliminator, or -- that one taken -- the SIMD of its wave 1, and swaps its roles then.  The
     // waves of a CU's workgroups form cycles over its four SIMDs (two waves each), so the greedy claim ends with one eliminator
@@ -45,7 +45,6 @@ __global__ void __launch_bounds__(128) k_band_forward_asm2(View v, int w0) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (threadIdx.x < 4) S[AS_FLAGS + threadIdx.x] = threadIdx.x < 2 ? -1.0 : 0.0;
     int swapped = 0;
-#if VF_ASM2_ROLES
     {
         const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));      // HW_ID: simd [5:4], cu [11:8], sh [12], se [15:13]
         const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));     // XCC_ID [3:0]
@@ -68,15 +67,11 @@ __global__ void __launch_bounds__(128) k_band_forward_asm2(View v, int w0) {
         swapped = __builtin_amdgcn_readfirstlane((int)S[AS_FLAGS + 6]);
         if (VF_ASM2_ROLES == 2) swapped = 1;          // (test build: wave 1 eliminates in every workgroup)
     }
-#else
-    __syncthreads();
-#endif
     const bool eliminator = (wave == 0) != (swapped != 0);
-#if VF_ASM2_PRIO
     // Issue priority to the eliminator: its steps are the critical path, the assembler has 40 % slack, and the two share one
-    // SIMD's float64 units (DESIGN.md 7.16: solve 3.66 -> 3.50 ms at 1 024 windows; priority to the assembler: 3.63)
-    if (eliminator == (VF_ASM2_PRIO == 1)) __builtin_amdgcn_s_setprio(3);
-#endif
+    // SIMD's float64 units (DESIGN.md 7.16: solve 3.66 -> 3.50 ms at 1 024 windows; priority to the assembler instead was
+    // 3.63, to neither 3.66)
+    if (eliminator) __builtin_amdgcn_s_setprio(3);
     if (eliminator) band_solve_body<SOLVE_ASM_A>(v, S, nullptr, nullptr, w, lane, 0);
     else band_solve_body<SOLVE_ASM_B>(v, S, nullptr, nullptr, w, lane, 0);
 }

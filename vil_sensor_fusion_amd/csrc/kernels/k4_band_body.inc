@@ -8,17 +8,6 @@ VF_DI double readlane_d(double x, int lane) {
     return __hiloint2double(hi, lo);
 }
 
-// lanes 0..15 of x copied into the other three 16-lane rows: two VALU lane swaps per 32-bit half (gfx950's
-// v_permlane16_swap: rows 1, 3 of the first operand <-> rows 0, 2 of the second; v_permlane32_swap: upper half <-> lower half)
-VF_DI double rep_row0(double x) {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const auto c = __builtin_amdgcn_permlane32_swap(a[0], a[0], false, false);
-    const auto d = __builtin_amdgcn_permlane32_swap(b[0], b[0], false, false);
-    return __hiloint2double((int)d[0], (int)c[0]);
-}
-
 // One wavefront per window.  Right-looking block Cholesky of the block-banded normal matrix,
 // exploiting its profile: IMU factors couple consecutive keyframes in all 15 dof, between
 // factors couple keyframes up to 3 apart in the 6 pose dof only, so the active set while
@@ -102,40 +91,12 @@ constexpr int RING_SPIN_MAX = 1 << 22;        // polls (each an LDS read + s_sle
 constexpr int S_BC_RING = S_PROG + 8;
 constexpr int S_TOTAL_RING = S_BC_RING + 16;
 #ifndef VF_ASM2_ROLES
-#define VF_ASM2_ROLES 1     // two-wave assembling sweep: 1 = the workgroups of a CU agree on one eliminator per SIMD (View::place), 0 = wave 0 eliminates, 2 = wave 1 does (test build)
+#define VF_ASM2_ROLES 1     // two-wave assembling sweep: 1 = the workgroups of a CU agree on one eliminator per SIMD (View::place), 2 = wave 1 eliminates in every workgroup (test build)
 #endif
-#ifndef VF_ASM2_BSLEEP
-#define VF_ASM2_BSLEEP 1    // s_sleep argument of the assembler's polls (units of 64 clocks)
-#endif
-#ifndef VF_ASM2_PRIO
-#define VF_ASM2_PRIO 1      // two-wave assembling sweep: 1 = the eliminator's instructions issue first (s_setprio), 2 = the assembler's, 0 = neither
-#endif
-#ifndef VF_PIVOT_PERMLANE
-#define VF_PIVOT_PERMLANE 0      // 1: the scaled pivot column is replicated over the 16-lane rows by VALU lane swaps instead of through LDS
-#endif
+static_assert(VF_ASM2_ROLES == 1 || VF_ASM2_ROLES == 2, "the roles of the two-wave assembling sweep are agreed per CU (1) or swapped in every workgroup (2, test build)");
 #define WSYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define VF_PIVOT_SLOT(i) do {} while (0)     // places the generated pivot code leaves for its caller (tools/gen_pivot.py)
-#ifndef VF_AS_PLACEMENT
-#define VF_AS_PLACEMENT 0   // which of the pivot code's 28 places take the assembling sweep's 15 pieces (as_piece_of_slot)
-#endif
-// piece (the I of as_piece: 0 = operand reads, 2 .. 17 = one matrix instruction each, with gaps) issued at place `slot` of the
-// pivot code; 1 = none.  Placement 0: as early as possible (places 0 .. 17); 1: every other place; 2: as late as possible
-constexpr int as_piece_of_slot(int slot) {
-    [[maybe_unused]] constexpr int pieces[15] = {0, 2, 3, 4, 5, 7, 8, 9, 10, 12, 13, 14, 15, 16, 17};
-#if VF_AS_PLACEMENT == 0
-    return slot;
-#elif VF_AS_PLACEMENT == 1
-    return slot == 0 ? 0 : (slot % 2 == 1 ? pieces[(slot + 1) / 2] : 1);
-#else
-    return slot == 0 ? 0 : ((slot >= 12 && slot <= 25) ? pieces[slot - 11] : 1);
-#endif
-}
-#ifndef VF_ASM2_CHUNK
-#define VF_ASM2_CHUNK 1024
-#endif
-#ifndef VF_AS_SLOTS
-#define VF_AS_SLOTS 1     // assembling sweep: 1 = its matrix-core pieces ride in the pivot code's places, 0 = in front of the Schur update
-#endif
+constexpr int ASM2_CHUNK = 1024;    // windows per launch of the two-wave assembling sweep
 #define VF_SB() __builtin_amdgcn_sched_barrier(0)
 #ifdef VF_SOLVE_STAMPS   // diagnostic build only (tools/build_stamps.sh); never in the shipped library
 __device__ unsigned long long g_stamps[16];
@@ -604,7 +565,7 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
                 } else {
                     nx.tiles_wanted++;
                     int spin = 0;
-                    while (lds_peek(S + AS_FLAGS + 2) < (double)nx.tiles_wanted && ++spin < (1 << 22)) __builtin_amdgcn_s_sleep(VF_ASM2_BSLEEP);
+                    while (lds_peek(S + AS_FLAGS + 2) < (double)nx.tiles_wanted && ++spin < (1 << 22)) __builtin_amdgcn_s_sleep(1);
                     if (spin >= (1 << 22) && lane == 0) S[AS_FLAGS + 3] = 1.0;
                 }
             } else {
@@ -778,7 +739,7 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
                 // the window may be touched once the eliminator has read pivot row R - 4 (its Schur write-back of the step
                 // before is then done as well) and until it reads the accumulators of that step -- it waits for us there
                 int spin = 0;
-                while (lds_peek(S + AS_FLAGS) < (double)(R - 4) && ++spin < (1 << 22)) __builtin_amdgcn_s_sleep(VF_ASM2_BSLEEP);
+                while (lds_peek(S + AS_FLAGS) < (double)(R - 4) && ++spin < (1 << 22)) __builtin_amdgcn_s_sleep(1);
                 if (spin >= (1 << 22) && lane == 0) S[AS_FLAGS + 3] = 1.0;      // (never seen: the eliminator reports it as a failed solve)
             }
             as_rmw(ph, az);
@@ -873,23 +834,19 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
         STAMP(1);
         // panel factorisation: straight-line code in a fixed issue order (tools/gen_pivot.py); a non-positive
         // pivot turns the last reciprocal into NaN / inf, tested once per step
+        // (each scaled column's pivot-block entries go through LDS to come back replicated over the 16-lane rows; replicating
+        // them by VALU lane swaps instead was bit-identical and slower, 2.76 -> 3.04 ms fused at 1 024 windows: NOTEBOOK.md 7)
         double pv_inv;
         const int pv_bcw = lane < 15 ? (RINGM ? S_BC_RING : S_BC) + lane : S_DUMP + 32 + lane;
         const int pv_bcr = (RINGM ? S_BC_RING : S_BC) + (lane & 15);
         // (assembling sweep: iteration k + 4 -- row k + 4 from the operands of factor k + 5 -- rides in the pivot code's places)
         const int as_fimg = AS_LJ + ((lo + k + 5) & (JT - 1)) * LJS;
+        // (piece i -- the I of as_piece: 0 = operand reads, 2 .. 17 = one matrix instruction each, with gaps -- at place i, i.e. as
+        // early as possible; every other place and as late as possible made no difference, nor did issuing all of them back
+        // to back in front of the Schur update)
 #undef VF_PIVOT_SLOT
-#if VF_AS_SLOTS
-#define VF_PIVOT_SLOT(i) do { if constexpr (AS) { as_piece(IC<as_piece_of_slot(i)>{}, az, as_fimg); if constexpr ((i) == 1) as_stage_btw(k + 4, az, anx); if constexpr ((i) == 26) as_rmw(ph, az); VF_SB(); } } while (0)
-#else
-#define VF_PIVOT_SLOT(i) do {} while (0)
-#endif
-#if VF_PIVOT_PERMLANE
-#include "../vf_pivot_15p.inc"
-        (void)pv_bcw; (void)pv_bcr;
-#else
+#define VF_PIVOT_SLOT(i) do { if constexpr (AS) { as_piece(IC<(i)>{}, az, as_fimg); if constexpr ((i) == 1) as_stage_btw(k + 4, az, anx); if constexpr ((i) == 26) as_rmw(ph, az); VF_SB(); } } while (0)
 #include "../vf_pivot_15.inc"
-#endif
 #undef VF_PIVOT_SLOT
 #define VF_PIVOT_SLOT(i) do {} while (0)
         (void)as_fimg;
@@ -921,20 +878,6 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
         WSYNC();
         if constexpr (RINGM) { if (lane == 0) S[S_PROG] = (double)(k + 1); }   // panel k is complete in its ring slot
         STAMP(3);
-#if !VF_AS_SLOTS
-        if constexpr (AS) {
-            // the iteration's 18 matrix-core instructions, back to back: nothing else of this wave wants the vector unit
-            // here, the staging of the next between linearisation and the loads behind it issue in between
-            as_piece(IC<0>{}, az, as_fimg);
-            as_piece(IC<2>{}, az, as_fimg);  as_piece(IC<3>{}, az, as_fimg);  as_piece(IC<4>{}, az, as_fimg);
-            as_stage_btw(k + 4, az, anx);
-            as_piece(IC<5>{}, az, as_fimg);  as_piece(IC<7>{}, az, as_fimg);  as_piece(IC<8>{}, az, as_fimg);
-            as_piece(IC<9>{}, az, as_fimg);  as_piece(IC<10>{}, az, as_fimg); as_piece(IC<12>{}, az, as_fimg);
-            as_piece(IC<13>{}, az, as_fimg); as_piece(IC<14>{}, az, as_fimg); as_piece(IC<15>{}, az, as_fimg); as_piece(IC<16>{}, az, as_fimg);
-            as_piece(IC<17>{}, az, as_fimg);
-            as_rmw(ph, az);
-        }
-#endif
         if constexpr (ASA) {    // row k + 4 committed, the between terms it brings added to rows k + 1 .. k + 3
             int spin = 0;
             if (as_seen < (double)(k + 4))
@@ -1007,9 +950,6 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
         }
     }
     }   // forward sweep
-#ifdef VF_K4_FWD_ONLY   // probe build only (tools/build_variant.sh): the forward sweep's share of the un-stamped kernel
-    if constexpr (MODE == SOLVE_FULL) return;
-#endif
     if constexpr (MODE == SOLVE_FULL_FWD || AS || ASA || INCF) {
         if constexpr (ASA) { if (lds_peek(S + AS_FLAGS + 3) != 0.0) failed = 1; }     // a wait of the assembler wave ran out
         if (lane == 0) v.fail[w] = failed;
@@ -1110,11 +1050,9 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
         WSYNC();
     }
     struct PRow { d2_t x[8]; };
-#ifndef VF_BWD_PD
-#define VF_BWD_PD 2      // (2 against 4 slots: solve stage 3.44 against 3.48-3.50 ms at 1 024 windows, 178 against 240 registers; round 5)
-#endif
-    static_assert(VF_BWD_PD == 2 || VF_BWD_PD == 4, "the back substitution keeps 2 or 4 panel slots: any other depth reads panels it has not loaded");
-    constexpr int PD = (MODE == SOLVE_FULL_BWD || INCB) ? VF_BWD_PD : 4;      // panels prefetched ahead of the recursion
+    constexpr int BWD_PD = 2;      // (2 against 4 slots: solve stage 3.44 against 3.48-3.50 ms at 1 024 windows, 178 against 240 registers; round 5)
+    static_assert(BWD_PD == 2 || BWD_PD == 4, "the back substitution keeps 2 or 4 panel slots: any other depth reads panels it has not loaded");
+    constexpr int PD = (MODE == SOLVE_FULL_BWD || INCB) ? BWD_PD : 4;      // panels prefetched ahead of the recursion
     // Backward sweep: lane r < 28 holds panel row r (sub-diagonal rows and the rhs row: they go through LDS); the rows of
     // L^-T sit in lanes XL .. XL+14 of ONE 16-lane row, where s and x are formed as well, so that both matrix-vector
     // products of the recursion broadcast their vector with DPP row_newbcast inside v_fmac_f64 (one instruction per term

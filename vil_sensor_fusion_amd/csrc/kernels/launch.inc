@@ -34,12 +34,12 @@ void launch_extra_combine(const View& v, const double* Zm, size_t zstride, int s
     }
 }
 static void launch_linearize_all(const View& v, int which, hipStream_t s) {
-    const int nb_imu = (int)nblk(v.G, VF_K1_BLOCK), nb_btw = nb_imu, nb_pri = (int)nblk(v.B, VF_K1_BLOCK);
-    if (v.sh_G > 1) hipLaunchKernelGGL(k_linearize_all<true>, dim3(nb_imu + nb_btw + nb_pri), dim3(VF_K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
-    else hipLaunchKernelGGL(k_linearize_all<false>, dim3(nb_imu + nb_btw + nb_pri), dim3(VF_K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
+    const int nb_imu = (int)nblk(v.G, K1_BLOCK), nb_btw = nb_imu, nb_pri = (int)nblk(v.B, K1_BLOCK);
+    if (v.sh_G > 1) hipLaunchKernelGGL(k_linearize_all<true>, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
+    else hipLaunchKernelGGL(k_linearize_all<false>, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
 }
 void launch_linearize_imu(const View& v, int which, hipStream_t s) {
-    hipLaunchKernelGGL(k_linearize_imu, dim3(nblk(v.G, VF_K1_BLOCK)), dim3(VF_K1_BLOCK), 0, s, v, which);
+    hipLaunchKernelGGL(k_linearize_imu, dim3(nblk(v.G, K1_BLOCK)), dim3(K1_BLOCK), 0, s, v, which);
 }
 void launch_linearize_between(const View& v, int which, hipStream_t s) {
     hipLaunchKernelGGL(k_linearize_between, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which);
@@ -56,10 +56,7 @@ void launch_linearize(const View& v, int which, hipStream_t s) {
     }
 }
 void launch_linearize_tail(const View& v, int nslid, hipStream_t s) {
-    hipLaunchKernelGGL(k_linearize_tail, dim3(2 * v.B + nblk(v.B, 64)), dim3(VF_K1_BLOCK), 0, s, v, nslid);
-}
-void launch_linearize_prior(const View& v, int which, hipStream_t s) {
-    hipLaunchKernelGGL(k_linearize_prior, dim3(nblk(v.B, 64)), dim3(64), 0, s, v, which);
+    hipLaunchKernelGGL(k_linearize_tail, dim3(2 * v.B + nblk(v.B, 64)), dim3(K1_BLOCK), 0, s, v, nslid);
 }
 // K3 for the partitioned half of a hybrid solve whose sweep half assembles its own rows (see k_assemble)
 void launch_assemble_for_partitioned(const View& v, hipStream_t s) {
@@ -118,9 +115,9 @@ static void launch_asm2(const View& v, hipStream_t s) {
     // one launch per 1 024 windows -- the workgroups the part holds at once (4 per CU).  As ONE grid of 2 048 workgroups
     // the second thousand, dispatched one by one into the slots the first leaves, ran 1.7x slower than the first
     // (9.0 ms against 7.1 for the two launches; no such effect on the one-wave kernels)
-    for (int w0 = 0; w0 < v.B; w0 += VF_ASM2_CHUNK) {
-        const unsigned nb = (unsigned)(v.B - w0 < VF_ASM2_CHUNK ? v.B - w0 : VF_ASM2_CHUNK);
-        if (VF_ASM2_ROLES) (void)hipMemsetAsync(v.place, 0, PLACE_CELLS * sizeof(unsigned), s);      // the per-CU claims of this launch
+    for (int w0 = 0; w0 < v.B; w0 += ASM2_CHUNK) {
+        const unsigned nb = (unsigned)(v.B - w0 < ASM2_CHUNK ? v.B - w0 : ASM2_CHUNK);
+        (void)hipMemsetAsync(v.place, 0, PLACE_CELLS * sizeof(unsigned), s);      // the per-CU claims of this launch
         hipLaunchKernelGGL(k_band_forward_asm2, dim3(nb), dim3(128), 0, s, v, w0);
     }
 }

@@ -5,7 +5,8 @@
 //                           built at gtsam_fusion/src/gtsam_fusion/IMUManager.cpp:68-73)
 //   K2 k_linearize_between  BetweenFactor<Pose3> residual + whitened 6x6 Jacobians
 //                           (factor built at GraphManager.cpp:86)
-//   K2b k_linearize_prior   the three priors of GraphManager.cpp:27-35
+//   K2b linearize_prior_window  the three priors of GraphManager.cpp:27-35 and the marginal prior, one lane per window
+//                           (inside k_linearize_between_prior, k_linearize_all, k_linearize_tail)
 //   K3 k_assemble           block-banded J^T J / J^T r, owner-computes per keyframe
 //   K0 k_preintegrate       combined-IMU preintegration (IMUManager.cpp:42-64 + GTSAM's PIM)
 //   K4 k_band_solve(_tw)    (H + lambda I) delta = -g, block-banded Cholesky, one wave per window

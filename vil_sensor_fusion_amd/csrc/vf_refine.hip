@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(256) k_jtu(View v, Refine q, const double* __r
         const int j = k - lo, r0 = j == 0 ? 0 : 15 + 6 * (j - 1), nr = j == 0 ? 15 : 6;
         const double* L = v.mp_L + (size_t)w * 729;
         const double* p0 = p + ((size_t)w * v.M + lo) * 15;
-        if (GRAD) {          // the marginal prior's gradient L d + eta, as k_linearize_prior left it
+        if (GRAD) {          // the marginal prior's gradient L d + eta, as linearize_prior_window left it
             const double* gm = v.mp_out + ((size_t)b * v.B + w) * 28;
             for (int c = 0; c < nr; c++) o[c] += gm[r0 + c];
         } else
