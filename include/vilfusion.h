@@ -207,6 +207,11 @@ typedef struct {
     int far_big_forms;       /* engines made with max_far_factors > VF_MAX_EXTRA: the small dense systems of the far factors in device
                                 memory even while VF_MAX_EXTRA or fewer are alive (default 0 = the LDS forms then; same bits: what
                                 tests/test_gpu_far_capacity.py compares) */
+    int solve_backsub_form;  /* split and assembling sweeps: the back substitution kernel.  0 (default) = by batch: up to one window per
+                                SIMD of the device (4 x its compute units, read when the engine is made) the form built for one wave
+                                per SIMD -- the recursion software-pipelined, four panels in flight, more than 256 registers --, above
+                                the form built for two waves per SIMD; 1 = always the two-per-SIMD form; 2 = always the
+                                one-per-SIMD form.  Same arithmetic in the same order: same bits (tests/test_gpu_backsub_forms.py) */
 } vf_engine_tuning;
 
 

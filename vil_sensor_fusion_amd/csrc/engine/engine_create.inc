@@ -56,6 +56,7 @@ static void tuning_defaults(vf_engine_tuning* t) {
     t->hybrid_active_list = 1;
     t->far_batch_columns = 1;
     t->far_big_forms = 0;
+    t->solve_backsub_form = 0;   // by batch: the one-per-SIMD form up to one window per SIMD
 }
 // The caller's struct may be shorter than the library's (built against an older header): only its own bytes are written, and
 // struct_size says how many those are.  A struct the library does not know (longer than its own) gets the bytes it does know.
@@ -136,6 +137,13 @@ static int create_engine(const vf_engine_opts* o_in, const vf_engine_tuning* t_i
     v.split_min = t->solve_split_min > 0 ? t->solve_split_min : 0;
     v.asm_min = t->solve_assemble_min > 0 ? t->solve_assemble_min : 0;
     v.asm_waves = t->solve_assemble_waves == 1 ? 1 : 2;
+    v.bwd_form = t->solve_backsub_form == 1 || t->solve_backsub_form == 2 ? t->solve_backsub_form : 0;
+    {
+        // the SIMDs of the device (four per compute unit), read once, here: the batch up to which the back substitution has a SIMD
+        // per window (0 = not known: the two-per-SIMD form at every batch)
+        int cus = 0;
+        v.simds = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device) == hipSuccess && cus > 0 ? 4 * cus : 0;
+    }
     if (on_stream) { e->stream = given; e->own_stream = false; }
     else HIPCHK(hipStreamCreate(&e->stream));
     HIPCHK(hipEventCreate(&e->ev0));

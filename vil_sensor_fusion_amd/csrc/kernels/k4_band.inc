@@ -83,6 +83,16 @@ __global__ void __launch_bounds__(64) k_band_backward(View v) {
     __shared__ double Sb[S_TOTAL - S_DUMP];
     band_solve_body<SOLVE_FULL_BWD>(v, Sb - S_DUMP, nullptr, nullptr, w, threadIdx.x, 0);
 }
+// the same for batches of at most one window per SIMD (SolvePlan::bwd_one_wave), where a wave has no partner to cover its LDS round
+// trips: the software-pipelined recursion of the fused kernel (two sets of column registers, four panels in flight), which
+// needs more than the 256 registers of two waves per SIMD and gets them at one
+__attribute__((amdgpu_waves_per_eu(1, 1)))
+__global__ void __launch_bounds__(64) k_band_backward_1w(View v) {
+    const int w = sweep_window(v, blockIdx.x);
+    if (w < 0 || v.hi[w] - v.lo[w] <= 0 || window_done(v, w) || gated_off(v)) return;
+    __shared__ double Sb[S_TOTAL - S_DUMP];
+    band_solve_body<SOLVE_FULL_BWD1>(v, Sb - S_DUMP, nullptr, nullptr, w, threadIdx.x, 0);
+}
 
 // incremental updates (View::inc_*): the suffix of the window from the checkpoint in front of the first changed keyframe
 __global__ void __launch_bounds__(64) k_inc_forward(View v) {

@@ -35,6 +35,10 @@ VF_DI double readlane_d(double x, int lane) {
 // One-wave workgroup: LDS operations of a wave retire in issue order, so cross-lane hand-offs
 // through LDS need no s_barrier and no vmcnt(0) (which __syncthreads() carries and which would
 // stall every step on the in-flight HBM prefetch); a compiler barrier (+ lgkmcnt(0) where a value is used) is enough.
+// The same holds between the two waves of the two-wave sweep: their hand-shake cells are read with ds_read (lds_peek, lds_ask),
+// never through a volatile generic pointer, which compiles to flat_load + s_waitcnt vmcnt(0).  The only vmcnt waits inside a
+// step loop are the counted ones the compiler puts in front of the uses of prefetched registers (block rows, J tiles); the last
+// word of a J tile is waited for with vmcnt(0), in the one step of eight that puts a tile in place.
 // Sequential in k: latency-bound for one window, HBM-bound (5 TB/s) under a full batch; see DESIGN.md "K4".
 constexpr int LDW = 61;
 // Panel of one keyframe in HBM (vf_kernels.hpp "Cholesky panel"): column pairs, lane = row, so one 16-byte store / load
@@ -111,6 +115,15 @@ VF_DI double lds_peek(const double* p) {
     asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(x) : "v"(addr) : "memory");
     return x;
 }
+// the same read issued and NOT waited for, for a value that is wanted later: a relaxed workgroup-scope atomic load through an
+// LDS-address-space pointer, i.e. one ds_read_b64 the compiler counts in lgkmcnt itself and waits for in front of the first use.
+// (Never a volatile access through the generic pointer: that stays a flat_load with sc0 sc1 and gets s_waitcnt vmcnt(0)
+// behind it -- a drain of every panel store and tile load in flight, once per step: NOTEBOOK.md 7.17.)
+#define VF_LDS __attribute__((address_space(3)))
+VF_DI double lds_ask(const double* p) {
+    const VF_LDS long long* q = (const VF_LDS long long*)(size_t)(unsigned)(size_t)p;    // low half of a flat LDS address = LDS offset
+    return __longlong_as_double(__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
 
 // TW = false: one wave sweeps the whole window (throughput form, one window per SIMD).
 // TW = true : burn-at-both-ends (twisted) factorisation for one-window latency: wave 0 eliminates
@@ -128,6 +141,8 @@ constexpr int MID_TOTAL = 45 * MID_LD + 48;     // + the 45 solved increments ha
 //   as two kernels.  They hand over through HBM only (the panels and the rhs row the forward sweep stores anyway); the
 //   back substitution needs 9 KB of LDS instead of 38 and so runs two and more waves per SIMD where the fused kernel
 //   is held to one by the forward sweep's trailing window.
+// MODE 11 (k_band_backward_1w): MODE 5 for batches of at most one window per SIMD (SolvePlan::bwd_one_wave) -- the software-pipelined
+//   recursion of SOLVE_FULL's back substitution, four panels in flight, as a kernel held to one wave per SIMD.
 // MODE 6 (assembling forward sweep, where solve_plan() picks it: vf_solve_plan.hpp): SOLVE_FULL_FWD that forms the block rows of H itself,
 //   from the J stream and the between linearisations K1 / K2 leave, on the matrix cores, under the waits of the pivot
 //   chain -- K3 is not launched, H is neither written nor read.  See "assembling sweep" below.
@@ -140,7 +155,7 @@ constexpr int MID_TOTAL = 45 * MID_LD + 48;     // + the 45 solved increments ha
 //   checkpoint of its trailing window (and leaving one at every CK-th keyframe slot it passes), and the back substitution of
 //   SOLVE_FULL_BWD that stops once it reproduces the increments that are there, below keyframe cg.ni of the window.
 enum { SOLVE_FULL = 0, SOLVE_TWISTED = 1, SOLVE_CHUNK_FWD = 2, SOLVE_CHUNK_BWD = 3, SOLVE_FULL_FWD = 4, SOLVE_FULL_BWD = 5, SOLVE_ASM_FWD = 6,
-       SOLVE_ASM_A = 7, SOLVE_ASM_B = 8, SOLVE_INC_FWD = 9, SOLVE_INC_BWD = 10 };
+       SOLVE_ASM_A = 7, SOLVE_ASM_B = 8, SOLVE_INC_FWD = 9, SOLVE_INC_BWD = 10, SOLVE_FULL_BWD1 = 11 };
 template <int MODE>
 __device__ __forceinline__ void band_solve_body(const View& v, double* __restrict__ S, double* __restrict__ S_other,
                                                 double* __restrict__ MID, const int w, const int lane, const int wave,
@@ -151,6 +166,7 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
     constexpr bool AS = MODE == SOLVE_ASM_FWD || ASB;    // rows of H assembled here (no K3)
     constexpr bool CW = MODE == SOLVE_FULL_FWD || AS || ASA;   // compact trailing window ("CW_" map above); the names below shadow the full map
     constexpr bool INCF = MODE == SOLVE_INC_FWD, INCB = MODE == SOLVE_INC_BWD;
+    constexpr bool BWD = MODE == SOLVE_FULL_BWD || MODE == SOLVE_FULL_BWD1;     // the split back substitution, either form
     constexpr int S_GD = CW ? CW_GD : vf::S_GD, S_DUMP = CW ? CW_DUMP : vf::S_DUMP, S_ZERO = CW ? CW_ZERO : vf::S_ZERO;
     constexpr int S_ID = CW ? CW_ID : vf::S_ID, S_P = CW ? CW_P : vf::S_P, S_BC = CW ? CW_BC : vf::S_BC;
     const int lo = v.lo[w], hi = v.hi[w];
@@ -710,7 +726,7 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
 #ifdef VF_SOLVE_STAMPS
     unsigned long long st[16] = {0}, tprev = __builtin_amdgcn_s_memtime();
 #endif
-    if constexpr (MODE != SOLVE_CHUNK_BWD && MODE != SOLVE_FULL_BWD && !INCB) {
+    if constexpr (MODE != SOLVE_CHUNK_BWD && !BWD && !INCB) {
     Asm az;
     AsmNext anx;
     if constexpr (AS) {
@@ -851,10 +867,11 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
 #define VF_PIVOT_SLOT(i) do {} while (0)
         (void)as_fimg;
         if (!(pv_inv < 1e300)) failed = 1;
-        // (two-wave form: ask now how far the assembler is -- the answer travels under the panel's stores, and if row k + 4
-        // is there already, which is the rule, the wait in front of the Schur update costs no LDS round trip)
+        // (two-wave form: ask now how far the assembler is -- the answer travels under the panel's LDS writes, and if row k + 4
+        // is there already, which is the rule, the wait in front of the Schur update costs no LDS round trip.  lds_ask issues
+        // the read and waits for nothing; the value is first used behind the lgkmcnt(0) that follows the panel's writes.)
         double as_seen = 0.0;
-        if constexpr (ASA) as_seen = *(volatile double*)(S + AS_FLAGS + 1);
+        if constexpr (ASA) as_seen = lds_ask(S + AS_FLAGS + 1);
         STAMP(2);
         // sub-panel + rhs -> LDS (MFMA operands); rows 15..57 -> HBM, one 128-B line per lane
         if constexpr (RINGM) {
@@ -1052,7 +1069,7 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
     struct PRow { d2_t x[8]; };
     constexpr int BWD_PD = 2;      // (2 against 4 slots: solve stage 3.44 against 3.48-3.50 ms at 1 024 windows, 178 against 240 registers; round 5)
     static_assert(BWD_PD == 2 || BWD_PD == 4, "the back substitution keeps 2 or 4 panel slots: any other depth reads panels it has not loaded");
-    constexpr int PD = (MODE == SOLVE_FULL_BWD || INCB) ? BWD_PD : 4;      // panels prefetched ahead of the recursion
+    constexpr int PD = (MODE == SOLVE_FULL_BWD || INCB) ? BWD_PD : 4;      // panels prefetched ahead of the recursion (SOLVE_FULL_BWD1, one wave per SIMD: 4)
     // Backward sweep: lane r < 28 holds panel row r (sub-diagonal rows and the rhs row: they go through LDS); the rows of
     // L^-T sit in lanes XL .. XL+14 of ONE 16-lane row, where s and x are formed as well, so that both matrix-vector
     // products of the recursion broadcast their vector with DPP row_newbcast inside v_fmac_f64 (one instruction per term
@@ -1171,7 +1188,8 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
         Col ca, cb;
         if constexpr (MODE == SOLVE_FULL_BWD || INCB) {
             // two waves per SIMD: the partner wave covers this one's LDS round trips, so the recursion is not software-
-            // pipelined here -- one set of column registers instead of two keeps the kernel inside 256 registers
+            // pipelined here -- one set of column registers instead of two keeps the kernel inside 256 registers.  (A batch of
+            // at most one window per SIMD has no partner wave: it takes SOLVE_FULL_BWD1, the pipelined loop below.)
             int stop_at = 0;
 #pragma unroll 1
             for (int k = n4 - 1; k >= 3; k -= 4) {
@@ -1207,8 +1225,8 @@ __device__ __forceinline__ void band_solve_body(const View& v, double* __restric
     }
 #undef CBAR
 #ifdef VF_SOLVE_STAMPS
-    if (w == 0 && lane == 0) for (int i = (MODE == SOLVE_FULL_BWD ? 6 : 0); i < (MODE == SOLVE_FULL_BWD ? 11 : 16); i++) g_stamps[i] = st[i];
+    if (w == 0 && lane == 0) for (int i = (BWD ? 6 : 0); i < (BWD ? 11 : 16); i++) g_stamps[i] = st[i];
 #endif
     if constexpr (MODE == SOLVE_FULL) { if (lane == 0) v.fail[w] = failed; }
-    else if constexpr (MODE != SOLVE_FULL_BWD && !INCB) { if (lane == 0 && failed) atomicOr(v.fail + w, 1); }
+    else if constexpr (!BWD && !INCB) { if (lane == 0 && failed) atomicOr(v.fail + w, 1); }
 }

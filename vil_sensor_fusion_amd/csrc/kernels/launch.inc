@@ -143,7 +143,8 @@ void launch_band_solve(const View& v, const View& vp, const SolvePlan& plan, hip
         case Sweep::asm1:
         case Sweep::asm2:
             launch_band_forward(a, plan.sweep, s);
-            hipLaunchKernelGGL(k_band_backward, dim3(a.B), dim3(64), 0, s, a);
+            if (plan.bwd_one_wave) hipLaunchKernelGGL(k_band_backward_1w, dim3(a.B), dim3(64), 0, s, a);
+            else hipLaunchKernelGGL(k_band_backward, dim3(a.B), dim3(64), 0, s, a);
             break;
     }
     if (plan.partitioned) launch_partitioned_solve(b, s);

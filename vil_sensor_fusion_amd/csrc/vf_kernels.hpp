@@ -198,7 +198,9 @@ struct View {
     int gate, gate_T;
     int* act;           // [B] or null: compacted list of the windows still taking trials (k_count_active); the one-wave sweeps of a hybrid
                         // solve then map workgroup i to window act[i], so that the active windows are dispatched first and contiguously
-    // the four below are read by the host only, in solve_plan() (vf_solve_plan.hpp), which says when each applies
+    // the six below are read by the host only, in solve_plan() (vf_solve_plan.hpp), which says when each applies
+    int simds;          // SIMDs of the device (4 x its compute units; 0 = not known), read when the engine is made
+    int bwd_form;       // back substitution of the split / assembling sweeps: 0 = by batch against simds, 1 = k_band_backward, 2 = k_band_backward_1w
     int tw_max;         // whole-window sweeps: up to this many windows two waves per window from both ends, above one wave per window
     int split_min;      // whole-window sweeps: from this many windows on, forward sweep and back substitution as two kernels (0 = never)
     int asm_min;        // whole-window sweeps: from this many windows on, the forward sweep may assemble H itself from the J stream and
