@@ -60,6 +60,31 @@ def test_k6_large_batch_vs_oracle():
             np.testing.assert_allclose(y, dor.evaluate(name, ms, ps), rtol=1e-7, atol=1e-9, err_msg=f"{name}/{sub}")
 
 
+@pytest.mark.parametrize("T", [1, 2, 33, 64, 65, 129])
+def test_k6_staging_edges_vs_oracle(T):
+    """Series that end at and around the edges of the staging: a wave stages 64 messages (the single-subset kernel in two halves
+    of 32) and the message in front of them, so T = 1 (nothing to score), 2, 33 (one past a half), 64 (one full tile), 65 (a
+    tile whose only message has its previous matrix in the tile before) and 129 (the same after two full tiles).  A metric
+    without a previous matrix, one with, and one with poses too; float64 against the numpy oracle, by both entry points,
+    at the tolerances of test_k6_large_batch_vs_oracle."""
+    from vil_sensor_fusion_amd import degeneracy as dg
+    rng = np.random.default_rng(13)
+    A = rng.normal(size=(129, 6, 6))
+    mats = (A @ A.transpose(0, 2, 1) + 0.5 * np.eye(6))[:T]
+    pose = rng.normal(size=(129, 6))[:T]
+    m3, p3 = np.ascontiguousarray(mats.transpose(1, 2, 0)), np.ascontiguousarray(pose.T[:, None, :])
+    subs = ["all", "trans", "rot"]
+    for name in ["d_opt", "max_eigen_ratio", "kullback_leibler"]:
+        fused = dg.scores(m3, p3, name, subsets=subs)
+        for sub in subs:
+            ms, ps = dor.subset(mats, pose, sub)
+            ref = dor.evaluate(name, ms, ps)
+            assert np.isfinite(ref).all()
+            for how, y in (("single", dg.apply_degen_function(m3, p3, sub, name)), ("fused", fused[sub])):
+                assert y.shape == (T,) and y[0] == 0.0, f"{name}/{sub}/{how}"
+                np.testing.assert_allclose(y, ref, rtol=1e-7, atol=1e-9, err_msg=f"{name}/{sub}/{how}")
+
+
 def test_k6_fp32_tolerance_sweep():
     from vil_sensor_fusion_amd import degeneracy as dg
     mats, pose = GOLD["well_mats"], GOLD["well_pose"]

@@ -11,6 +11,12 @@
 // Small-matrix kernels: Householder tridiagonalisation + implicit QL for symmetric eigenvalues, one-sided
 // (Hestenes) Jacobi for singular values, LU with partial pivoting for det / inverse, all with compile-time
 // indices so a 6x6 lives in 36 registers.  float64 and float32 instantiations (fp32 tolerance sweep).
+//
+// Layout: the small-matrix routines; the Metric enum with metric_traits (what a metric reads); the metric functions, which
+// take blocks and return values (spectrum_metrics: the three of SPECTRUM); then what owns memory: stage_series_tile (HBM ->
+// LDS image), pick_block (image -> registers), score_block with Put (values -> output rows), and the three kernels --
+// k_degeneracy (one subset, image in two halves: more waves per SIMD), k_degeneracy_scores (any subsets of a mask from one
+// image) and k_degeneracy_scores_windows (the same over an engine's windows) -- and the C entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -216,30 +222,44 @@ DI void jacobi_svd(T (&a)[N * N], T (&sv)[N], bool active) {
     }
 }
 
-// LU with partial pivoting (row swaps by predicated moves): log|det| as numpy.linalg.slogdet()[1]
-template <typename T, int N>
-DI T lu_logabsdet(const T (&m)[N * N]) {
-    T a[N * N];
+template <typename T> DI void swap(T& x, T& y) { const T t = x; x = y; y = t; }
+
+// Partial pivoting at column c: the row among c .. N-1 with the largest |entry| in that column changes places with row c (by
+// predicated moves), in `a` and in every matrix of `more` alike.  True if rows moved.
+template <typename T, int N, typename... More>
+DI bool pivot_swap(int c, T (&a)[N * N], More&... more) {
+    int piv = c;
+    T best = t_abs(a[c * N + c]);
+    // (every row with those up to c skipped, not `r = c + 1 ..`: a trip count that depends on the argument is not unrolled in
+    // a function of its own, and the matrix went to scratch, 36 words per lane)
 #pragma unroll
-    for (int i = 0; i < N * N; i++) a[i] = m[i];
-    T logabs = T(0);
-#pragma unroll
-    for (int c = 0; c < N; c++) {
-        int piv = c;
-        T best = t_abs(a[c * N + c]);
-#pragma unroll
-        for (int r = c + 1; r < N; r++) {
+    for (int r = 1; r < N; r++)
+        if (r > c) {
             const T v = t_abs(a[r * N + c]);
             if (v > best) { best = v; piv = r; }
         }
 #pragma unroll
-        for (int r = c + 1; r < N; r++)
-            if (piv == r) {
+    for (int r = 1; r < N; r++)
+        if (r > c && piv == r) {
 #pragma unroll
-                for (int k = 0; k < N; k++) { const T t = a[c * N + k]; a[c * N + k] = a[r * N + k]; a[r * N + k] = t; }
-            }
+            for (int k = 0; k < N; k++) { swap(a[c * N + k], a[r * N + k]); (swap(more[c * N + k], more[r * N + k]), ...); }
+        }
+    return piv != c;
+}
+
+// LU with partial pivoting: each(pivot) for the pivots in elimination order, every one as soon as it is known (what `each` does
+// with it overlaps the row updates that follow: a float64 log is some fifty instructions); true if the number of row swaps is odd
+template <typename T, int N, typename Each>
+DI bool lu_pivots(const T (&m)[N * N], Each&& each) {
+    T a[N * N];
+#pragma unroll
+    for (int i = 0; i < N * N; i++) a[i] = m[i];
+    bool odd = false;
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+        odd ^= pivot_swap<T, N>(c, a);
         const T d = a[c * N + c];
-        logabs += log(t_abs(d));
+        each(d);
         const T inv = T(1) / d;
 #pragma unroll
         for (int r = c + 1; r < N; r++) {
@@ -248,43 +268,24 @@ DI T lu_logabsdet(const T (&m)[N * N]) {
             for (int k = c + 1; k < N; k++) a[r * N + k] = fma(-f, a[c * N + k], a[r * N + k]);
         }
     }
+    return odd;
+}
+
+// log|det| as numpy.linalg.slogdet()[1]: the logs of the pivots, summed in elimination order
+template <typename T, int N>
+DI T lu_logabsdet(const T (&m)[N * N]) {
+    T logabs = T(0);
+    lu_pivots<T, N>(m, [&](T d) __attribute__((always_inline)) { logabs += log(t_abs(d)); });
     return logabs;
 }
 
-// plain determinant with the swap parity applied
+// plain determinant: the pivots multiplied in elimination order, with the swap parity applied (a change of sign is exact, so
+// it commutes with the product)
 template <typename T, int N>
 DI T lu_det(const T (&m)[N * N]) {
-    T a[N * N];
-#pragma unroll
-    for (int i = 0; i < N * N; i++) a[i] = m[i];
     T det = T(1);
-#pragma unroll
-    for (int c = 0; c < N; c++) {
-        int piv = c;
-        T best = t_abs(a[c * N + c]);
-#pragma unroll
-        for (int r = c + 1; r < N; r++) {
-            const T v = t_abs(a[r * N + c]);
-            if (v > best) { best = v; piv = r; }
-        }
-#pragma unroll
-        for (int r = c + 1; r < N; r++)
-            if (piv == r) {
-#pragma unroll
-                for (int k = 0; k < N; k++) { const T t = a[c * N + k]; a[c * N + k] = a[r * N + k]; a[r * N + k] = t; }
-                det = -det;
-            }
-        const T d = a[c * N + c];
-        det *= d;
-        const T inv = T(1) / d;
-#pragma unroll
-        for (int r = c + 1; r < N; r++) {
-            const T f = a[r * N + c] * inv;
-#pragma unroll
-            for (int k = c + 1; k < N; k++) a[r * N + k] = fma(-f, a[c * N + k], a[r * N + k]);
-        }
-    }
-    return det;
+    const bool odd = lu_pivots<T, N>(m, [&](T d) __attribute__((always_inline)) { det *= d; });
+    return odd ? -det : det;
 }
 
 // inverse by Gauss-Jordan with partial pivoting
@@ -297,22 +298,7 @@ DI void gj_inverse(const T (&m)[N * N], T (&inv)[N * N]) {
     for (int i = 0; i < N; i++) inv[i * N + i] = T(1);
 #pragma unroll
     for (int c = 0; c < N; c++) {
-        int piv = c;
-        T best = t_abs(a[c * N + c]);
-#pragma unroll
-        for (int r = c + 1; r < N; r++) {
-            const T v = t_abs(a[r * N + c]);
-            if (v > best) { best = v; piv = r; }
-        }
-#pragma unroll
-        for (int r = c + 1; r < N; r++)
-            if (piv == r) {
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    T t = a[c * N + k]; a[c * N + k] = a[r * N + k]; a[r * N + k] = t;
-                    t = inv[c * N + k]; inv[c * N + k] = inv[r * N + k]; inv[r * N + k] = t;
-                }
-            }
+        pivot_swap<T, N>(c, a, inv);
         const T ip = T(1) / a[c * N + c];
 #pragma unroll
         for (int k = 0; k < N; k++) { a[c * N + k] *= ip; inv[c * N + k] *= ip; }
@@ -399,6 +385,22 @@ enum Metric { D_OPT, D_OPT_RATIO, A_OPT, A_OPT_RATIO, E_OPT, E_OPT_RATIO, MAX_EI
               JENSEN_BREGMAN_0, KL_0POSE, KL_0COV, CONDITION_COV, N_METRICS,
               SPECTRUM = N_METRICS };     // (not a metric of the reference: e_opt, max_eigen and condition_number of one eigen-solve, vf_degeneracy_spectrum_batch)
 
+// What a metric reads besides the matrix of its own message (make_prettier_graphs.py:565-574): prev = the previous message's
+// matrix (the ratio / divergence family), ratio = it enters as now . prev^-1, pose = the poses of both messages
+struct MetricTraits { bool prev, ratio, pose; };
+__host__ __device__ constexpr MetricTraits metric_traits(int m) {
+    switch (m) {
+        case D_OPT_RATIO: case A_OPT_RATIO: case NORM_FRO_RATIO: case NORM_NUC_RATIO: case NORM_1_RATIO: case NORM_2_RATIO:
+            return {true, true, false};
+        case E_OPT_RATIO: case MAX_EIGEN_RATIO: case JENSEN_BREGMAN: case CORR_DIST: case KL_0POSE:
+            return {true, false, false};
+        case KULLBACK_LEIBLER:
+            return {true, false, true};
+        default:
+            return {false, false, false};
+    }
+}
+
 // subset id -> (N, offset of the block on the diagonal): 0 all (6, 0), 1 trans (3, 0), 2 rot (3, 3), 3 + a the 1x1 entry of
 // axis a = x y z roll pitch yaw (1, a)
 constexpr int N_SUBSETS = 9;
@@ -422,7 +424,7 @@ DI T metric_1x1(T a, T b, T du) {
     switch (METRIC) {
         case D_OPT: return exp(log(t_abs(a)));
         case D_OPT_RATIO: return b != T(0) ? exp(log(t_abs(r))) : nan;
-        case A_OPT: case E_OPT: case MAX_EIGEN: case SPECTRUM: return a;
+        case A_OPT: case E_OPT: case MAX_EIGEN: return a;
         case A_OPT_RATIO: case E_OPT_RATIO: case MAX_EIGEN_RATIO: return b != T(0) ? r : nan;
         case JENSEN_BREGMAN: return log(t_abs((a + b) / T(2))) - T(0.5) * det_1x1(a * b);
         case JENSEN_BREGMAN_0: return log(t_abs(a / T(2)));
@@ -468,26 +470,75 @@ DI T normfro(const T (&a)[N * N]) {
     return t_sqrt(s);
 }
 
-// Which metrics read the previous message's matrix (the ratio / divergence family, make_prettier_graphs.py:565-574)
-__host__ __device__ constexpr bool metric_needs_prev(int m) {
-    return m == D_OPT_RATIO || m == A_OPT_RATIO || m == E_OPT_RATIO || m == MAX_EIGEN_RATIO || m == JENSEN_BREGMAN || m == CORR_DIST ||
-           m == KULLBACK_LEIBLER || m == NORM_FRO_RATIO || m == NORM_NUC_RATIO || m == NORM_1_RATIO || m == NORM_2_RATIO ||
-           m == KL_0POSE;
-}
 constexpr int MSTRIDE = 37;   // LDS stride of one 6x6 (36 + 1 pad: 64 lanes reading entry e of their own matrix hit 32 / 64 distinct banks)
 
-// One metric of message i on its N x N block, N = 6 or 3 (`now`, `prev`: the block of message i and of message i - 1, the
-// identity on lanes that are not `active`); off = the block's first row / column, for the pose.  SPECTRUM also writes
-// out2 / out3.
+// The symmetric part (m + m^T) / 2 with the largest |m_rc - m_cr| and the largest |entry| of m
+template <typename T, int N>
+DI void sym_part(const T (&m)[N * N], T (&s)[N * N], T& asym, T& big) {
+    asym = T(0);
+    big = T(0);
+#pragma unroll
+    for (int r = 0; r < N; r++)
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            s[r * N + c] = T(0.5) * (m[r * N + c] + m[c * N + r]);
+            big = t_abs(m[r * N + c]) > big ? t_abs(m[r * N + c]) : big;
+            if (c > r) { const T dsy = t_abs(m[r * N + c] - m[c * N + r]); asym = dsy > asym ? dsy : asym; }
+        }
+}
+// "Symmetric" = to within rounding of the entries (an asymmetry of that size moves a singular value by as much: what the SVD's
+// own rounding does)
+template <typename T>
+DI bool symmetric_to_rounding(T asym, T big) { return asym <= T(8) * Lim<T>::eps * big; }
+
+// What the metrics read off a spectrum (eigenvalues, or singular values, which are their own moduli): its two ends, the two
+// ends of its moduli and their sum
+template <typename T>
+struct Spectrum {
+    T lo, hi, alo, ahi, sum;
+    DI T cond() const { return ahi / alo; }       // numpy.linalg.cond of a symmetric matrix
+};
+template <typename T, int N>
+DI Spectrum<T> spectrum_of(const T (&ev)[N]) {
+    Spectrum<T> s{ev[0], ev[0], t_abs(ev[0]), t_abs(ev[0]), T(0)};
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const T x = t_abs(ev[k]);
+        s.lo = ev[k] < s.lo ? ev[k] : s.lo; s.hi = ev[k] > s.hi ? ev[k] : s.hi;
+        s.alo = x < s.alo ? x : s.alo; s.ahi = x > s.ahi ? x : s.ahi;
+        s.sum += x;
+    }
+    return s;
+}
+
+// e_opt, max_eigen and condition_number from ONE eigen-solve of the symmetric part: e_opt and max_eigen are defined on it;
+// condition_number too whenever the matrix is symmetric to rounding -- other matrices get NaN there (the SVD's business:
+// COND_NUMBER below).  The single metrics E_OPT and MAX_EIGEN are members of this.
+template <typename T> struct SpectrumMetrics { T e_opt, max_eigen, condition_number; };
+template <typename T, int N>
+DI SpectrumMetrics<T> spectrum_metrics(const T (&now)[N * N], bool active) {
+    if constexpr (N == 1) {
+        return {now[0], now[0], -cond_1x1(now[0])};
+    } else {
+        T s[N * N], ev[N], asym, big;
+        sym_part<T, N>(now, s, asym, big);
+        sym_eig<T, N>(s, ev, active);
+        const Spectrum<T> sp = spectrum_of<T, N>(ev);
+        return {sp.lo, sp.hi, symmetric_to_rounding(asym, big) ? -sp.cond() : T(NAN)};
+    }
+}
+
+// One metric of a message on its N x N block, N = 6 or 3 (`now`, `prev`: the block of the message and of the one before it, the
+// identity on lanes that are not `active`; du: the pose difference on the block's axes, KULLBACK_LEIBLER only).
+// The wave-uniform decisions in here (__any in the QL loop of sym_eig, __all in the sweep of jacobi_svd and in front of the
+// symmetric fast path) are taken over the wave's 64 consecutive messages of a series, whichever kernel calls; lanes that are
+// not active hold the identity and vote for the cheap side.  Built with -ffp-contract=fast: an expression keeps its grouping.
 template <typename T, int N, int METRIC>
-DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __restrict__ pose, int i, int count, int off,
-                  bool active, T* __restrict__ out2, T* __restrict__ out3) {
+DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T (&du)[N], bool active) {
     const T nan = T(NAN);
     T y = nan;
-    constexpr bool is_ratio = METRIC == D_OPT_RATIO || METRIC == A_OPT_RATIO || METRIC == NORM_FRO_RATIO ||
-                              METRIC == NORM_NUC_RATIO || METRIC == NORM_1_RATIO || METRIC == NORM_2_RATIO;
     T ratio[N * N];
-    if (is_ratio) {
+    if (metric_traits(METRIC).ratio) {
         T pinv[N * N];
         gj_inverse<T, N>(prev, pinv);
         matmul<T, N>(now, pinv, ratio);
@@ -503,50 +554,14 @@ DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __rest
             for (int k = 0; k < N; k++) s += (METRIC == A_OPT) ? now[k * N + k] : ratio[k * N + k];
             y = s;
         } break;
-        case SPECTRUM: {
-            // the three metrics that read the ends of the spectrum, from ONE eigen-solve of the symmetric part (e_opt and max_eigen
-            // are defined on it; condition_number too whenever the matrix is symmetric to rounding, see COND_NUMBER below --
-            // other matrices get NaN there and the caller asks for condition_number by itself)
-            T s[N * N], ev[N], asym = T(0), big = T(0);
-#pragma unroll
-            for (int r = 0; r < N; r++)
-#pragma unroll
-                for (int c = 0; c < N; c++) {
-                    s[r * N + c] = T(0.5) * (now[r * N + c] + now[c * N + r]);
-                    big = t_abs(now[r * N + c]) > big ? t_abs(now[r * N + c]) : big;
-                    if (c > r) { const T dsy = t_abs(now[r * N + c] - now[c * N + r]); asym = dsy > asym ? dsy : asym; }
-                }
-            sym_eig<T, N>(s, ev, active);
-            T lo = ev[0], hi = ev[0], alo = t_abs(ev[0]), ahi = t_abs(ev[0]);
-#pragma unroll
-            for (int k = 1; k < N; k++) {
-                lo = ev[k] < lo ? ev[k] : lo; hi = ev[k] > hi ? ev[k] : hi;
-                const T x = t_abs(ev[k]); alo = x < alo ? x : alo; ahi = x > ahi ? x : ahi;
-            }
-            y = lo;
-            if (i == 0) { out2[0] = T(0); out3[0] = T(0); }
-            else if (i < count) { out2[i] = hi; out3[i] = asym <= T(8) * Lim<T>::eps * big ? -(ahi / alo) : nan; }
-        } break;
-        case E_OPT: case MAX_EIGEN: {
-            T s[N * N], ev[N];
-#pragma unroll
-            for (int r = 0; r < N; r++)
-#pragma unroll
-                for (int c = 0; c < N; c++) s[r * N + c] = T(0.5) * (now[r * N + c] + now[c * N + r]);
-            sym_eig<T, N>(s, ev, active);
-            T lo = ev[0], hi = ev[0];
-#pragma unroll
-            for (int k = 1; k < N; k++) { lo = ev[k] < lo ? ev[k] : lo; hi = ev[k] > hi ? ev[k] : hi; }
-            y = METRIC == E_OPT ? lo : hi;
-        } break;
+        case E_OPT: y = spectrum_metrics<T, N>(now, active).e_opt; break;
+        case MAX_EIGEN: y = spectrum_metrics<T, N>(now, active).max_eigen; break;
         case E_OPT_RATIO: case MAX_EIGEN_RATIO: {
             T ev[N];
             bool ok;
             ratio_eig<T, N>(now, prev, ev, ok, active);
-            T lo = ev[0], hi = ev[0];
-#pragma unroll
-            for (int k = 1; k < N; k++) { lo = ev[k] < lo ? ev[k] : lo; hi = ev[k] > hi ? ev[k] : hi; }
-            y = ok ? (METRIC == E_OPT_RATIO ? lo : hi) : nan;
+            const Spectrum<T> sp = spectrum_of<T, N>(ev);
+            y = ok ? (METRIC == E_OPT_RATIO ? sp.lo : sp.hi) : nan;
         } break;
         case JENSEN_BREGMAN: {
             T avg[N * N], prod[N * N];
@@ -577,16 +592,15 @@ DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __rest
             }
             y = ok ? T(1) - tr / (t_sqrt(fx) * t_sqrt(fy)) : nan;
         } break;
-        case KULLBACK_LEIBLER: case KL_0POSE: {   // E1 = prev, E2 = now; KL_0POSE: pose difference 0
+        case KULLBACK_LEIBLER: case KL_0POSE: {   // E1 = prev, E2 = now; KL_0POSE: pose difference 0 (du is)
+            // (the determinants first: `now` is not needed past the inversion then, and du is carried through it)
+            const T c = log(t_abs(lu_det<T, N>(now)) / t_abs(lu_det<T, N>(prev)));
             T e2i[N * N], m[N * N];
             gj_inverse<T, N>(now, e2i);
             matmul<T, N>(e2i, prev, m);
-            T a = 0;
+            T a = 0, b = 0;
 #pragma unroll
             for (int k = 0; k < N; k++) a += m[k * N + k] - T(1);
-            T du[N], b = 0;
-#pragma unroll
-            for (int k = 0; k < N; k++) du[k] = (METRIC == KULLBACK_LEIBLER && pose && active) ? pose[(size_t)(i - 1) * 6 + off + k] - pose[(size_t)i * 6 + off + k] : T(0);
 #pragma unroll
             for (int r = 0; r < N; r++) {
                 T s = 0;
@@ -594,7 +608,6 @@ DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __rest
                 for (int c = 0; c < N; c++) s = fma(e2i[r * N + c], du[c], s);
                 b = fma(du[r], s, b);
             }
-            const T c = log(t_abs(lu_det<T, N>(now)) / t_abs(lu_det<T, N>(prev)));
             y = T(0.5) * (a + b + c);
         } break;
         case NORM_FRO: y = normfro<T, N>(now); break;
@@ -603,43 +616,29 @@ DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __rest
         case NORM_1_RATIO: y = norm1<T, N>(ratio); break;
         case NORM_NUC: case NORM_2: case COND_NUMBER: case CONDITION_COV: case NORM_NUC_RATIO: case NORM_2_RATIO: {
             T w[N * N], sv[N];
-            constexpr bool r = METRIC == NORM_NUC_RATIO || METRIC == NORM_2_RATIO;
-            constexpr bool cond = METRIC == COND_NUMBER || METRIC == CONDITION_COV;    // CONDITION_COV = +cond, the same bits negated
-            if (METRIC == NORM_NUC || METRIC == NORM_2 || cond) {
+            constexpr bool r = metric_traits(METRIC).ratio;
+            // the nuclear norm, the 2-norm or the condition number of a spectrum; CONDITION_COV = +cond, the same bits negated
+            auto of = [](const Spectrum<T>& sp) {
+                if (METRIC == NORM_NUC || METRIC == NORM_NUC_RATIO) return sp.sum;
+                if (METRIC == COND_NUMBER) return -sp.cond();
+                return METRIC == CONDITION_COV ? sp.cond() : sp.ahi;
+            };
+            if (!r) {
                 // An information matrix is symmetric, and the singular values of a symmetric matrix are the moduli of its
                 // eigenvalues: sigma_max / sigma_min, the sum and the maximum come from the eigen-solve e_opt / max_eigen use, at a
-                // seventh of the cost of a Jacobi SVD.  "Symmetric" = to within rounding of the entries (an asymmetry of that
-                // size moves a singular value by as much: what the SVD's own rounding does); a wave with a lane that holds
-                // anything else takes the general path below.
-                T asym = T(0), big = T(0);
-#pragma unroll
-                for (int rr = 0; rr < N; rr++)
-#pragma unroll
-                    for (int cc = 0; cc < N; cc++) {
-                        big = t_abs(now[rr * N + cc]) > big ? t_abs(now[rr * N + cc]) : big;
-                        if (cc > rr) { const T dsy = t_abs(now[rr * N + cc] - now[cc * N + rr]); asym = dsy > asym ? dsy : asym; }
-                    }
-                if (__all(!active || asym <= T(8) * Lim<T>::eps * big)) {
-                    T sy[N * N], ev[N];
-#pragma unroll
-                    for (int rr = 0; rr < N; rr++)
-#pragma unroll
-                        for (int cc = 0; cc < N; cc++) sy[rr * N + cc] = T(0.5) * (now[rr * N + cc] + now[cc * N + rr]);
-                    sym_eig<T, N>(sy, ev, active);
-                    T lo = t_abs(ev[0]), hi = t_abs(ev[0]), sum = T(0);
-#pragma unroll
-                    for (int k = 0; k < N; k++) { const T x = t_abs(ev[k]); lo = x < lo ? x : lo; hi = x > hi ? x : hi; sum += x; }
-                    y = METRIC == NORM_NUC ? sum : (cond ? (METRIC == COND_NUMBER ? -(hi / lo) : hi / lo) : hi);
+                // seventh of the cost of a Jacobi SVD.  A wave with a lane that holds anything else takes the general path below.
+                T asym, big;
+                sym_part<T, N>(now, w, asym, big);
+                if (__all(!active || symmetric_to_rounding(asym, big))) {
+                    sym_eig<T, N>(w, sv, active);
+                    y = of(spectrum_of<T, N>(sv));
                     break;
                 }
             }
 #pragma unroll
             for (int k = 0; k < N * N; k++) w[k] = r ? ratio[k] : now[k];
             jacobi_svd<T, N>(w, sv, active);
-            T lo = sv[0], hi = sv[0], sum = 0;
-#pragma unroll
-            for (int k = 0; k < N; k++) { lo = sv[k] < lo ? sv[k] : lo; hi = sv[k] > hi ? sv[k] : hi; sum += sv[k]; }
-            y = (METRIC == NORM_NUC || METRIC == NORM_NUC_RATIO) ? sum : (cond ? (METRIC == COND_NUMBER ? -(hi / lo) : hi / lo) : hi);
+            y = of(spectrum_of<T, N>(sv));
         } break;
         case DIFF_ENTROPY: {
             const T x = pow(T(2.0 * 3.141592653589793 * 2.718281828459045), T(N));
@@ -651,25 +650,43 @@ DI T block_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __rest
     return y;
 }
 
-// One metric on the N x N block of any subset: N = 1 (the per-axis subsets) takes the closed forms of metric_1x1.  Both
-// kernels below call this, so a subset computed by the fused launch is the arithmetic of the launch of that subset alone,
-// and the wave-uniform decisions inside (__all / __any of the eigen-solver and the SVD, the symmetric fast path) are taken
-// over the same 64 consecutive messages in both.
+// One metric on the N x N block of any subset: N = 1 (the per-axis subsets) takes the closed forms of metric_1x1
 template <typename T, int N, int METRIC>
-DI T degeneracy_metric(const T (&now)[N * N], const T (&prev)[N * N], const T* __restrict__ pose, int i, int count, int off,
-                       bool active, T* __restrict__ out2, T* __restrict__ out3) {
-    if constexpr (N == 1) {
-        const bool kl = METRIC == KULLBACK_LEIBLER && pose && active;
-        const T du = kl ? pose[(size_t)(i - 1) * 6 + off] - pose[(size_t)i * 6 + off] : T(0);
-        const T y = metric_1x1<T, METRIC>(now[0], prev[0], du);
-        if (METRIC == SPECTRUM) {     // e_opt = max_eigen = a, condition_number = -cond
-            if (i == 0) { out2[0] = T(0); out3[0] = T(0); }
-            else if (i < count) { out2[i] = y; out3[i] = -cond_1x1(y); }
-        }
-        return y;
-    } else {
-        return block_metric<T, N, METRIC>(now, prev, pose, i, count, off, active, out2, out3);
+DI T degeneracy_metric(const T (&now)[N * N], const T (&prev)[N * N], const T (&du)[N], bool active) {
+    if constexpr (N == 1) return metric_1x1<T, METRIC>(now[0], prev[0], du[0]);
+    else return block_metric<T, N, METRIC>(now, prev, du, active);
+}
+
+// Where a lane's values go: entry i of one output row after another, `row` values apart.  The first message of a series has
+// nothing in front of it and scores 0 (make_prettier_graphs.py:562-563); lanes past the end of the series store nothing.
+template <typename T>
+struct Put {
+    T* __restrict__ o;
+    size_t row;
+    int i, count;
+    DI void operator()(T y) {
+        if (i == 0) o[0] = T(0);
+        else if (i < count) o[i] = y;
+        o += row;
     }
+};
+
+// Message i's values of METRIC on the N x N block at `off`: one, or the three of SPECTRUM
+template <typename T, int N, int METRIC>
+DI Put<T> score_block(const T (&now)[N * N], const T (&prev)[N * N], const T* __restrict__ pose, int i, int off, bool active, Put<T> put) {
+    if constexpr (METRIC == SPECTRUM) {
+        const SpectrumMetrics<T> s = spectrum_metrics<T, N>(now, active);
+        put(s.e_opt);
+        put(s.max_eigen);
+        put(s.condition_number);
+    } else {
+        T du[N];     // the pose of the message before, minus this one's
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            du[k] = (metric_traits(METRIC).pose && pose && active) ? pose[(size_t)(i - 1) * 6 + off + k] - pose[(size_t)i * 6 + off + k] : T(0);
+        put(degeneracy_metric<T, N, METRIC>(now, prev, du, active));
+    }
+    return put;
 }
 
 // the N x N block at (off, off) of the 6 x 6 staged at `m` (LDS), or the identity on a lane that is not active
@@ -681,42 +698,65 @@ DI void pick_block(const T* m, int off, bool active, T (&a)[N * N]) {
         for (int c = 0; c < N; c++) a[r * N + c] = active ? m[off * 7 + r * 6 + c] : T(r == c);
 }
 
-// mats: (T,6,6) row-major, pose (T,6) or null; N and off from the subset (6 / 3 / 1, subset_off); out[0] = 0.
-// One wave per 64 consecutive messages.  The wave's matrices (and the one in front of them, for the metrics that compare
-// with the previous message) are ONE contiguous stretch of HBM: it is copied to LDS with 16-byte loads, fully
-// coalesced, and every lane then picks its own matrix out of LDS (lane = message reads of 288-byte records straight
-// from HBM touch 64 cache lines per load instruction).  METRIC is a template parameter: a metric's kernel contains
-// only its own arithmetic and loads the previous matrix only if it uses it.
+// Staging: the TILE matrices of the series from `base` on (those that exist: the series has `count`), and with PREV the one in
+// front of them, are ONE contiguous stretch of HBM; it is copied into the LDS image (matrix base + l at local index l + 1, the
+// one in front at 0) with 16-byte loads, fully coalesced, FLIGHT of them per lane (0: all) issued before the first is waited for
+// (they are 4 registers of the lane each while they fly).  Every lane then picks its own matrix out of LDS (lane = message reads
+// of 288-byte records straight from HBM touch 64 cache lines per load instruction).
+template <typename T, bool PREV, int TILE, int FLIGHT>
+DI void stage_series_tile(T* __restrict__ lds, const T* __restrict__ mats, int base, int count, int lane) {
+    const int first = (PREV && base > 0) ? base - 1 : base;           // first matrix staged, local index first - base + 1
+    const int last = base + TILE < count ? base + TILE : count;
+    constexpr int V = 16 / (int)sizeof(T);                             // elements per 16-byte load (36 is a multiple of both)
+    constexpr int PER = ((TILE + 1) * 36 / V + 63) / 64;               // 16-byte loads per lane at most
+    const int nvec = (last - first) * 36 / V;
+    using vec_t = T __attribute__((ext_vector_type(V)));
+    const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
+    constexpr int F = FLIGHT ? FLIGHT : PER;
+    // (the groups in a rolled loop that a lane leaves when it has run out of vectors: unrolled, the LDS addresses of every group
+    // are computed up front and a kernel that stages at four or more waves per SIMD loses one of them to the registers; a fixed
+    // number of rounds with every load and store predicated cost k_degeneracy 3-5 % at 2^22 matrices,
+    // profiles/k6_one_path_timing.json)
+#pragma unroll 1
+    for (int v0 = lane; v0 < nvec; v0 += 64 * F) {
+        vec_t x[F];
+#pragma unroll
+        for (int k = 0; k < F; k++)
+            if (k == 0 || v0 + 64 * k < nvec) x[k] = __builtin_nontemporal_load(src + v0 + 64 * k);
+#pragma unroll
+        for (int k = 0; k < F; k++) {
+            const int v = v0 + 64 * k;
+            if (k == 0 || v < nvec) {
+                const int e = v * V, m = e / 36, r = e - m * 36;
+                T* dst = lds + (m + first - base + 1) * MSTRIDE + r;
+#pragma unroll
+                for (int j = 0; j < V; j++) dst[j] = x[k][j];
+            }
+        }
+        if (F == PER) break;         // one group holds them all: no loop
+    }
+}
+
+// mats: (T,6,6) row-major, pose (T,6) or null; N and off from the subset (6 / 3 / 1, subset_off); out: one row of `count`
+// values (SPECTRUM: three).  One wave per 64 consecutive messages.  METRIC is a template parameter: a metric's kernel
+// contains only its own arithmetic and loads the previous matrix only if it uses it.
 template <typename T, int N, int METRIC>
 __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, const T* __restrict__ pose, int count, int off,
-                                                   T* __restrict__ out, T* __restrict__ out2 = nullptr, T* __restrict__ out3 = nullptr) {
+                                                   T* __restrict__ out) {
     // staged in two halves of 32 messages (lanes 0-31 pick theirs up after the first, 32-63 after the second): 9.8 KB of LDS
-    // per wave instead of 19.2, i.e. four waves per SIMD instead of two for the Jacobi kernels
+    // per wave instead of 19.2, i.e. four waves per SIMD instead of two for the Jacobi kernels; with that many waves to hide a
+    // load behind, one load in flight per lane (the matrices of the first half are in registers while the second is staged)
     __shared__ T lds[33 * MSTRIDE];
     const int lane = threadIdx.x, base = blockIdx.x * 64;
     const int i = base + lane;
-    constexpr bool PREV = metric_needs_prev(METRIC);
+    constexpr bool PREV = metric_traits(METRIC).prev;
     const bool active = i > 0 && i < count;
     T now[N * N], prev[N * N];
 #pragma unroll
     for (int half = 0; half < 2; half++) {
         const int hb = base + 32 * half;                                  // first message of this half
         if (half) __syncthreads();
-        if (hb < count) {
-            const int first = (PREV && hb > 0) ? hb - 1 : hb;            // first matrix staged, local index first - hb + 1
-            const int last = hb + 32 < count ? hb + 32 : count;
-            constexpr int V = 16 / (int)sizeof(T);                        // elements per 16-byte load (36 is a multiple of both)
-            const int nvec = (last - first) * 36 / V;
-            using vec_t = T __attribute__((ext_vector_type(V)));
-            const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
-            for (int v = lane; v < nvec; v += 64) {
-                const vec_t x = __builtin_nontemporal_load(src + v);
-                const int e = v * V, m = e / 36, r = e - m * 36;
-                T* dst = lds + (m + first - hb + 1) * MSTRIDE + r;
-#pragma unroll
-                for (int k = 0; k < V; k++) dst[k] = x[k];
-            }
-        }
+        if (hb < count) stage_series_tile<T, PREV, 32, 1>(lds, mats, hb, count, lane);
         __syncthreads();
         if ((lane >> 5) == half) {
             const int l = lane & 31;
@@ -724,90 +764,47 @@ __global__ void __launch_bounds__(64) k_degeneracy(const T* __restrict__ mats, c
             pick_block<T, N>(lds + l * MSTRIDE, off, PREV && active, prev);
         }
     }
-    const T y = degeneracy_metric<T, N, METRIC>(now, prev, pose, i, count, off, active, out2, out3);
-    if (i == 0) out[0] = T(0);            // make_prettier_graphs.py:562-563
-    else if (i < count) out[i] = y;
+    score_block<T, N, METRIC>(now, prev, pose, i, off, active, Put<T>{out, (size_t)count, i, count});
 }
 
-// The staging of the two fused kernels below: the 64 matrices of the series from `base` on (those that exist: the series has
-// `count`), and with PREV the one in front of them, are ONE contiguous stretch of HBM; it is copied into the LDS image (matrix
-// base + l at local index l + 1, the one in front at 0) with 16-byte loads, all of them issued before the first is waited for.
-template <typename T, bool PREV>
-DI void stage_series_tile(T* __restrict__ lds, const T* __restrict__ mats, int base, int count, int lane) {
-    const int first = (PREV && base > 0) ? base - 1 : base;           // first matrix staged, local index first - base + 1
-    const int last = base + 64 < count ? base + 64 : count;
-    constexpr int V = 16 / (int)sizeof(T);
-    constexpr int PER = (65 * 36 / V + 63) / 64;                       // 16-byte loads per lane at most
-    const int nvec = (last - first) * 36 / V;
-    using vec_t = T __attribute__((ext_vector_type(V)));
-    const vec_t* src = reinterpret_cast<const vec_t*>(mats + (size_t)first * 36);
-    vec_t x[PER];
-#pragma unroll
-    for (int k = 0; k < PER; k++)
-        if (lane + 64 * k < nvec) x[k] = __builtin_nontemporal_load(src + lane + 64 * k);
-#pragma unroll
-    for (int k = 0; k < PER; k++) {
-        const int v = lane + 64 * k;
-        if (v < nvec) {
-            const int e = v * V, m = e / 36, r = e - m * 36;
-            T* dst = lds + (m + first - base + 1) * MSTRIDE + r;
-#pragma unroll
-            for (int j = 0; j < V; j++) dst[j] = x[k][j];
-        }
-    }
-}
-
-// ... and what they do with the image: every subset set in `mask` for message i = base + lane of the series, one after
-// another (subsets in sequence, not interleaved: the registers are those of the largest one).  out: one row per subset in
-// the mask, in ascending subset id, `row` values apart; the lane's value goes to entry i of each.
+// What the two fused kernels below do with the image of a tile of 64: every subset set in `mask` for message i = base + lane
+// of the series, one after another (subsets in sequence, not interleaved: the registers are those of the largest one).  out:
+// one row per subset in the mask, in ascending subset id, `row` values apart; the lane's value goes to entry i of each.
 template <typename T, int METRIC>
 DI void scores_from_image(const T* __restrict__ lds, const T* __restrict__ pose, int i, int count, unsigned mask, T* __restrict__ out,
                           size_t row, int lane) {
-    constexpr bool PREV = metric_needs_prev(METRIC);
+    constexpr bool PREV = metric_traits(METRIC).prev;
     const bool active = i > 0 && i < count;
     const T* mn = lds + (lane + 1) * MSTRIDE;
     const T* mp = lds + lane * MSTRIDE;
-    T* o = out;
-    auto put = [&](T y) {
-        if (i == 0) o[0] = T(0);
-        else if (i < count) o[i] = y;
-        o += row;
+    Put<T> put{out, row, i, count};
+    auto subset = [&](auto N, int s) __attribute__((always_inline)) {
+        T now[N() * N()], prev[N() * N()];
+        pick_block<T, N()>(mn, subset_off(s), active, now);
+        pick_block<T, N()>(mp, subset_off(s), PREV && active, prev);
+        put = score_block<T, N(), METRIC>(now, prev, pose, i, subset_off(s), active, put);
     };
-    if (mask & 1u) {
-        T now[36], prev[36];
-        pick_block<T, 6>(mn, 0, active, now);
-        pick_block<T, 6>(mp, 0, PREV && active, prev);
-        put(degeneracy_metric<T, 6, METRIC>(now, prev, pose, i, count, 0, active, nullptr, nullptr));
-    }
+    if (mask & 1u) subset(std::integral_constant<int, 6>{}, 0);
 #pragma unroll 1
     for (int s = 1; s < 3; s++)
-        if (mask >> s & 1u) {
-            T now[9], prev[9];
-            pick_block<T, 3>(mn, subset_off(s), active, now);
-            pick_block<T, 3>(mp, subset_off(s), PREV && active, prev);
-            put(degeneracy_metric<T, 3, METRIC>(now, prev, pose, i, count, subset_off(s), active, nullptr, nullptr));
-        }
+        if (mask >> s & 1u) subset(std::integral_constant<int, 3>{}, s);
 #pragma unroll 1
     for (int s = 3; s < N_SUBSETS; s++)
-        if (mask >> s & 1u) {
-            T now[1], prev[1];
-            pick_block<T, 1>(mn, subset_off(s), active, now);
-            pick_block<T, 1>(mp, subset_off(s), PREV && active, prev);
-            put(degeneracy_metric<T, 1, METRIC>(now, prev, pose, i, count, subset_off(s), active, nullptr, nullptr));
-        }
+        if (mask >> s & 1u) subset(std::integral_constant<int, 1>{}, s);
 }
 
 // Several subsets of one metric in one launch (the online node's score_all / score_trans / score_rot of one message,
 // vil_fusion/src/vil_fusion/degeneracy_detection.py:115-130): the wave's 64 matrices (and the one before them) are staged
-// into LDS ONCE, as k_degeneracy stages them, and every subset set in `mask` is then evaluated from that image, one
-// after another.  out: one row of `count` values per subset in the mask, in ascending subset id.  All 65 matrices stay in
-// LDS for the whole launch (19.2 KB per wave in float64).
+// into LDS ONCE and every subset set in `mask` is then evaluated from that image, one after another, by the arithmetic of
+// k_degeneracy over the same 64 messages: a row has the bits of the launch of its subset alone.  out: one row of `count`
+// values per subset in the mask, in ascending subset id.  All 65 matrices stay in LDS for the whole launch (19.2 KB per wave
+// in float64).
 template <typename T, int METRIC>
 __global__ void __launch_bounds__(64) k_degeneracy_scores(const T* __restrict__ mats, const T* __restrict__ pose, int count,
                                                           unsigned mask, T* __restrict__ out) {
     __shared__ T lds[65 * MSTRIDE];
     const int lane = threadIdx.x, base = blockIdx.x * 64;
-    stage_series_tile<T, metric_needs_prev(METRIC)>(lds, mats, base, count, lane);
+    stage_series_tile<T, metric_traits(METRIC).prev, 64, 0>(lds, mats, base, count, lane);
     __syncthreads();
     scores_from_image<T, METRIC>(lds, pose, base + lane, count, mask, out, (size_t)count, lane);
 }
@@ -828,7 +825,7 @@ __global__ void __launch_bounds__(64) k_degeneracy_scores_windows(const double* 
     const int lo = range[2 * w], count = range[2 * w + 1] - lo;
     if (base >= count || lo < 0 || lo + count > M) return;
     const size_t g0 = (size_t)w * M + lo;
-    stage_series_tile<double, metric_needs_prev(METRIC)>(lds, mats + g0 * 36, base, count, lane);
+    stage_series_tile<double, metric_traits(METRIC).prev, 64, 0>(lds, mats + g0 * 36, base, count, lane);
     __syncthreads();
     scores_from_image<double, METRIC>(lds, pose + g0 * 6, base + lane, count, mask, out + g0, row, lane);
 }
@@ -929,24 +926,19 @@ void with_block(int subset, F&& f) {
     else f(std::integral_constant<int, 1>{});
 }
 
-template <typename T>
-int run_metric(const void* mats, const void* pose, int count, int subset, int metric, void* out, int reps, float* kernel_ms) {
-    const int off = subset_off(subset);
-    const dim3 grid((count + 63) / 64);
-    return run_batch<T>(mats, pose, count, 1, {out}, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
-        with_block(subset, [&](auto N) {
-            with_metric(metric, [&](auto M) { hipLaunchKernelGGL((k_degeneracy<T, N(), M()>), grid, dim3(64), 0, 0, m, p, count, off, o); });
-        });
-    });
-}
+// f(T{}) for the element type of a dtype id (checked by check_batch)
+template <typename F>
+int with_dtype(int dtype, F&& f) { return dtype == 0 ? f(double{}) : f(float{}); }
 
+// one subset of one metric; metric = SPECTRUM: its three values, in the three arrays of `outs`
 template <typename T>
-int run_spectrum(const void* mats, int count, int subset, void* o_min, void* o_max, void* o_cond, int reps, float* kernel_ms) {
+int run_metric(const void* mats, const void* pose, int count, int subset, int metric, std::initializer_list<void*> outs, int reps, float* kernel_ms) {
     const int off = subset_off(subset);
     const dim3 grid((count + 63) / 64);
-    return run_batch<T>(mats, nullptr, count, 3, {o_min, o_max, o_cond}, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
+    return run_batch<T>(mats, pose, count, (int)outs.size(), outs, reps, kernel_ms, [&](const T* m, const T* p, T* o) {
         with_block(subset, [&](auto N) {
-            hipLaunchKernelGGL((k_degeneracy<T, N(), SPECTRUM>), grid, dim3(64), 0, 0, m, p, count, off, o, o + count, o + 2 * (size_t)count);
+            if (metric == SPECTRUM) hipLaunchKernelGGL((k_degeneracy<T, N(), SPECTRUM>), grid, dim3(64), 0, 0, m, p, count, off, o);
+            else with_metric(metric, [&](auto M) { hipLaunchKernelGGL((k_degeneracy<T, N(), M()>), grid, dim3(64), 0, 0, m, p, count, off, o); });
         });
     });
 }
@@ -959,16 +951,26 @@ int run_scores(const void* mats, const void* pose, int count, int metric, unsign
     });
 }
 
+int check_subset(int subset) {
+    if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
+    return VF_OK;
+}
+
+int check_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    return VF_OK;
+}
+
 // What the batch entry points refuse alike, in this order; *run: there are matrices, and a device to take them to
 int check_batch(bool null_argument, int count, int metric, int dtype, bool has_pose, bool* run) {
     *run = false;
     if (null_argument || count < 0) return derr(VF_ERR_INVALID, "null argument");
     if (metric < 0 || metric >= N_METRICS) return derr(VF_ERR_INVALID, "unknown metric %d", metric);
     if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
-    if (metric == KULLBACK_LEIBLER && !has_pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
+    if (metric_traits(metric).pose && !has_pose) return derr(VF_ERR_INVALID, "kullback_leibler needs poses");
     if (count == 0) return VF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    if (int rc = check_device()) return rc;
     *run = true;
     return VF_OK;
 }
@@ -990,19 +992,19 @@ extern "C" {
 int vf_degeneracy_spectrum_batch(const void* mats, int count, int dtype, int subset, void* e_opt, void* max_eigen, void* condition_number,
                                  int reps, float* kernel_ms) {
     bool run;
-    if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
+    if (int rc = check_subset(subset)) return rc;
     if (int rc = check_batch(!mats || !e_opt || !max_eigen || !condition_number, count, E_OPT, dtype, false, &run); rc || !run) return rc;
-    return dtype == 0 ? run_spectrum<double>(mats, count, subset, e_opt, max_eigen, condition_number, reps, kernel_ms)
-                      : run_spectrum<float>(mats, count, subset, e_opt, max_eigen, condition_number, reps, kernel_ms);
+    return with_dtype(dtype, [&](auto t) {
+        return run_metric<decltype(t)>(mats, nullptr, count, subset, SPECTRUM, {e_opt, max_eigen, condition_number}, reps, kernel_ms);
+    });
 }
 
 int vf_degeneracy_batch(const void* mats, const void* pose, int count, int dtype, int subset, int metric, void* out,
                         int reps, float* kernel_ms) {
     bool run;
-    if (subset < 0 || subset >= N_SUBSETS) return derr(VF_ERR_INVALID, "subset must be 0 (all), 1 (trans), 2 (rot) or 3 .. 8 (x y z roll pitch yaw)");
+    if (int rc = check_subset(subset)) return rc;
     if (int rc = check_batch(!mats || !out, count, metric, dtype, pose != nullptr, &run); rc || !run) return rc;
-    return dtype == 0 ? run_metric<double>(mats, pose, count, subset, metric, out, reps, kernel_ms)
-                      : run_metric<float>(mats, pose, count, subset, metric, out, reps, kernel_ms);
+    return with_dtype(dtype, [&](auto t) { return run_metric<decltype(t)>(mats, pose, count, subset, metric, {out}, reps, kernel_ms); });
 }
 
 int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, int dtype, int metric, unsigned subset_mask, void* out,
@@ -1010,16 +1012,14 @@ int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, in
     bool run;
     if (subset_mask == 0 || (subset_mask >> N_SUBSETS) != 0) return derr(VF_ERR_INVALID, "subset_mask 0x%x: bits 0 .. 8, at least one", subset_mask);
     if (int rc = check_batch(!mats || !out, count, metric, dtype, pose != nullptr, &run); rc || !run) return rc;
-    return dtype == 0 ? run_scores<double>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms)
-                      : run_scores<float>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms);
+    return with_dtype(dtype, [&](auto t) { return run_scores<decltype(t)>(mats, pose, count, metric, subset_mask, out, reps, kernel_ms); });
 }
 
 int vf_dopt_filter_f32(const float* hessians, int count, float rot_thr, float trans_thr, float* rot_dopt,
                        float* trans_dopt, unsigned char* keep) {
     if (!hessians || !rot_dopt || !trans_dopt || !keep || count < 0) return derr(VF_ERR_INVALID, "null argument");
     if (count == 0) return VF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return derr(VF_ERR_NO_DEVICE, "no HIP device visible; libvilfusion has no CPU path");
+    if (int rc = check_device()) return rc;
     vf::DeviceBuf<float> d_h, d_r, d_t;
     vf::DeviceBuf<unsigned char> d_k;
     HIPCHK(d_h.ensure((size_t)count * 36 * sizeof(float)));
