@@ -61,34 +61,15 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
 #define JOUT(r, c) (JRef{sink, (r), (c)})
 
     const State si = load_state(v, b, gk - 1), sj = load_state(v, b, gk);
-    const double dt = IN(0);
-    const V3 dba = si.ba - v3(IN(10), IN(11), IN(12));
-    const V3 dbg = si.bg - v3(IN(13), IN(14), IN(15));
-    // bias-corrected preintegrated delta: d + H (b_i - bhat)   (biasCorrectedDelta)
-    double xt[9];
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-        double s = IN(1 + r);
-        s = fma(IN(16 + r * 6 + 0), dba.x, s);
-        s = fma(IN(16 + r * 6 + 1), dba.y, s);
-        s = fma(IN(16 + r * 6 + 2), dba.z, s);
-        s = fma(IN(16 + r * 6 + 3), dbg.x, s);
-        s = fma(IN(16 + r * 6 + 4), dbg.y, s);
-        s = fma(IN(16 + r * 6 + 5), dbg.z, s);
-        xt[r] = s;
-    }
-    const V3 tht = v3(xt[0], xt[1], xt[2]), pt = v3(xt[3], xt[4], xt[5]), vt = v3(xt[6], xt[7], xt[8]);
-    const M3 Ri = qrot(si.q), Rj = qrot(sj.q);
-    const V3 grav = v3(v.grav[0], v.grav[1], v.grav[2]);
-    const V3 gib = mulT(Ri, grav), vib = mulT(Ri, si.vel);
-    // NavState::correctPIM
-    const V3 xp = pt + dt * vib + (0.5 * dt * dt) * gib;
-    const V3 xv = vt + dt * gib;
-    // NavState::retract -> predicted state j
-    const Q4 eq = qexp(tht);
+    // bias-corrected preintegrated delta, NavState::correctPIM, NavState::retract -> predicted state j
+    const ImuPrediction p = imu_predict(v, si, ImuRecordHbm{in});
+    const double dt = p.dt;
+    const V3 tht = p.tht, pt = p.pt, vt = p.vt;
+    const M3 Ri = p.Ri, Rj = qrot(sj.q);
+    const Q4 eq = p.eq;
     const Q4 qp = qmul(si.q, eq);
-    const V3 pp = si.t + mul(Ri, xp);
-    const V3 vp = si.vel + mul(Ri, xv);
+    const V3 pp = si.t + mul(Ri, p.xp);
+    const V3 vp = si.vel + mul(Ri, p.xv);
     // NavState::localCoordinates(state_j, predicted)
     const V3 rth = qlog(qmul(qconj(sj.q), qp));
     const V3 rp = mulT(Rj, pp - sj.t);

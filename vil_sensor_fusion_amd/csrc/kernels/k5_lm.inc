@@ -200,35 +200,8 @@ __global__ void __launch_bounds__(256) k_reset_lambda(View v, const double* __re
 
 // ------------------------------------------------------------------------------------ a2
 VF_DI State predict_state(const View& v, const State& si, long gk_factor) {
-    const double* in = v.imu_in + (size_t)(gk_factor >> 6) * IMU_IN * TILE + (gk_factor & 63);
-#define IN(f) in[(size_t)(f) * TILE]
-    const double dt = IN(0);
-    const V3 dba = si.ba - v3(IN(10), IN(11), IN(12));
-    const V3 dbg = si.bg - v3(IN(13), IN(14), IN(15));
-    double xt[9];
-    for (int r = 0; r < 9; r++) {
-        double s = IN(1 + r);
-        s = fma(IN(16 + r * 6 + 0), dba.x, s);
-        s = fma(IN(16 + r * 6 + 1), dba.y, s);
-        s = fma(IN(16 + r * 6 + 2), dba.z, s);
-        s = fma(IN(16 + r * 6 + 3), dbg.x, s);
-        s = fma(IN(16 + r * 6 + 4), dbg.y, s);
-        s = fma(IN(16 + r * 6 + 5), dbg.z, s);
-        xt[r] = s;
-    }
-#undef IN
-    const M3 Ri = qrot(si.q);
-    const V3 grav = v3(v.grav[0], v.grav[1], v.grav[2]);
-    const V3 gib = mulT(Ri, grav), vib = mulT(Ri, si.vel);
-    const V3 xp = v3(xt[3], xt[4], xt[5]) + dt * vib + (0.5 * dt * dt) * gib;
-    const V3 xv = v3(xt[6], xt[7], xt[8]) + dt * gib;
-    State o;
-    o.q = qnormalize(qmul(si.q, qexp(v3(xt[0], xt[1], xt[2]))));
-    o.t = si.t + mul(Ri, xp);
-    o.vel = si.vel + mul(Ri, xv);
-    o.ba = si.ba;
-    o.bg = si.bg;
-    return o;
+    const ImuRecordHbm rec = {v.imu_in + (size_t)(gk_factor >> 6) * IMU_IN * TILE + (gk_factor & 63)};
+    return predicted_state(si, imu_predict(v, si, rec));
 }
 
 // window < 0: all windows (one lane each)

@@ -6,8 +6,9 @@
 // the raw samples steps[off[w] .. off[w + 1]) that follow its last keyframe i = hi[w] - 1:
 //   (a) integrate them as K0's ingest form does -- the bias of keyframe i in the current buffer, the same step update in the same
 //       accumulation order: mean, 9 x 6 bias Jacobians, 15 x 15 covariance P (no reverse Cholesky: P itself is wanted);
-//   (b) predict the state with the arithmetic of predict_state (k5_lm.inc), from keyframe i of the current buffer or, from_estimate,
-//       of the trial buffer (reference-compat engines: the estimate, as k_predict(from_trial));
+//   (b) predict the state by imu_predict, as k_predict does, the record's words taken from where they are (registers, sH), from
+//       keyframe i of the current buffer or, from_estimate, of the trial buffer (reference-compat engines: the estimate, as
+//       k_predict(from_trial));
 //   (c) with_cov: Sigma+ = B^-1 (A Sigma_ii A^T + P) B^-T, A and B the unwhitened Jacobians of the combined-IMU factor's residual
 //       with respect to keyframe i and the predicted keyframe j (the closed forms of linearize_imu_core at x_j = predicted: r_theta = 0,
 //       L = I, R_j^T R_i = E^T), Sigma_ii the block the last vf_engine_marginals_ex left.  B = -diag(I, I, R_j^T, I, I): its inverse
@@ -15,15 +16,6 @@
 // F, P, Sigma, A and the products live in LDS (5 x 225 + 2 x 54 doubles, 9.9 KB), thread (i, j) owns entry (i, j); no scratch (pick9).
 // No samples: the keyframe's state and Sigma_ii are copied, bit for bit -- F = I, P = 0 pass through no arithmetic.
 // out: [B][16 + 225].  A window whose marginals failed (sig_failed) gets a NaN covariance and a valid state; an empty window NaNs.
-// entry k of a 3 x 3 matrix held in registers, k known only at run time: selects on nine values loaded unconditionally (indexing
-// the array, or loading inside the selects' arms, keeps the matrix in scratch: K0's 368 bytes per lane)
-VF_DI double pick9(const M3& A, int k) {
-    const double a0 = A.a[0], a1 = A.a[1], a2 = A.a[2], a3 = A.a[3], a4 = A.a[4], a5 = A.a[5], a6 = A.a[6], a7 = A.a[7], a8 = A.a[8];
-    const double r0 = k == 1 ? a1 : (k == 2 ? a2 : a0);
-    const double r1 = k == 4 ? a4 : (k == 5 ? a5 : a3);
-    const double r2 = k == 7 ? a7 : (k == 8 ? a8 : a6);
-    return k < 3 ? r0 : (k < 6 ? r1 : r2);
-}
 __global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict__ off, const double* __restrict__ steps, ImuCov prm,
                                                   int with_cov, int from_estimate, const double* __restrict__ sig,
                                                   const int* __restrict__ sig_failed, double* __restrict__ out) {
@@ -121,34 +113,12 @@ __global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict
         dtij += dt;
         __syncthreads();
     }
-    // (b) the state: predict_state with the record's words taken from where they are (registers, sH)
+    // (b) the state (b_i - bhat is zero unless from_estimate)
     const State si = load_state(v, bs, gk);
-    const V3 dba = si.ba - bacc, dbg = si.bg - bgyr;          // (zero unless from_estimate)
     const double mean[9] = {th.x, th.y, th.z, pos.x, pos.y, pos.z, vel.x, vel.y, vel.z};
-    double xt[9];
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-        double s = mean[r];
-        s = fma(sH[r * 6 + 0], dba.x, s);
-        s = fma(sH[r * 6 + 1], dba.y, s);
-        s = fma(sH[r * 6 + 2], dba.z, s);
-        s = fma(sH[r * 6 + 3], dbg.x, s);
-        s = fma(sH[r * 6 + 4], dbg.y, s);
-        s = fma(sH[r * 6 + 5], dbg.z, s);
-        xt[r] = s;
-    }
-    const V3 tht = v3(xt[0], xt[1], xt[2]), pt = v3(xt[3], xt[4], xt[5]), vt = v3(xt[6], xt[7], xt[8]);
-    const M3 Ri = qrot(si.q);
-    const V3 grav = v3(v.grav[0], v.grav[1], v.grav[2]);
-    const V3 gib = mulT(Ri, grav), vib = mulT(Ri, si.vel);
-    const V3 xp = pt + dtij * vib + (0.5 * dtij * dtij) * gib;
-    const V3 xv = vt + dtij * gib;
-    State sj;
-    sj.q = qnormalize(qmul(si.q, qexp(tht)));
-    sj.t = si.t + mul(Ri, xp);
-    sj.vel = si.vel + mul(Ri, xv);
-    sj.ba = si.ba;
-    sj.bg = si.bg;
+    const ImuPrediction p =
+        imu_predict(v, si, [&](int f) { return f == 0 ? dtij : (f < 10 ? mean[f - 1] : (f < 16 ? bh[f - 10] : sH[f - 16])); });
+    const State sj = predicted_state(si, p);
     if (tid == 0) {
         o[0] = sj.q.w; o[1] = sj.q.x; o[2] = sj.q.y; o[3] = sj.q.z;
         o[4] = sj.t.x; o[5] = sj.t.y; o[6] = sj.t.z;
@@ -163,20 +133,20 @@ __global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict
     // (c) A (DESIGN.md "K1" at r_theta = 0) into sA, Sigma_ii into sS
     if (tid < 225) {
         const M3 Rj = qrot(sj.q);
-        const M3 Rji = mulTA(Rj, Ri);              // R_j^T R_i
+        const M3 Rji = mulTA(Rj, p.Ri);             // R_j^T R_i
         const int bi = i / 3, r = i - bi * 3, bj = j / 3, c = j - bj * 3;
         double x = 0.0;
         if (i >= 9) x = i == j ? 1.0 : 0.0;        // bias rows: b_i - b_j
         else if (j < 9) {
             if (bj == 0) {
-                const M3 X = bi == 0 ? transpose(qrot(qexp(tht))) : mulSkew(Rji, neg(bi == 1 ? pt : vt));   // E^T, -R_ji [p~]x, -R_ji [v~]x
+                const M3 X = bi == 0 ? transpose(qrot(qexp(p.tht))) : mulSkew(Rji, neg(bi == 1 ? p.pt : p.vt));   // E^T, -R_ji [p~]x, -R_ji [v~]x
                 x = pick9(X, r * 3 + c);
             } else if (bj == 1) x = bi == 1 ? pick9(Rji, r * 3 + c) : 0.0;
-            else x = bi == 1 ? dtij * pick9(Rj, c * 3 + r) : (bi == 2 ? pick9(Rj, c * 3 + r) : 0.0);
+            else x = bi == 1 ? p.dt * pick9(Rj, c * 3 + r) : (bi == 2 ? pick9(Rj, c * 3 + r) : 0.0);
         } else {
             const int cb = j - 9;
             const V3 h = v3(sH[(bi * 3 + 0) * 6 + cb], sH[(bi * 3 + 1) * 6 + cb], sH[(bi * 3 + 2) * 6 + cb]);
-            x = vget(bi == 0 ? mul(so3_jr(tht), h) : mul(Rji, h), r);
+            x = vget(bi == 0 ? mul(so3_jr(p.tht), h) : mul(Rji, h), r);
         }
         sA[tid] = x;
         sS[tid] = sg[i >= j ? h_tri(i, j) : h_tri(j, i)];

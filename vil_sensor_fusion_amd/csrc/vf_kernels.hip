@@ -122,6 +122,7 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
     }
 }
 
+#include "kernels/imu_common.inc"
 #include "kernels/k0_preintegrate.inc"
 #include "kernels/k12_linearize.inc"
 #include "kernels/far.inc"
