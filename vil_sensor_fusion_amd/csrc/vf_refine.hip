@@ -265,7 +265,12 @@ __global__ void __launch_bounds__(64) k_pcg_scalar(View v, Refine q, int mode, d
         const bool first = rz < 0.0;
         // stop: the preconditioned residual has lost rel_stop^2 of its first value, or is no longer positive (rounding floor,
         // or a correction solve that failed)
-        if (!(s > 0.0) || (!first && s <= rel_stop * rel_stop * rz0)) { q.stop[w] = 1; return; }
+        // (a value the rule stops at belongs to the x that stays: it is what vf_engine_read_refine reports as the reduction)
+        if (!(s > 0.0) || (!first && s <= rel_stop * rel_stop * rz0)) {
+            if (s > 0.0) q.rz[w] = s;
+            q.stop[w] = 1;
+            return;
+        }
         q.coef[w] = first ? 0.0 : s / rz;
         q.first[w] = first ? 1 : 0;
         q.rz[w] = s;

@@ -344,13 +344,25 @@ class LockstepGroup:
             for s in self.solvers:
                 s.eng.refine_end()
 
-    def iterate(self, iterations: int):
+    # the three parts of iterate(), for callers that look at one solve between them (its increment, its refinement)
+    def begin(self):
         for s in self.solvers:
             s.begin()
+
+    def solve(self):
+        """one staged solve of all shards, the refinement included; the increments stay in the engines (read_delta)"""
+        self._solve()
+
+    def finish(self):
+        """retraction, linearisation of the trial, decision -- on every shard"""
+        for s in self.solvers:
+            s.phase_finish()
+
+    def iterate(self, iterations: int):
+        self.begin()
         for _ in range(iterations):
-            self._solve()
-            for s in self.solvers:
-                s.phase_finish()
+            self.solve()
+            self.finish()
         for s in self.solvers:
             s.eng.close_excursions()
 
@@ -358,6 +370,6 @@ class LockstepGroup:
         """one reference-compat update on every shard (ShardedSolver.gn_step)"""
         for s in self.solvers:
             s.eng.gn_begin(relin_threshold)
-        self._solve()
+        self.solve()
         for s in self.solvers:
             s.eng.retract()
