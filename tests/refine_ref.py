@@ -296,13 +296,14 @@ def operator(rw: Rows, lam):
     return lambda p: Jt @ (J @ p) + L @ p + lam * p
 
 
-def preconditioner(oracle, case: Case, rw: Rows, lam=LAMBDA):
+def preconditioner(oracle, case: Case, rw: Rows, lam=LAMBDA, normal=None):
     """(v -> M^-1 v, g (15 n,), H band, U dense or None): M = H + lambda I + U^T U, U the far factors' rows; g with their
-    J^T r.  The band part is oracle.band_solve.  With far factors M^-1 v = y - Z (I + U Z)^-1 U y, y = B^-1 v, Z = B^-1 U^T,
+    J^T r.  The band part is oracle.band_solve; normal = (H, g) is another evaluation of it than normal_equations
+    (tests/direct_ref.py).  With far factors M^-1 v = y - Z (I + U Z)^-1 U y, y = B^-1 v, Z = B^-1 U^T,
     B = H + lambda I: the inverse of the dense M (tests/test_refine_ref_host.py holds it to that), evaluated the way the
     engine does and without BLAS -- a LAPACK Cholesky of the dense M changes its summation order with the thread count, and
     case F's figure with it (1.77e-8 with eight threads, 1.34e-8 with one)"""
-    H, g = normal_equations(oracle, case)
+    H, g = normal_equations(oracle, case) if normal is None else normal
     g = g.ravel().copy()
 
     def bsolve(v):
@@ -380,6 +381,8 @@ def twin_rows(case: Case, rw: Rows) -> Rows:
     lin = prob.linearize()
     J, r = rw.J.copy(), rw.r.copy()
     for kind, w in (("imu", 15), ("btw", 6)):
+        if not rw.find(kind):                   # (a window of two keyframes has no between factor and the twin no "btw")
+            continue
         rt, Jt = lin[kind]
         for f, (_, a, b, r0, nr) in enumerate(rw.find(kind)):
             if kind == "btw":

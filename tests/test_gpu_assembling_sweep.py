@@ -8,7 +8,9 @@ oracle it is held to the same bars as every other form.  Covered here: ragged wi
 all eight positions of a J-stream tile (slides), marginalised slides (6 x 15 strip of the marginal prior), a prior on
 a keyframe in the middle of the window, windows without any between factor and with factors reaching back 1, 2 and 3
 keyframes, vf_engine_read_normal on such an engine, and the cases in which the engine must NOT use the form (far
-factors; the partitioned half of the termination rule's hybrid solve), where it has to give the bits of the two-kernel path."""
+factors; the partitioned half of the termination rule's hybrid solve), where it has to give the bits of the two-kernel path.
+(worst_d <= 1e-4 below compares two forms loosely, on an H this form never stores; its increment is held to the exact least-squares
+reference in tests/test_gpu_direct_small.py.)"""
 import numpy as np
 import pytest
 
