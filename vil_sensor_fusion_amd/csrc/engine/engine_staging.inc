@@ -117,6 +117,7 @@ int vf_engine_set_imu(vf_engine* e, int window, int k0, int n, const double* rec
     if ((rc = e->ensure_stage(bytes))) return rc;
     HIPCHK(hipMemcpyAsync(e->stage, rec, bytes, hipMemcpyHostToDevice, e->stream));
     vf::launch_scatter(e->stage, e->v.imu_in, (long)window * e->v.M + k0, n, vf::IMU_IN, e->stream);
+    vf::launch_fixed_jwords(e->v, (long)window * e->v.M + k0, n, e->stream);    // (the records' own words of the J stream: K1 does not write them)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
     return VF_OK;

@@ -443,6 +443,10 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
     e->epoch++;
     // the linearisation of the current states is part of the state other entry points rely on (vf_engine_marginalize reads
     // the Jacobians of the oldest keyframe's factors): recompute it in the new buffers
+    // (imu_in came over, imu_j did not: the words of the J stream that are the records' own, for every slot -- a record may sit
+    // beyond a window's end, preintegrated and not yet appended -- in front of the linearisation that writes the rest)
+    vf::launch_fixed_jwords(e->v, 0, e->v.G, e->stream);
+    HIPCHK(hipGetLastError());
     bool any = false;
     for (int w = 0; w < e->v.B; w++) any = any || e->h_hi[w] > e->h_lo[w];
     if (any && (rc = vf_engine_linearize(e, 0))) return rc;

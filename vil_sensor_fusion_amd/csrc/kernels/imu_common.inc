@@ -68,3 +68,28 @@ struct ImuRecordHbm {
     const double* __restrict__ in;
     VF_DI double operator()(int f) const { return in[(size_t)f * TILE]; }
 };
+
+// ------------------------------------------------------------------------------------ fixed words of the J stream
+// Word t (0 .. JS_NJF - 1) of the j side's fixed words of the factor in slot gk (vf_jstream.hpp): entry (row, col) of J with col
+// in X_j.p (12..14) or B_j (24..29), which is -R(row, col - 9) resp. -R(row, col - 15) of the record's square-root information
+// whatever the states are.  Written into BOTH buffers of imu_j -- K1 writes neither -- by whoever writes the record: K0 from the
+// R it has just made, k_fixed_jwords from the record where a record arrives by another road (vf_engine_set_imu,
+// vf_engine_grow).  One thread per word; sqrt_info(row, col) answers R, row <= col.  The negation is the one K1 made (exact).
+template <class SqrtInfo>
+VF_DI void write_fixed_jwords(const View& v, const long gk, const int t, const SqrtInfo& sqrt_info) {
+    const int e = JS_NJV + t, f = JMD.fld[2 * JS_PI + e];
+    const int row = f / 30, col = f - row * 30;
+    const double x = -sqrt_info(row, col < 24 ? col - 9 : col - 15);
+    const size_t word = (size_t)(gk >> JT_LOG) * JT_STRIDE + ((size_t)(JS_PI + (e >> 1)) * JT + (gk & (JT - 1))) * 2 + (e & 1);
+    v.imu_j[word] = x;
+    v.imu_j[(size_t)(v.G >> JT_LOG) * JT_STRIDE + word] = x;
+}
+// ... for the factors in slots [g0, g0 + n), from their records in v.imu_in
+__global__ void __launch_bounds__(256) k_fixed_jwords(View v, long g0, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * JS_NJF) return;
+    const long gk = g0 + i / JS_NJF;
+    const int t = (int)(i % JS_NJF);
+    const double* __restrict__ in = v.imu_in + (size_t)(gk >> 6) * IMU_IN * TILE + (gk & 63);
+    write_fixed_jwords(v, gk, t, [in](int row, int col) { return in[(size_t)(70 + off15(row) + (col - row)) * TILE]; });
+}

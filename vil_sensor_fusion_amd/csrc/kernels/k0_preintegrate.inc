@@ -5,7 +5,8 @@
 // IMU preintegration, one 256-thread workgroup per factor: PreintegratedCombinedMeasurements::
 // integrateMeasurement over the factor's steps (mean, bias Jacobians, 15x15 covariance; GTSAM 4.0.x tangent
 // form), then the noise model R = chol_upper(cov^-1) of the CombinedImuFactor built at
-// gtsam_fusion/src/gtsam_fusion/IMUManager.cpp:68-73.  Runs once per factor (not per LM iteration).
+// gtsam_fusion/src/gtsam_fusion/IMUManager.cpp:68-73.  Runs once per factor (not per LM iteration), and so leaves, beside the
+// record, the 90 words of the factor's Jacobian that are columns of -R whatever the states (write_fixed_jwords, imu_common.inc).
 // F, P and F P live in LDS, thread (i, j) owns entry (i, j) of the 15x15 products; the small 3x3 quantities of a
 // step are computed by every thread.  (The first version ran one LANE per factor with the 15x15 work in per-lane
 // scratch arrays: 2-4 ms whatever the batch, i.e. most of a GraphManager::solve, which preintegrates one factor.)
@@ -162,6 +163,11 @@ __global__ void __launch_bounds__(256) k_preintegrate_t(View v, long g0, int n, 
             x = sT[r * 15 + r + o];
         }
         out[(size_t)tid * TILE] = x;
+    }
+    // ... and the words of the factor's Jacobian that are this R and no state's, into both buffers of the J stream
+    if (tid < JS_NJF) {
+        const double* T = sT;
+        write_fixed_jwords(v, gk, tid, [T](int row, int col) { return T[row * 15 + col]; });
     }
     if (tid == 0 && (!s_ok || off[f + 1] == off[f])) atomicOr(status, 1);
 }

@@ -2,7 +2,8 @@
 // A section of vf_kernels.hip (ONE translation unit: the kernels share device helpers and must inline as they always have);
 // included from there, inside namespace vf, never compiled by itself.
 // ------------------------------------------------------------------------------------ K1
-// Algorithmic traffic per factor: 222 doubles in (2 states x 16, record 190), 465 out.
+// Algorithmic traffic per factor: 222 doubles in (2 states x 16, record 190); out 15 (r) + 202 (101 pairs of J: the 90 words of
+// J that do not depend on the states are in the stream since the record was written, write_fixed_jwords) = 3 512 B with the input.
 constexpr int K1_BLOCK = 256, K1_WAVES = 1;     // launch bounds of the linearisation kernels: threads per block, waves per execution unit
 VF_DI const double* jtile_ptr(const double* base, long gk) { return base + (size_t)(gk >> JT_LOG) * JT_STRIDE; }
 // entry (row, col) of the Jacobian of the factor in slot gk of a J stream buffer (0 for a structural zero)
@@ -15,8 +16,10 @@ VF_DI double jstream_entry(const double* jbuf, long gk, int row, int col) {
 
 // Where a factor's (r | J) goes.  K1: r into the AoSoA residual array, J into the factor's slot of its J-stream tile as
 // 16-byte non-temporal stores of two consecutive entries (write-once streams far beyond L2 / MALL: +15 % measured for
-// non-temporal).  (A copy of the i-side pairs of a tile's first factor into the tile in front of it, so that K3 would
-// find its halo factor in its own block, cost K1 0.48 ms: 16-byte partial-line writes.  K3 reads the halo where it is.)
+// non-temporal): the 74 pairs of the i side and the first 27 = JS_NJV / 2 of the j side -- the 45 pairs behind them are the
+// record's, not the states' (vf_jstream.hpp), and are not K1's to write.  (A copy of the i-side pairs of a tile's first
+// factor into the tile in front of it, so that K3 would find its halo factor in its own block, cost K1 0.48 ms: 16-byte
+// partial-line writes.  K3 reads the halo where it is.)
 // `jac` = false (time-sharded windows, factors this rank does not assemble): residual only.
 struct HbmSink {
     // The 9x6 bias Jacobians of the record are used twice (bias-corrected delta, bias columns of J) and the second read
@@ -133,10 +136,7 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
         white9<0, 9>(R, u, o);
 #pragma unroll
         for (int a = 0; a < 9; a++) JOUT(a, 9 + c) = o[a];
-        // X_j.p : rows p = -I  => -R11(:, 3+c)
-#pragma unroll
-        for (int a = 0; a < 9; a++)
-            if (a <= 3 + c) JOUT(a, 12 + c) = -R[idx9(a < 3 + c ? a : 3 + c, 3 + c)];   // rows below: structural zeros
+        // X_j.p : rows p = -I  => -R11(:, 3+c): fixed words of the record, in the stream since the record was written
         // V_j : rows v = -R_j^T
 #pragma unroll
         for (int r = 0; r < 3; r++) { u[r] = 0; u[3 + r] = 0; u[6 + r] = -Rj.a[c * 3 + r]; }
@@ -167,8 +167,7 @@ __device__ __forceinline__ void linearize_imu_core(const View& v, const int b, c
         for (int a = 0; a < 15; a++) {
             const double bi = (a < 9) ? o[a] + Rc[a] : Rc[a];
             if (a < n_rc) {                       // rows >= 10 + c: structural zeros
-                JOUT(a, 18 + c) = bi;
-                JOUT(a, 24 + c) = -Rc[a];
+                JOUT(a, 18 + c) = bi;                     // (B_j = -Rc: fixed words, like X_j.p)
             }
             rw[a] = fma(Rc[a], rb, rw[a]);
         }

@@ -267,6 +267,9 @@ void launch_shift_btw_a(int* a, long G, int M, int shift, hipStream_t s) {
 void launch_scatter(const double* aos, double* aosoa, long g0, long n, int nf, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_scatter, dim3(nblk(n * nf, 256)), dim3(256), 0, s, aos, aosoa, g0, n, nf);
 }
+void launch_fixed_jwords(const View& v, long g0, long n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_fixed_jwords, dim3(nblk(n * JS_NJF, 256)), dim3(256), 0, s, v, g0, n);
+}
 void launch_gather(const double* aosoa, double* aos, long g0, long n, int nf, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_gather, dim3(nblk(n * nf, 256)), dim3(256), 0, s, aosoa, aos, g0, n, nf);
 }

@@ -29,7 +29,9 @@ class SolveMemory {
     // ---- events.  lo / hi: window 0's range as it is when the event fires (the engine's own mirror, passed in, not kept here)
     // something the bookkeeping cannot follow was written: the next solve / update / marginalisation starts from nothing
     void rewritten() { warm_ = inc_valid_ = ahead_valid_ = false; }
-    // records were written from slot k of window w onwards.  At or beyond the end it is an append; up to LINEARIZE_TAIL_MAX slots
+    // records were written from slot k of window w onwards (an IMU record takes the fixed words of its own slot of the J stream with
+    // it, both buffers, on the stream the record is written on: K0, k_fixed_jwords -- no other slot's words, so what holds for the
+    // record holds for them).  At or beyond the end it is an append; up to LINEARIZE_TAIL_MAX slots
     // inside it (late odometry for a keyframe an earlier solve covered) the warm tail grows; the incremental update follows
     // a write anywhere behind the window's first keyframe.  Everything else is rewritten().
     void written_from(int w, int k, int lo, int hi) {

@@ -17,6 +17,10 @@ constexpr int IMU_OUT = 465;    // r(15), J(15x30 row-major): the documented (ho
 //          (144 = 72 pairs), stored as [pair][8 slots][2 doubles].  A K1 store instruction is 16 bytes per lane = 8 full
 //          128-B lines (146 of them per factor instead of 291 8-byte ones); a K3 workgroup copies ONE contiguous 18.7 KB
 //          block into LDS as it is, plus the i-side pairs of its halo factor (slot 0 of the next tile).
+//          The last 45 pairs of the j side (X_j.p and B_j: 90 words, the negated columns 3..5 and 9..14 of the record's
+//          square-root information) do not depend on the states.  They are written into both buffers when the record is
+//          (K0, or k_fixed_jwords behind vf_engine_set_imu / vf_engine_grow) and K1 stores the other 101 pairs only: with its
+//          222 input words and the residual it moves 3 512 B per factor instead of 4 232.
 constexpr int IMU_R = 15;
 constexpr int JT_LOG = 3, JT = 1 << JT_LOG; // keyframe slots per J tile (= K3's tile): 8
 constexpr int JS_NI = 147, JS_NJ = 144;             // non-zero entries of the i-side / j-side columns
@@ -379,6 +383,9 @@ void launch_shift_btw_a(int* a, long G, int M, int shift, hipStream_t s);
 // AoS <-> AoSoA staging
 void launch_scatter(const double* aos, double* aosoa, long g0, long n, int nf, hipStream_t s);
 void launch_gather(const double* aosoa, double* aos, long g0, long n, int nf, hipStream_t s);
+// the words of the J stream that are the record's alone (imu_j above), both buffers, of the IMU records in slots [g0, g0 + n):
+// behind every write of imu_in that is not K0's (which writes them itself)
+void launch_fixed_jwords(const View& v, long g0, long n, hipStream_t s);
 void launch_scatter_states(const double* aos, double* x, long G, int buf, long g0, long n, hipStream_t s);
 // the documented (r | J) records of IMU factors [g0, g0 + n) of buffer b, AoS [n][465], from imu_r / imu_j
 void launch_gather_imu_lin(const View& v, int b, long g0, long n, double* aos, hipStream_t s);
