@@ -555,6 +555,83 @@ int vf_engine_marginal_scores(vf_engine* e, int source, int metric, unsigned sub
  * vf_engine_marginal_scores (its metric and mask), for keyframes k0 .. k0+n-1.  VF_ERR_INVALID: no scores since the last
  * vf_engine_marginals_ex; VF_ERR_BAD_KEY: outside the range the marginals were computed for; VF_ERR_NOT_SPD: a failed window. */
 int vf_engine_read_marginal_scores(vf_engine* e, int window, int k0, int n, double* out);
+/* Per-factor chi-square errors and a consistency summary (no reference code: the counterpart of NonlinearFactor::error,
+ * NonlinearFactorGraph::error and printErrors, which the reference never calls).  The error of a factor is e = 0.5 |r|^2 of its
+ * whitened residual r at the window's current states (what vf_engine_get_states returns: the estimate of an LM engine, the
+ * linearisation points theta of a reference-compat one); the errors of a window add up to the cost vf_engine_read_lm reports.
+ * Enqueues one launch over every window (kernels/kerr.inc) and one over their summaries.
+ *   flags = 0: the residuals the last solve left in the current buffer are read as they lie, provided the engine can vouch that
+ *     they are of the current states -- nothing has been written since a vf_engine_iterate, vf_engine_isam_step,
+ *     vf_engine_linearize(e, 0) or vf_engine_marginals_ex ended, other than records at or beyond the end of a one-window engine's
+ *     window.  Such a call touches nothing but its own buffer: warm start, the marginal prior computed ahead, the cached result
+ *     block, covariances and scores are as they were.
+ *   VF_ERRORS_RELINEARIZE, or an engine that cannot vouch (always: engines with lm_excursion active or incremental != 0): every
+ *     factor is first linearised at the current states, as vf_engine_marginals does -- the same bits into the same buffer, LM state
+ *     untouched, engine marked cold (the next vf_engine_iterate gives the bits it would have given without the call).
+ * chi2_threshold6 (may be NULL: nothing is flagged): per class, a factor counts as flagged when 2 e exceeds the class's threshold; an
+ * entry that is not a finite positive number flags nothing in its class.
+ * The results live in a device buffer of their own (16 B per keyframe slot, 2 x max_far_factors doubles and one summary per window),
+ * made by the first call.  They are of the call that wrote them: later solves leave them readable, the next call replaces them,
+ * vf_engine_compact and vf_engine_grow void them.  VF_ERR_INVALID: unknown flags, time-sharded engines. */
+#define VF_ERRORS_RELINEARIZE 1u
+#define VF_FACTOR_IMU 0
+#define VF_FACTOR_BETWEEN 1
+#define VF_FACTOR_PRIOR 2
+#define VF_FACTOR_MARGINAL_PRIOR 3
+#define VF_FACTOR_FAR 4
+#define VF_FACTOR_FAR_LINEAR 5
+#define VF_FACTOR_CLASSES 6
+#define VF_CONSISTENCY_NONFINITE 1u /* vf_consistency.status: some factor's error is not finite */
+#define VF_CONSISTENCY_FLAGGED 2u   /* ... some factor is flagged */
+#define VF_CONSISTENCY_EMPTY 4u     /* ... the window holds no keyframe */
+/* One window's summary, per class VF_FACTOR_*: the number of factors, the sum of their errors, the largest and where it sits (a
+ * keyframe slot for classes 0 .. 3 -- the slot a band factor ends at, the prior's slot, the window's first slot for the marginal
+ * prior --, an index of vf_engine_read_far_errors for classes 4 and 5; the lowest of a tie; max = -1 and argmax = -1 when there is
+ * none), how many are flagged, how many are not finite.  Errors that are not finite are counted in nonfinite and enter neither
+ * sum nor max.  total: the six sums added in class order.  rows: whitened rows, 15, 6, 15, 27, 6 and 6 per factor by class;
+ * unknowns = 15 x keyframes.  A plain output struct: the caller fills struct_size (sizeof), the library writes no byte beyond it;
+ * 0 or a size larger than the library's is VF_ERR_INVALID.  Grows at the end only. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t status;           /* VF_CONSISTENCY_* bits */
+    int32_t count[6];
+    int32_t argmax[6];
+    int32_t flagged[6];
+    int32_t nonfinite[6];
+    double sum[6];
+    double max[6];
+    double total;
+    int32_t keyframes;
+    int32_t rows;
+    int32_t unknowns;
+    int32_t reserved;
+} vf_consistency;
+/* The whole batch, from the summaries and the LM words at the time of the call (the lifetime counters of vf_engine_read_lm): windows
+ * that are empty; with n_fail > 0; whose cost or any factor's error is not finite; non-empty ones that never accepted a trial; with
+ * a flagged factor; and the window with the largest reduced chi-square 2 total / max(rows - unknowns, 1) (the lowest of a tie; -1
+ * and 0.0 if every window is empty).  struct_size as in vf_consistency. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t windows;
+    int32_t empty;
+    int32_t failed;
+    int32_t nonfinite;
+    int32_t never_accepted;
+    int32_t flagged_windows;
+    int32_t worst_window;
+    double worst_reduced_chi2;
+} vf_batch_health;
+int vf_engine_factor_errors(vf_engine* e, unsigned flags, const double* chi2_threshold6);
+/* ... read back (synchronises): for keyframe slots k0 .. k0+n-1 of the range the call saw, the error of the IMU factor and of the
+ * band between factor ending at each slot (-1: none -- the window's first slot has no IMU factor) and the slot that between factor
+ * starts from (-1: none).  Any pointer may be NULL.  VF_ERR_INVALID: no vf_engine_factor_errors since the engine was made, compacted
+ * or grown; VF_ERR_BAD_KEY: outside that range. */
+int vf_engine_read_factor_errors(vf_engine* e, int window, int k0, int n, double* imu_err, double* btw_err, int32_t* btw_a);
+/* ... the far factors' errors, max_far_factors entries each (vf_engine_opts; 8 by default): far_err[i] of entry i of the window's
+ * list (vf_engine_get_extra_between), far_linear_err[s] of far end s of its linear far factor (vf_engine_get_linear_far); -1: none */
+int vf_engine_read_far_errors(vf_engine* e, int window, double* far_err, double* far_linear_err);
+int vf_engine_read_consistency(vf_engine* e, int window, vf_consistency* out);
+int vf_engine_read_health(vf_engine* e, vf_batch_health* out);
 int vf_engine_read_lm(vf_engine* e, int window, double* cost, double* lambda, int* accepted,
                       int* rejected, int* solve_failures);
 /* non-monotone LM: trials kept provisionally so far (not counted in accepted / rejected), and whether an excursion is open */
@@ -755,6 +832,18 @@ int vf_get_marginal_covariance(vf_graph* g, uint64_t key, double cov225[225]);
  * yet they are computed with VF_MARGINALS_POSE (and VF_MARGINALS_FAR under vf_graph_opts.far_covariance), then the scores
  * (vf_engine_marginal_scores); vf_solve and vf_set_initial_state void them.  Refusals and lock rule as vf_get_marginal_covariance. */
 int vf_get_degeneracy_scores(vf_graph* g, int source, int metric, unsigned subset_mask, uint64_t key0, int n, double* out);
+/* factor->error(values) of the factors of the last solve (vf_engine_factor_errors; reference-compat handles: at the linearisation
+ * points): for keys key0 .. key0+n-1 the error 0.5 |r|^2 of the IMU factor X(key-1) -> X(key) and of the band between factor ending
+ * at the key (-1: none), and the key that between factor starts from (UINT64_MAX: none).  Any output may be NULL.  The first call
+ * after a solve computes, from the residuals the solve left, later ones read; vf_solve and vf_set_initial_state void the result.
+ * A vf_reserve_node in between changes nothing.  Loop closures (far factors) are not keyed by their end: their errors are read
+ * through the engine call, vf_engine_read_far_errors; they are part of vf_get_consistency.  VF_ERR_INVALID before the first solve;
+ * VF_ERR_BAD_KEY for a key not solved yet or gone from the window.  Takes the state lock: never call it from inside a callback. */
+int vf_get_factor_errors(vf_graph* g, uint64_t key0, int n, double* imu_err, double* btw_err, uint64_t* btw_prev_key);
+/* graph.error(values) and printErrors with a threshold: the window's summary by factor class (vf_consistency; argmax in keyframe
+ * slots of the handle's engine).  chi2_threshold6 as in vf_engine_factor_errors; a call with thresholds computes again (the
+ * errors are the same bits), one without reads what the last call since the solve left, its flags included.  Refusals and lock rule as vf_get_factor_errors. */
+int vf_get_consistency(vf_graph* g, const double* chi2_threshold6, vf_consistency* out);
 /* The state at `time`, between two solves: predicted from the last solved key through the steps of every queued, not yet solved
  * IMU factor and then what vf_reserve_node(time) would cut from the IMU buffer at this moment -- which is not consumed
  * (vf_engine_propagate_tail; reference_compat handles predict from the estimate).  cov225 (may be NULL): the propagated covariance,

@@ -7,8 +7,9 @@ benchmark and Python callers; it never computes factor math on the CPU and raise
 library or a GPU is missing.
 """
 from ._lib import VilFusionError, lib, lib_path  # noqa: F401
+from ._lib import CHI2_999, FACTOR_CLASSES  # noqa: F401
 from .engine import Engine, EngineOpts  # noqa: F401
 
-__all__ = ["VilFusionError", "lib", "lib_path", "Engine", "EngineOpts"]
+__all__ = ["VilFusionError", "lib", "lib_path", "Engine", "EngineOpts", "CHI2_999", "FACTOR_CLASSES"]
 from .graph_manager import GraphManager  # noqa: F401,E402
 from .sensor_manager import SensorManager  # noqa: F401,E402

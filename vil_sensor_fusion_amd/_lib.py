@@ -58,8 +58,30 @@ class GraphOptsC(C.Structure):
                 ("synchronous_staging", C.c_int), ("max_far_factors", C.c_int), ("far_covariance", C.c_int)]
 
 
+class ConsistencyC(C.Structure):
+    """one window's summary of its factors' chi-square errors by class (include/vilfusion.h vf_consistency); the caller fills struct_size"""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("count", C.c_int32 * 6), ("argmax", C.c_int32 * 6),
+                ("flagged", C.c_int32 * 6), ("nonfinite", C.c_int32 * 6), ("sum", C.c_double * 6), ("max", C.c_double * 6),
+                ("total", C.c_double), ("keyframes", C.c_int32), ("rows", C.c_int32), ("unknowns", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BatchHealthC(C.Structure):
+    """the whole batch at the time of vf_engine_factor_errors (vf_batch_health); the caller fills struct_size"""
+    _fields_ = [("struct_size", C.c_uint32), ("windows", C.c_int32), ("empty", C.c_int32), ("failed", C.c_int32),
+                ("nonfinite", C.c_int32), ("never_accepted", C.c_int32), ("flagged_windows", C.c_int32), ("worst_window", C.c_int32),
+                ("worst_reduced_chi2", C.c_double)]
+
+
 CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                        C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+ERRORS_RELINEARIZE = 1   # vf_engine_factor_errors: linearise every factor at the current states first (VF_ERRORS_RELINEARIZE)
+FACTOR_CLASSES = ("imu", "between", "prior", "marginal_prior", "far", "far_linear")    # VF_FACTOR_*, in id order
+FACTOR_ROWS = (15, 6, 15, 27, 6, 6)                                                    # whitened rows of a factor, by class
+CONSISTENCY_NONFINITE, CONSISTENCY_FLAGGED, CONSISTENCY_EMPTY = 1, 2, 4                # vf_consistency.status
+# 0.999 quantiles of the chi-square distribution by degrees of freedom: a threshold on 2 e for a factor of that many rows
+# (scipy.stats.chi2.ppf(0.999, k); constants, the package does not import scipy)
+CHI2_999 = {6: 22.4577, 15: 37.6973, 27: 55.4760}
 
 MARGINALS_FAR = 1        # vf_engine_marginals_ex: take far factors alive into account (VF_MARGINALS_FAR)
 MARGINALS_POSE = 2       # ... leave the nav_msgs pose covariance, its inverse and the pose of every keyframe on the device (VF_MARGINALS_POSE)
@@ -85,6 +107,7 @@ SYMBOLS = [
     "vf_engine_read_imu_lin", "vf_engine_read_between_lin", "vf_engine_read_normal",
     "vf_engine_read_delta", "vf_engine_read_panels", "vf_engine_read_lm", "vf_engine_marginals", "vf_engine_marginals_ex", "vf_engine_read_marginals",
     "vf_engine_read_pose_marginals", "vf_engine_marginal_scores", "vf_engine_read_marginal_scores",
+    "vf_engine_factor_errors", "vf_engine_read_factor_errors", "vf_engine_read_far_errors", "vf_engine_read_consistency", "vf_engine_read_health",
     "vf_engine_time_stage", "vf_engine_time_iterate", "vf_engine_counts",
     "vf_engine_preintegrate", "vf_engine_get_imu", "vf_engine_ingest_tail", "vf_engine_ingest_status",
     "vf_engine_propagate_tail", "vf_engine_read_propagated", "vf_engine_propagate_status",
@@ -97,7 +120,7 @@ SYMBOLS = [
     "vf_engine_isam_step", "vf_engine_predict_from_estimate", "vf_engine_get_estimate", "vf_engine_incremental_info", "vf_engine_set_async", "vf_engine_read_result", "vf_engine_marginalize_ahead",
     "vf_graph_default_opts", "vf_graph_default_opts_sized", "vf_create", "vf_destroy", "vf_add_imu", "vf_reserve_node",
     "vf_add_between", "vf_solve", "vf_get_state", "vf_get_bias", "vf_most_recent_pose_time",
-    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_predict_state", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
+    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_predict_state", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
     "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged",
     "vf_degeneracy_batch", "vf_degeneracy_spectrum_batch", "vf_degeneracy_scores_batch", "vf_dopt_filter_f32",
 ]
@@ -125,6 +148,9 @@ def lib():
         l.vf_engine_propagate_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]
         l.vf_predict_state.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.vf_get_degeneracy_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.c_int, C.c_void_p]
+        l.vf_engine_factor_errors.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
+        l.vf_get_factor_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.vf_get_consistency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

@@ -65,6 +65,7 @@ int vf_engine_isam_step(vf_engine* e, double relin_threshold) {
         (rc = vf_engine_solve(e)) || (rc = vf_engine_retract(e))) return rc;
     if ((rc = first_failed_window(e))) return rc;
     e->mem.rewritten();
+    e->mem.residuals_current();     // (linearised at theta by vf_engine_gn_begin; the solve and the retraction wrote the trial buffer)
     return VF_OK;
 }
 int vf_engine_incremental_info(vf_engine* e, int window, long* updates, long* whole_window_updates, int* first_eliminated, int* last_substituted) {

@@ -245,6 +245,7 @@ static int create_engine(const vf_engine_opts* o_in, const vf_engine_tuning* t_i
     e->graph_off = t->use_hip_graph == 0;
     e->mem.one_window = v.B == 1;
     e->mem.no_warm = o->cold_start != 0;
+    e->mem.incremental = o->incremental != 0;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->h_lo.assign(v.B, 0);
     e->h_hi.assign(v.B, 0);

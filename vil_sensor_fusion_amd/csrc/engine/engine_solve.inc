@@ -222,6 +222,7 @@ static int close_excursions(vf_engine* e) {
 }
 static int decide(vf_engine* e, int init) {
     e->v.nm_W = e->excursion();
+    e->mem.excursions = e->v.nm_W > 0;       // (such trials restore states without their residuals: SolveMemory::residuals_vouched)
     if (e->v.nm_W > 0)
         if (int rc = e->ensure_excursion()) return rc;
     vf::launch_decide(e->v, init ? 1 : 0, e->stream);
@@ -235,7 +236,12 @@ static int decide(vf_engine* e, int init) {
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
-int vf_engine_linearize(vf_engine* e, int which) { VF_ENTER(e, Entry::rewrites); return linearize(e, which); }
+int vf_engine_linearize(vf_engine* e, int which) {
+    VF_ENTER(e, Entry::rewrites);
+    const int rc = linearize(e, which);
+    if (rc == VF_OK && !which) e->mem.residuals_current();      // (every factor, at the current states, into the current buffer)
+    return rc;
+}
 int vf_engine_assemble(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return assemble(e); }
 int vf_engine_solve(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return solve(e); }
 int vf_engine_retract(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return retract(e); }

@@ -372,6 +372,24 @@ struct vf_engine : EngineHandle {
     int* pm_range() const { return (int*)(pm_cov + (size_t)v.G * 78); }
     // vf_engine_marginal_scores: one row of G scores per subset asked for, grown on demand
     vf::DeviceBuf<double> sc;
+    // vf_engine_factor_errors (engine/engine_errors.inc): [G] + [G] errors of the band factors, [B][2 x_cap] of the far factors, the
+    // windows' summaries and the batch's block, one allocation made by the first call.  Whether it holds anything is SolveMemory's
+    // to say (errors_valid); err_lo / err_hi: the ranges the call saw, read only behind errors_valid()
+    vf::DeviceBuf<double> err;
+    static_assert(sizeof(vf::ErrSummary) % sizeof(double) == 0 && sizeof(vf::ErrSummary) == sizeof(vf_consistency), "vf_consistency and its device twin");
+    static_assert(sizeof(vf::BatchHealth) == sizeof(vf_batch_health), "vf_batch_health and its device twin");
+    vf::FactorErrors err_view() const {
+        vf::FactorErrors o{};
+        o.imu = err;
+        o.btw = err + (size_t)v.G;
+        o.far = err + 2 * (size_t)v.G;
+        o.summary = (vf::ErrSummary*)(o.far + (size_t)v.B * 2 * x_cap);
+        o.health = (vf::BatchHealth*)(o.summary + v.B);
+        o.x_cap = x_cap;
+        return o;
+    }
+    size_t err_bytes() const { return (2 * (size_t)v.G + (size_t)v.B * 2 * x_cap) * sizeof(double) + (size_t)v.B * sizeof(vf::ErrSummary) + sizeof(vf::BatchHealth); }
+    std::vector<int> err_lo, err_hi;
     // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
     void swap_arrays(vf_engine& o) { std::swap(*this, o), std::swap<EngineHandle>(*this, o); }
 };
@@ -398,4 +416,5 @@ extern "C" {
 #include "engine/engine_read.inc"
 #include "engine/engine_marginals.inc"
 #include "engine/engine_propagate.inc"
+#include "engine/engine_errors.inc"
 }  // extern "C"

@@ -5,8 +5,10 @@
 // start: the next solve linearises only a tail), the panels and checkpoints of the incremental update, a marginal prior
 // computed ahead of time, the result block an adaptive solve has already read, and what the covariance calls left (the blocks,
 // the pose records, the scores: each only with the one before it).  A sixth outlives the arrays' next solve too: the last IMU-rate
-// propagation (vf_engine_propagate_tail), which only a grown engine loses.  Every entry point of the engine says what it did through
-// one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
+// propagation (vf_engine_propagate_tail), which only a grown engine loses.  A seventh is a fact about the residuals rather than a
+// saving: whether the current buffer's whitened residuals are those of the current states, so that vf_engine_factor_errors may read
+// them as they lie (residuals_vouched), with the per-factor errors that call left (errors_valid).  Every entry point of the engine
+// says what it did through one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
 #pragma once
 
 #include <algorithm>
@@ -25,19 +27,25 @@ class SolveMemory {
     // the facts about the engine the rules need: `slid` is one count for the whole engine, so appends are followed on
     // one-window engines only; time-sharded engines and vf_engine_opts.cold_start never start warm
     bool one_window = true, sharded = false, no_warm = false;
+    // ... and two the residuals' fact needs: non-monotone LM restores states without their residuals (k_decide outcome 3,
+    // k_close_excursion), and an incremental update linearises a suffix only -- such engines are never vouched for
+    bool excursions = false, incremental = false;
 
     // ---- events.  lo / hi: window 0's range as it is when the event fires (the engine's own mirror, passed in, not kept here)
     // something the bookkeeping cannot follow was written: the next solve / update / marginalisation starts from nothing
-    void rewritten() { warm_ = inc_valid_ = ahead_valid_ = false; }
+    void rewritten() { forget(), res_current_ = false; }
     // records were written from slot k of window w onwards (an IMU record takes the fixed words of its own slot of the J stream with
     // it, both buffers, on the stream the record is written on: K0, k_fixed_jwords -- no other slot's words, so what holds for the
     // record holds for them).  At or beyond the end it is an append; up to LINEARIZE_TAIL_MAX slots
     // inside it (late odometry for a keyframe an earlier solve covered) the warm tail grows; the incremental update follows
     // a write anywhere behind the window's first keyframe.  Everything else is rewritten().
     void written_from(int w, int k, int lo, int hi) {
+        // (a record at or beyond the end of the engine's one window is read by no residual the last solve left: an asynchronous
+        // handle preintegrates the next keyframe's record while the last solve's errors are still wanted)
+        if (!(one_window && w == 0 && k >= hi)) res_current_ = false;
         // (within a factor's reach of the first keyframe: it may be a factor the marginalisation of that keyframe reads)
         if (w == 0 && k <= lo + VF_MAX_BANDWIDTH) ahead_valid_ = false;
-        if (!behind_first(w, k, lo) || !(warm_ || inc_valid_)) return rewritten();
+        if (!behind_first(w, k, lo) || !(warm_ || inc_valid_)) return forget();
         if (inc_valid_) inc_first_dirty_ = std::min(inc_first_dirty_, k);
         if (!warm_) return;
         redo_ = std::max(redo_, hi - k);          // (<= 0: beyond the current end)
@@ -46,35 +54,41 @@ class SolveMemory {
     // the range of a window became [lo, hi); it was [old_lo, old_hi).  Growing the end of the one window of an engine is an
     // append of hi - old_hi keyframes (its start is moved by slid_by_one / vf_engine_drop_oldest only).
     void range_set(int lo, int hi, int old_lo, int old_hi) {
-        if (!(one_window && lo == old_lo && hi >= old_hi && old_hi > old_lo)) return rewritten();
+        res_current_ = false;
+        if (!(one_window && lo == old_lo && hi >= old_hi && old_hi > old_lo)) return forget();
         if (warm_) slid_ += hi - old_hi;
         else ahead_valid_ = false;
         if (inc_valid_ && hi > old_hi) inc_first_dirty_ = std::min(inc_first_dirty_, old_hi);
     }
     // every window slid by one keyframe (vf_engine_slide): a change both the warm start and the incremental update follow
-    void slid_by_one() { slid_ += warm_, inc_slid_ += inc_valid_; }
+    void slid_by_one() { slid_ += warm_, inc_slid_ += inc_valid_, res_current_ = false; }
     // a solve ended: every record, H row and g entry is that of the current states.  Engines holding far factors start every
     // solve cold.  replayed: the solve was a hipGraph replay, which runs no host code of the stages -- the panels of the
     // incremental update and the stash survive it ("ahead_valid is voided only through cold()": the fix is
     // to drop the condition below).
     void solve_ended(bool far_alive, bool replayed) {
-        if (!replayed) rewritten();
+        if (!replayed) forget();
         warm_ = !no_warm && !far_alive;
         slid_ = redo_ = 0;
+        residuals_current();
     }
     // an incremental update ended: its panels and checkpoints are those of the problem as it stands, or (failed) of nothing
     void inc_update_ended(bool ok) { rewritten(), inc_slid_ = 0, inc_first_dirty_ = INT_MAX, inc_valid_ = ok; }
+    // every factor of every window has just been linearised at the current states into the current buffer, and nothing has moved
+    // since: a solve that ended, a finished vf_engine_isam_step or vf_engine_linearize(e, 0), vf_engine_marginals_ex, the
+    // relinearising path of vf_engine_factor_errors
+    void residuals_current() { res_current_ = !excursions && !incremental; }
     // states from slot k of window w onwards were predicted from the estimate: a rewrite for the warm start and the stash,
     // an append for the incremental update if it lies behind the first keyframe of a one-window engine
     void predicted_from_estimate(int w, int k, int lo) {
         if (inc_valid_ && behind_first(w, k, lo)) inc_first_dirty_ = std::min(inc_first_dirty_, k);
         else inc_valid_ = false;
-        warm_ = ahead_valid_ = false;
+        warm_ = ahead_valid_ = res_current_ = false;
     }
     // the window was compacted: the covariance blocks stay in the slots they were computed for
-    void compacted() { rewritten(), covariances_started(); }
+    void compacted() { rewritten(), covariances_started(), err_valid_ = false; }
     // the engine was grown: new arrays, nothing linearised in them yet, no covariances
-    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = false; }
+    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = err_valid_ = false; }
     // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
     void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
     void stash_committed() { ahead_valid_ = false; }
@@ -91,12 +105,16 @@ class SolveMemory {
     void covariances_started() { sig_valid_ = pose_valid_ = false, score_rows_ = 0; }
     // ... it got through, with the pose records (VF_MARGINALS_POSE) or, as the plain vf_engine_marginals, without; scores are of the
     // records of one call: none yet
-    void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, score_rows_ = 0; }
+    void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, score_rows_ = 0, residuals_current(); }
     // vf_engine_marginal_scores left `rows` rows of scores (0: it is about to overwrite them)
     void scores_computed(int rows) { score_rows_ = rows; }
     // vf_engine_propagate_tail left a propagation in its own buffer, with or without the covariance.  It is of the arrays it was
     // enqueued on: nothing but grown() voids it
     void propagated(bool cov) { prop_valid_ = true, prop_cov_ = cov; }
+    // vf_engine_factor_errors is about to overwrite what the last one left / left the errors of every window in its own buffer.
+    // They are of the call that wrote them: later solves leave them, a compacted or grown engine loses them
+    void errors_started() { err_valid_ = false; }
+    void errors_computed() { err_valid_ = true; }
 
     // ---- queries
     // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
@@ -114,8 +132,13 @@ class SolveMemory {
     int score_rows() const { return pose_records_valid() ? score_rows_ : 0; }
     bool propagation_valid() const { return prop_valid_; }
     bool propagated_covariance_valid() const { return prop_valid_ && prop_cov_; }
+    // the current buffer's residuals are those of the current states (never on engines with excursions or incremental updates)
+    bool residuals_vouched() const { return res_current_ && !excursions && !incremental; }
+    bool errors_valid() const { return err_valid_; }
 
   private:
+    // what rewritten() does to the savings, for the events that are rewrites inside but say themselves what becomes of the residuals
+    void forget() { warm_ = inc_valid_ = ahead_valid_ = false; }
     bool behind_first(int w, int k, int lo) const { return one_window && w == 0 && k > lo; }
     bool warm_ = false;
     int slid_ = 0, redo_ = 0;     // keyframes appended since the last solve / slots in front of the old end whose factors changed
@@ -128,6 +151,7 @@ class SolveMemory {
     bool sig_valid_ = false, pose_valid_ = false;
     int score_rows_ = 0;
     bool prop_valid_ = false, prop_cov_ = false;
+    bool res_current_ = false, err_valid_ = false;
 };
 
 }  // namespace vf

@@ -232,7 +232,7 @@ int vf_set_initial_state(vf_graph* g, const double state16[16]) {
     int rc;
     if ((rc = vf_engine_set_states(g->eng, 0, 0, 1, st)) || (rc = vf_engine_set_prior(g->eng, 0, 0, rec))) return rc;
     memcpy(g->state, st, sizeof(st));
-    g->cov_valid = false;
+    g->cov_valid = g->err_valid = false;
     memcpy(g->anchor, st, sizeof(st));
     return VF_OK;
 }
@@ -742,7 +742,7 @@ int vf_solve(vf_graph* g) {
     int rc, fails = 0, flags = 0;
     {
         std::lock_guard<std::mutex> sl(g->state_mutex);  // :117
-        g->cov_valid = false;
+        g->cov_valid = g->err_valid = false;
         (rc = refuse_late(g, t)) || (rc = make_room(g, t, lap)) || (rc = marginalise(g, t, lap)) || (rc = stage_imu(g, t, lap)) || (rc = stage_band(g, t, lap)) ||
             (rc = adopt_engine_far_list(g, t)) || (rc = stage_far_list(g, t, lap)) || (rc = vf_engine_set_range(g->eng, 0, g->lo, slot_of(g, t.last_key) + 1));
         t.requeue = rc != VF_OK;    // up to here a failure gives the take back; the optimisation consumes it, whatever it returns

@@ -1,5 +1,5 @@
 // vf_graph_handle.hpp -- the GraphManager handle (struct vf_graph) as the translation units behind its C ABI see it: vf_graph.cpp,
-// which owns the bookkeeping, and vf_graph_scores.cpp, whose entry point needs engine calls that vf_graph.cpp must not reference
+// which owns the bookkeeping, and vf_graph_scores.cpp and vf_graph_errors.cpp, whose entry points need engine calls that vf_graph.cpp must not reference
 // (the host tests link vf_graph.cpp against a stand-in engine that has only what vf_graph.cpp calls).  Internal: not installed,
 // not part of include/vilfusion.h.  Host code, no HIP.
 #pragma once
@@ -71,6 +71,7 @@ struct vf_graph {
     bool solved_once = false;   // a vf_solve has succeeded
     bool cov_valid = false;     // the engine holds the covariances of the window as the last solve left it (vf_engine_marginals)
     bool cov_pose = false;      // ... computed with VF_MARGINALS_POSE: the nav_msgs records are there too (vf_graph_scores.cpp)
+    bool err_valid = false;     // the engine holds the per-factor errors of the window as the last solve left it (vf_graph_errors.cpp)
 };
 
 // key -> keyframe slot of the handle's one window, and the oldest key still in it

@@ -18,6 +18,9 @@
 //   K5 k_retract, k_decide  x (+) delta, cost reduction, LM accept/reject
 //   a2 k_predict, k_slide   PreintegrationBase::predict initial values (GraphManager.cpp:152-160)
 //   k_propagate             the state between two solves at IMU rate, with its propagated covariance (no reference code)
+//   k_factor_errors, k_batch_health
+//                           every factor's chi-square error from the residuals the solve left, a summary per window, the
+//                           batch's health (no reference code: factor->error, graph.error, printErrors of GTSAM)
 //
 // Mapping: one lane per factor / keyframe for K1-K3,K5 (HBM-bound, coalesced AoSoA tiles of 64:
 // lane l of a wave reads word l of a 512-byte field row), one 64-lane wave per window or per
@@ -139,4 +142,5 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
 #include "kernels/k4_selinv_far.inc"
 #include "kernels/kpose.inc"
 #include "kernels/kprop.inc"
+#include "kernels/kerr.inc"
 }  // namespace vf

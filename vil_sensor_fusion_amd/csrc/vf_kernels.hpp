@@ -344,7 +344,34 @@ void launch_pose_marginals(const View& v, const int* failed, const double* sig, 
 // out: [B][16 + 225]
 void launch_propagate(const View& v, const int* off, const double* steps, const ImuCov& prm, int with_cov, int from_estimate,
                       const double* sig, const int* sig_failed, double* out, hipStream_t s);
-constexpr int K6_METRICS = 25, K6_SUBSETS = 9;     // metric ids 0 .. 24 (VF_METRIC_*) and subset ids 0 .. 8 (VF_SUBSET_*) of vf_degeneracy.hip
+// Per-factor chi-square errors (kernels/kerr.inc; vf_engine_factor_errors): e = 0.5 |whitened residual|^2 of every factor of the
+// current buffer, -1 where a slot holds none, a summary per window and one block for the batch.  ErrSummary and BatchHealth are
+// the device twins of vf_consistency and vf_batch_health (include/vilfusion.h), byte for byte: the word of struct_size is unused.
+constexpr int ERR_CLASSES = 6;
+enum { ERR_IMU = 0, ERR_BETWEEN = 1, ERR_PRIOR = 2, ERR_MARGINAL = 3, ERR_FAR = 4, ERR_FAR_LINEAR = 5 };     // VF_FACTOR_*
+constexpr unsigned ERR_STATUS_NONFINITE = 1u, ERR_STATUS_FLAGGED = 2u, ERR_STATUS_EMPTY = 4u;                // VF_CONSISTENCY_*
+struct ErrSummary {
+    unsigned reserved0, status;
+    int count[ERR_CLASSES], argmax[ERR_CLASSES], flagged[ERR_CLASSES], nonfinite[ERR_CLASSES];
+    double sum[ERR_CLASSES], max[ERR_CLASSES], total;
+    int keyframes, rows, unknowns, reserved1;
+};
+struct BatchHealth {
+    unsigned reserved0;
+    int windows, empty, failed, nonfinite, never_accepted, flagged_windows, worst_window;
+    double worst_reduced_chi2;
+};
+struct FactorErrors {
+    double* imu;            // [G]              error of the IMU factor ending at each slot
+    double* btw;            // [G]              ... of the band between factor ending there
+    double* far;            // [B][2 x_cap]     nonlinear far factors by list entry, then the linear far factor's far ends
+    ErrSummary* summary;    // [B]
+    BatchHealth* health;    // [1]
+    double thr[ERR_CLASSES];  // a factor is flagged when 2 e exceeds its class's threshold (+inf: never)
+    int x_cap;
+};
+void launch_factor_errors(const View& v, const FactorErrors& o, hipStream_t s);
+constexpr int K6_METRICS = 25, K6_SUBSETS = 9;    // metric ids 0 .. 24 (VF_METRIC_*) and subset ids 0 .. 8 (VF_SUBSET_*) of vf_degeneracy.hip
 // K6 over those records (vf_degeneracy.hip, k_degeneracy_scores_windows): one metric on the subsets of `mask`, every window's range a
 // series of its own; mats / pose: [B M][36] / [B M][6], range: [B][2], out: one row of B M values per subset in the mask
 void launch_degeneracy_scores_windows(int metric, unsigned mask, const double* mats, const double* pose, const int* range, int B, int M,

@@ -27,6 +27,31 @@ def _i(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+FACTOR_CLASSES, CHI2_999 = _lib.FACTOR_CLASSES, _lib.CHI2_999
+
+
+def _thresholds(thresholds):
+    """six chi-square thresholds by class as a ctypes pointer (None: none): a sequence of six, {class name: value}, or
+    {rows: value} (CHI2_999: every class gets the quantile of its own number of rows); classes left out flag nothing"""
+    if thresholds is None:
+        return None
+    if isinstance(thresholds, dict):
+        t = [float(thresholds.get(name, thresholds.get(rows, 0.0))) for name, rows in zip(_lib.FACTOR_CLASSES, _lib.FACTOR_ROWS)]
+    else:
+        t = [float(x) for x in thresholds]
+    assert len(t) == 6
+    return (C.c_double * 6)(*t)
+
+
+def _consistency_dict(c):
+    out = {name: dict(count=c.count[i], sum=c.sum[i], max=c.max[i], argmax=c.argmax[i], flagged=c.flagged[i], nonfinite=c.nonfinite[i])
+           for i, name in enumerate(_lib.FACTOR_CLASSES)}
+    dof = c.rows - c.unknowns
+    out.update(status=c.status, total=c.total, keyframes=c.keyframes, rows=c.rows, unknowns=c.unknowns,
+               reduced_chi2=2.0 * c.total / dof if dof > 0 else None)
+    return out
+
+
 @dataclass
 class EngineOpts:
     windows: int = 1
@@ -446,6 +471,45 @@ class Engine:
         x = np.zeros((n, 15, 15)) if cross else None
         check(self._l.vf_engine_read_marginals(self._h, window, k0, n, _d(cov), _d(x) if cross else None))
         return (cov, x) if cross else cov
+
+    # ---- per-factor chi-square errors (include/vilfusion.h "vf_engine_factor_errors")
+    def factor_errors(self, relinearize=False, thresholds=None):
+        """Enqueue the chi-square error 0.5 |r|^2 of every factor of every window at the current states, a summary per window and
+        the batch's health (vf_engine_factor_errors).  By default the residuals the last solve left are read where the engine can
+        vouch for them; relinearize=True linearises at the current states first (same bits, engine left cold).  thresholds: six
+        values by class (FACTOR_CLASSES), a dict {class name: value} or {rows: value} such as CHI2_999; a factor is flagged when
+        2 e exceeds its class's threshold (None: nothing is flagged).  Read with read_factor_errors, read_far_errors,
+        read_consistency, read_health."""
+        check(self._l.vf_engine_factor_errors(self._h, _lib.ERRORS_RELINEARIZE if relinearize else 0, _thresholds(thresholds)))
+
+    def read_factor_errors(self, window, k0, n):
+        """(imu_err (n,), btw_err (n,), btw_a (n,)) for keyframe slots k0 .. k0+n-1: the error of the IMU factor and of the band
+        between factor ending at each slot, -1 where there is none, and the slot that between factor starts from (-1: none)"""
+        ei, eb, a = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        check(self._l.vf_engine_read_factor_errors(self._h, window, k0, n, _d(ei), _d(eb), _i(a)))
+        return ei, eb, a
+
+    def read_far_errors(self, window):
+        """(far_err, far_linear_err), max_far_factors entries each: by entry of get_extra_between / far end of get_linear_far; -1: none"""
+        cap = self.opts.max_far_factors or MAX_FAR
+        f, fl = np.zeros(cap), np.zeros(cap)
+        check(self._l.vf_engine_read_far_errors(self._h, window, _d(f), _d(fl)))
+        return f, fl
+
+    def read_consistency(self, window):
+        """{class name: dict(count, sum, max, argmax, flagged, nonfinite)} of one window, plus status, total, keyframes, rows,
+        unknowns and reduced_chi2 = 2 total / (rows - unknowns), None when the degrees of freedom are not positive"""
+        c = _lib.ConsistencyC()
+        c.struct_size = C.sizeof(c)
+        check(self._l.vf_engine_read_consistency(self._h, window, C.byref(c)))
+        return _consistency_dict(c)
+
+    def read_health(self):
+        """the whole batch at the time of the last factor_errors (vf_batch_health) as a dict"""
+        h = _lib.BatchHealthC()
+        h.struct_size = C.sizeof(h)
+        check(self._l.vf_engine_read_health(self._h, C.byref(h)))
+        return {name: getattr(h, name) for name, _ in h._fields_ if name != "struct_size"}
 
     def read_lm(self, window):
         cost, lam = C.c_double(), C.c_double()

@@ -177,6 +177,34 @@ class GraphManager:
         names = {v: k for k, v in degeneracy.SUBSETS.items()}
         return {names[r]: out[i] for i, r in enumerate(rows)}
 
+    def _window_keys(self, key0, n):
+        if key0 is None or n is None:
+            last = self.getMostRecentPoseTime()[1]
+            first = last - self.solverInfo()[0] + 1
+            key0 = first if key0 is None else key0
+            n = last - key0 + 1 if n is None else n
+        return key0, n
+
+    def factor_errors(self, key0=None, n=None):
+        """factor->error(values) for the factors of the last solve (vf_get_factor_errors): (imu_err (n,), btw_err (n,),
+        btw_prev_key (n,)) for keys key0 .. key0+n-1 -- the chi-square error 0.5 |r|^2 of the IMU factor X(key-1) -> X(key) and of
+        the band between factor ending at the key, -1 where there is none, and the key that between factor starts from (-1: none).
+        Defaults: the window of the last solve, as degeneracy_scores."""
+        key0, n = self._window_keys(key0, n)
+        ei, eb, prev = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint64)
+        check(self._l.vf_get_factor_errors(self._h, C.c_uint64(key0), n, ei.ctypes.data_as(C.c_void_p), eb.ctypes.data_as(C.c_void_p),
+                                           prev.ctypes.data_as(C.c_void_p)))
+        return ei, eb, np.where(prev == np.iinfo(np.uint64).max, -1, prev.astype(np.int64))
+
+    def consistency(self, thresholds=None):
+        """graph.error(values) and printErrors with a threshold (vf_get_consistency): the window's summary by factor class, as
+        Engine.read_consistency returns it; thresholds as Engine.factor_errors takes them (e.g. engine.CHI2_999)."""
+        from . import engine
+        c = _lib.ConsistencyC()
+        c.struct_size = C.sizeof(c)
+        check(self._l.vf_get_consistency(self._h, engine._thresholds(thresholds), C.byref(c)))
+        return engine._consistency_dict(c)
+
     def getState(self):
         q, t, v, b = np.zeros(4), np.zeros(3), np.zeros(3), np.zeros(6)
         check(self._l.vf_get_state(self._h, _d(q), _d(t), _d(v), _d(b)))
