@@ -1,7 +1,8 @@
 """Scripted engine-level call sequences that exercise what the engine remembers from solve to solve (csrc/vf_engine_memory.hpp):
 warm tails, late writes, set_range, several windows, cold_start, marginalise-ahead / commit, the cached result block,
 incremental updates, far factors, compact and grow in mid-run, what the covariance calls leave across those two, each with
-vf_engine_opts.use_hip_graph off and on where it applies.
+vf_engine_opts.use_hip_graph off and on where it applies; and the launches whose View differs from the engine's
+(csrc/vf_launch_view.hpp): refined and staged solves, the hybrid K4, factor errors, stage timings, one window's H on demand.
 
 After each call one line: the call, its return code, and what the ABI shows -- vf_engine_graph_info, vf_engine_solve_form,
 vf_engine_incremental_info, a digest of the window's states and the last state as hex; after a read of covariances, pose
@@ -53,8 +54,11 @@ class Run:
             line += f" | graph {g} form {e.solve_form()}"
             if self.eng.opts.incremental:
                 line += f" inc {e.incremental_info(0)}"
-            for w in range(self.B):
-                s = e.get_states(w, self.lo, self.hi - self.lo)
+            states = [e.get_states(w, self.lo, self.hi - self.lo) for w in range(self.B)]
+            if self.B > 4:                         # a large batch: one digest over all windows
+                line += f" | all {digest(*states)} trials {digest(np.array([sum(e.read_lm(w)[k] for k in ('accepted', 'rejected')) for w in range(self.B)]))}"
+                states = []
+            for w, s in enumerate(states):
                 line += f" | w{w} {hashlib.sha256(s.tobytes()).hexdigest()[:16]} {s[-1].tobytes().hex()}"
         print(line, flush=True)
 
@@ -255,12 +259,164 @@ def far(graph):
     r.eng.close()
 
 
-SCENARIOS = dict(fixed_lag=fixed_lag, several_windows=several_windows, graph_manager=graph_manager, isam=isam, far=far)
+# ---- launches whose View differs from the engine's (csrc/vf_launch_view.hpp): another right-hand side with skip flags, restored
+# windows only, the hybrid's gate and active list, one window's K3, every window whatever its `done` flag says
+FAR_REC = lambda r: synth.between_records(r.seqs[0])[:1].copy()       # (any record will do: what is compared is two builds)
+
+
+def show_delta(r, what="read_delta"):
+    e, n = r.eng, r.hi - r.lo
+    out = r.call(what, lambda: digest(*[e.read_delta(w, r.lo, n) for w in range(r.B)]), probe=False)
+    print(f"    {out}")
+
+
+def refined(graph):
+    """refined solves with a far factor alive and excursions allowed: correction solves on (nres, z) that skip the stopped windows,
+    the far combine on z, relinearize_restored behind every decision, close_excursions; on a batch engine the Woodbury columns
+    one after the other through the same band solve"""
+    del graph
+    for windows in (1, 3):
+        r = Run(f"refined windows={windows}", 128, 0, 56, windows=windows, refine_iterations=2, lm_excursion=2)
+        w = windows - 1
+        r.call(f"set_extra_between(w{w})", r.eng.set_extra_between, w, np.array([5], dtype=np.int32), np.array([40], dtype=np.int32), FAR_REC(r))
+        r.iterate(3)
+        show_delta(r)
+        for ww in range(windows):
+            out = r.call(f"read_refine(w{ww}) / read_excursions", lambda: (r.eng.read_refine(ww), r.eng.read_excursions(ww)), probe=False)
+            print(f"    {out}")
+        r.call("set_convergence", r.eng.set_convergence, 1e-5, 1e-5, probe=False)
+        r.iterate(4)
+        show_delta(r)
+        r.slide()
+        r.iterate(2)
+        r.eng.close()
+
+
+def staged(graph):
+    """a chunks=4 engine driven stage by stage as a time-sharded caller drives it (a world of one), plain and with every solve
+    refined between refine_begin and refine_end"""
+    del graph
+    for R in (0, 2):
+        r = Run(f"staged refine={R}", 128, 0, 64, chunks=4, refine_iterations=R, lm_excursion=2 if R else 0)
+        e = r.eng
+        r.call("reset_lambda", e.reset_lambda, probe=False)
+        r.call("linearize(0)", e.linearize, 0, probe=False)
+        r.call("decide(init)", e.decide, True, probe=False)
+        for trial in range(3):
+            r.call("assemble", e.assemble, probe=False)
+            r.call("solve_local", e.solve_local, probe=False)
+            r.call("solve_global", e.solve_global, probe=False)
+            show_delta(r)
+            if R:
+                r.call("refine_begin", e.refine_begin, probe=False)
+                for _ in range(e.refine_count()):
+                    r.call("solve_local", e.solve_local, probe=False)
+                    r.call("solve_global", e.solve_global, probe=False)
+                    r.call("refine_step", e.refine_step, probe=False)
+                r.call("refine_end", e.refine_end, probe=False)
+                show_delta(r)
+            r.call("retract", e.retract, probe=False)
+            r.call("linearize(1)", e.linearize, 1, probe=False)
+            r.call(f"decide (trial {trial})", e.decide, False)
+            if trial == 0:
+                r.call("set_convergence", e.set_convergence, 1e-5, 1e-5, probe=False)      # (the later trials under the rule)
+        r.call("close_excursions", e.close_excursions)
+        r.eng.close()
+
+
+def hybrid(graph):
+    """130 short windows under the termination rule, perturbed differently so that they stop at different trials: both forms of K4
+    are launched and gate themselves on the number still active, with and without the compacted list, with K3 for all windows
+    and for the partitioned half only; then H and g of one converged window on demand"""
+    for active_list, asm_min in ((1, 1), (0, 1), (1, 0)):
+        r = Run(f"hybrid graph={int(graph)} active_list={active_list} assemble_min={asm_min}", 64, 0, 20, windows=130, chunks=1, use_hip_graph=graph,
+                sweep_two_sided_max=0, solve_assemble_min=asm_min, hybrid_threshold=65, hybrid_active_list=active_list,
+                refine_iterations=0, lm_excursion=0)
+        e, n = r.eng, r.hi - r.lo
+        rng = np.random.default_rng(5)
+        for w in range(r.B):
+            s = e.get_states(w, r.lo, n)
+            s[1:, 4:10] += rng.normal(size=(n - 1, 6)) * (1e-4 * 10 ** (w % 4))
+            e.set_states(w, r.lo, s)
+        r.call("set_convergence", e.set_convergence, 1e-5, 1e-5, probe=False)
+        r.iterate(6)
+        trials = [sum(e.read_lm(w)[k] for k in ("accepted", "rejected")) for w in range(r.B)]
+        print(f"    windows by trials taken: {np.bincount(trials).tolist()}")
+        out = r.call("read_normal(w77)", lambda: digest(*e.read_normal(77, r.lo, n)), probe=False)
+        print(f"    {out}")
+        r.slide()
+        r.iterate(4)
+        r.eng.close()
+
+
+def errors(graph):
+    """factor errors from what a solve left and after a relinearisation, behind a solve that left `done` flags up; with a far factor
+    alive, also across a marginalisation, staged synchronously and asynchronously"""
+    del graph
+
+    def read_all(r):
+        e, n = r.eng, r.hi - r.lo
+        for what, fn in (("read_factor_errors", lambda: digest(*e.read_factor_errors(0, r.lo, n))),
+                         ("read_far_errors", lambda: digest(*e.read_far_errors(0))),
+                         ("read_consistency", lambda: digest(np.frombuffer(repr(sorted(e.read_consistency(0).items())).encode(), dtype=np.uint8))),
+                         ("read_health", lambda: sorted(e.read_health().items()))):
+            out = r.call(what, fn, probe=False)
+            print(f"    {out}")
+
+    for far_on, async_on in ((False, False), (True, False), (True, True)):
+        r = Run(f"errors far={int(far_on)} async={int(async_on)}", 128, 0, 48)
+        e = r.eng
+        if async_on:
+            r.call("set_async", e.set_async, True, probe=False)
+        r.call("set_convergence", e.set_convergence, 1e-5, 1e-5, probe=False)
+        if far_on:
+            r.call("set_extra_between", e.set_extra_between, 0, np.array([0], dtype=np.int32), np.array([40], dtype=np.int32), FAR_REC(r))
+        r.iterate(5)
+        r.call("factor_errors", e.factor_errors, probe=False)
+        read_all(r)
+        r.call("factor_errors(relinearize)", e.factor_errors, True)
+        read_all(r)
+        r.iterate(2)
+        r.call("marginalize", e.marginalize, probe=False)          # (the far factor at the window's first keyframe goes into the prior)
+        r.call("drop_oldest", e.drop_oldest, probe=False)
+        r.lo += 1
+        r.call("predict(hi, 1)", e.predict, 0, r.hi, 1, probe=False)
+        r.set_range(r.lo, r.hi + 1)
+        r.iterate(3)
+        r.call("factor_errors", e.factor_errors, probe=False)
+        read_all(r)
+        r.eng.close()
+
+
+def stages(graph):
+    """vf_engine_time_stage of every stage on a converged engine (the timings are not printed: what each stage left is), then a solve;
+    H and g of a window whose solves do not keep them"""
+    del graph
+    from vil_sensor_fusion_amd.engine import STAGES
+    for name, opts in (("partitioned", {}), ("assembling", dict(SWEEP, solve_assemble_min=1))):
+        r = Run(f"stages {name}", 128, 0, 48, **opts)
+        e, n = r.eng, r.hi - r.lo
+        r.call("set_convergence", e.set_convergence, 1e-5, 1e-5, probe=False)
+        r.iterate(5)
+        for stage in STAGES:
+            r.call(f"time_stage({stage})", e.time_stage, stage, 2)
+            show_delta(r)
+        out = r.call("read_normal", lambda: digest(*e.read_normal(0, r.lo, n)), probe=False)
+        print(f"    {out}")
+        r.iterate(2)
+        out = r.call("read_normal", lambda: digest(*e.read_normal(0, r.lo, n)), probe=False)
+        print(f"    {out}")
+        r.eng.close()
+
+
+SCENARIOS = dict(fixed_lag=fixed_lag, several_windows=several_windows, graph_manager=graph_manager, isam=isam, far=far,
+                 refined=refined, staged=staged, hybrid=hybrid, errors=errors, stages=stages)
+NO_GRAPH = ("isam", "refined", "staged", "errors", "stages")        # scenarios that have no replayed form
 
 if __name__ == "__main__":
     for name in sys.argv[1:] or SCENARIOS:
         for graph in (False, True):
-            if name == "isam" and graph:
+            if name in NO_GRAPH and graph:
                 continue
             SCENARIOS[name](graph)
     print("engine_sequences done")

@@ -37,10 +37,7 @@ static int first_failed_window(vf_engine* e) {
 static int isam_step_incremental(vf_engine* e, double relin_threshold) {
     const int invalid = (e->mem.inc_whole_window() || e->opts.incremental == 2) ? 1 : 0;     // (incremental = 2: the same kernels over the whole window, every time)
     const int appended = e->mem.inc_appended(e->h_hi[0]);
-    vf::View a = e->v;
-    a.inc_on = 1;
-    a.inc_prior = (invalid || e->mem.inc_slid()) ? 1 : 0;
-    a.stop_on = 0;
+    const vf::View a = vf::incremental(e->v, invalid || e->mem.inc_slid());     // (the priors too where the marginal prior has changed)
     vf::launch_inc_begin(a, relin_threshold, appended, invalid, e->stream);
     HIPCHK(hipMemsetAsync(e->v.lambda, 0, e->v.B * sizeof(double), e->stream));     // Gauss-Newton: no damping
     vf::launch_linearize(a, 0, e->stream);

@@ -7,8 +7,8 @@
 //                SolveMemory knows whether anything has been written since (residuals_vouched).  The call then launches
 //                k_factor_errors on what is there and touches nothing else: no event fires, the cached result block stays.
 //   relinearise  asked for (VF_ERRORS_RELINEARIZE), or the engine cannot vouch: every factor is linearised at the current states
-//                first, on a copy of the View as vf_engine_marginals_ex makes it -- the same bits into the same buffer -- and the
-//                engine is marked cold, as after the covariances.
+//                first, every window whether or not the termination rule has finished it (vf::every_window, vf_launch_view.hpp) -- the
+//                same bits into the same buffer -- and the engine is marked cold, as after the covariances.
 // The result buffer belongs to the call that wrote it: later solves leave it, compact and grow void it (SolveMemory::errors_valid).
 int vf_engine_factor_errors(vf_engine* e, unsigned flags, const double* chi2_threshold6) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
@@ -24,10 +24,7 @@ int vf_engine_factor_errors(vf_engine* e, unsigned flags, const double* chi2_thr
     }
     if ((flags & VF_ERRORS_RELINEARIZE) || !e->mem.residuals_vouched()) {
         e->mem.rewritten();
-        vf::View a = e->v;
-        a.stop_on = 0;                   // every window, whether or not the termination rule has finished it
-        a.inc_on = 0;
-        a.relin_only = 0;
+        const vf::View a = vf::every_window(e->v);
         vf::launch_linearize(a, 0, e->stream);      // (which = 0: the estimate, or theta of a reference-compat engine)
         if (e->x_used > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
         e->mem.residuals_current();

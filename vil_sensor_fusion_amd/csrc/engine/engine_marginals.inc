@@ -2,8 +2,8 @@
 // A section of vf_engine.hip (the C ABI of the engine: include/vilfusion.h); included from there, inside extern "C", never
 // compiled by itself.
 //
-// The undamped factorisation at the current states is made on a COPY of the View whose lambda, failure flags and `fresh` flags
-// point at arrays of this section: the LM state of the engine (states, increments, lambda, counters, done flags, sticky words,
+// The undamped factorisation at the current states is launched on vf::undamped_whole (vf_launch_view.hpp): the engine's View with
+// lambda, failure flags and `fresh` flags pointing at arrays of this section.  The LM state of the engine (states, increments, lambda, counters, done flags, sticky words,
 // the cached result block) is not touched.  What is overwritten -- the current buffer's linearisation (the same bits: it is of
 // the same states), H, g and the panels -- is what a cold start rebuilds, and the engine is marked cold.
 //
@@ -52,16 +52,9 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     // allocated on first use as sig is (G x 624 B): only engines that ask for the nav_msgs records hold them
     if (pose) HIPCHK(e->pm_cov.ensure(G * (36 + 36 + 6) * sizeof(double) + 2 * B * sizeof(int) + 256));
     e->mem.rewritten();
-    vf::View a = e->v;
-    a.lambda = e->sig_zero();         // undamped
-    a.fail = e->sig_fail();
-    a.fresh = e->sig_ones();          // every window assembled, whole
-    a.stop_on = 0;                   // ... whether or not the termination rule has finished it
-    a.gate = 0;
-    a.act = nullptr;
-    a.inc_on = 0;
-    a.relin_only = 0;
-    a.P = 0;                         // whole-window sweep whatever form the engine's solves take (they may be partitioned)
+    // undamped, every window assembled and swept whole -- whether or not the termination rule has finished it, whatever form the
+    // engine's solves take (they may be partitioned)
+    const vf::View a = vf::undamped_whole(e->v, e->sig_zero(), e->sig_fail(), e->sig_ones());
     HIPCHK(hipMemsetAsync(e->sig_fail(), 0, B * sizeof(int), e->stream));
     // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
     vf::launch_linearize(a, 0, e->stream);
@@ -70,8 +63,7 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     // is the one the same engine without far factors would have: far factors veto the assembling sweep for the SOLVE (its Woodbury
     // columns read H and g), but they never enter the band and the downdate reads only the panels -- so a window without far
     // factors gets the bits it gets from an engine that has none, on batch engines that assemble as well
-    const vf::SolvePlan plan = vf::solve_plan(vf::solve_inputs(e->v, e->hybrid && e->v.stop_on, e->act_list != nullptr,
-                                                               e->refine_iters() > 0 || e->v.min_fidelity > 0.0));
+    const vf::SolvePlan plan = vf::solve_plan(solve_inputs(e, false));
     if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
     vf::launch_band_factor(a, plan, e->stream);
     vf::launch_selinv(a, e->sig_fail(), e->sig, e->stream);

@@ -154,8 +154,7 @@ int vf_engine_read_excursions(vf_engine* e, int window, int* provisional_trials,
 int vf_engine_time_stage(vf_engine* e, int stage, int reps, float* avg_ms) {
     Entry entry_(e, Entry::rewrites);
     if (!e || !avg_ms || reps < 1) return fail(VF_ERR_INVALID, "bad argument");
-    vf::View tv = e->v;
-    tv.stop_on = 0;           // stage timings are of the full work, whatever the windows' convergence flags say
+    const vf::View tv = vf::every_window(e->v);      // stage timings are of the full work, whatever the windows' convergence flags say
     // K4's stage is the form the View alone gives: never the hybrid, and the assembling sweep even where the engine's own solves
     // are vetoed from it
     vf::SolveInputs in = solve_inputs(e);

@@ -68,6 +68,10 @@ int vf_engine_shard_info(vf_engine* e, vf_shard_info* out) {
     }
     return VF_OK;
 }
+// what the staged solve works on: the engine's system, or while a refinement is open the correction's (converged windows are skipped)
+static vf::View staged_view(const vf_engine* e) {
+    return e->refine_open ? vf::on_buffers(e->v, e->rq.nres, e->rq.z, e->rq.stop) : e->v;
+}
 static int check_sharded(vf_engine* e) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
     if (e->v.P < 2) return fail(VF_ERR_INVALID, "engine was not created with the partitioned solve (chunks >= 2)");
@@ -83,9 +87,7 @@ int vf_engine_solve_local(vf_engine* e) {
     Entry entry_(e, Entry::rewrites);
     int rc = check_sharded(e);
     if (rc) return rc;
-    vf::View a = e->v;
-    if (e->refine_open) { a.gvec = e->rq.nres; a.delta = e->rq.z; a.stop_on = 1; a.done = e->rq.stop; }    // (converged windows are skipped)
-    vf::launch_partitioned_local(a, e->stream);
+    vf::launch_partitioned_local(staged_view(e), e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
 }
@@ -93,8 +95,7 @@ int vf_engine_solve_global(vf_engine* e) {
     Entry entry_(e, Entry::rewrites);
     int rc = check_sharded(e);
     if (rc) return rc;
-    vf::View a = e->v;
-    if (e->refine_open) { a.gvec = e->rq.nres; a.delta = e->rq.z; a.stop_on = 1; a.done = e->rq.stop; }
+    const vf::View a = staged_view(e);
     vf::launch_partitioned_global(a, e->stream);
     if (e->v.sh_G > 1) vf::launch_mask_delta(a, e->stream);
     HIPCHK(hipGetLastError());

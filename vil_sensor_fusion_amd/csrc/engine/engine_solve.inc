@@ -22,9 +22,10 @@ static int linearize(vf_engine* e, int which) {
 }
 // What the form of this engine's solves depends on (vf_solve_plan.hpp).  The sweep may not assemble H itself while something in
 // the solve reads H and g: the far factors' correction solves, the refined solve's, GTSAM's accept rule (k_model_change).
-static vf::SolveInputs solve_inputs(const vf_engine* e) {
+// (far_veto = false: the plan the same engine without far factors would have -- vf_engine_marginals_ex)
+static vf::SolveInputs solve_inputs(const vf_engine* e, bool far_veto = true) {
     return vf::solve_inputs(e->v, e->hybrid && e->v.stop_on, e->act_list != nullptr,
-                            e->x_used > 0 || e->refine_iters() > 0 || e->v.min_fidelity > 0.0);
+                            (far_veto && e->x_used > 0) || e->refine_iters() > 0 || e->v.min_fidelity > 0.0);
 }
 static vf::SolvePlan solve_plan(const vf_engine* e) { return vf::solve_plan(solve_inputs(e)); }
 static int assemble(vf_engine* e) {
@@ -46,17 +47,10 @@ static int solve(vf_engine* e) {
     auto band_solve = [&](double* gvec, double* delta, const int* skip = nullptr) {      // the engine's K4 form on another right-hand side / increment buffer
         // (skip: windows that take no part -- a refinement's correction solves pass its stop flags, which include the windows
         // the termination rule has finished, so that a window whose corrections have converged costs its later solves nothing)
-        auto on = [&](vf::View a) {
-            a.gvec = gvec;
-            a.delta = delta;
-            if (skip) { a.stop_on = 1; a.done = const_cast<int*>(skip); }
-            return a;
-        };
-        vf::View a = on(e->v);
-        if (plan.hybrid()) {
-            a.act = e->act_list;
-            vf::launch_band_solve(a, on(e->partitioned_view()), plan, e->stream);     // (the partitioned half skips the same windows)
-        } else vf::launch_band_solve(a, a, plan, e->stream);
+        const vf::View a = vf::on_buffers(e->v, gvec, delta, skip);
+        if (plan.hybrid())      // (the sweeps take their windows from the active list; the partitioned half skips the same windows)
+            vf::launch_band_solve(vf::from_active_list(a, e->act_list), vf::on_buffers(e->partitioned_view(), gvec, delta, skip), plan, e->stream);
+        else vf::launch_band_solve(a, a, plan, e->stream);
     };
     // (single-window engines with a second stream -- the GraphManager's: the column engine's solve needs H and the far factors'
     // rows, nothing the window's own solve writes, and each of the two is a chain of small launches that leaves most of the part
@@ -115,13 +109,8 @@ static int solve(vf_engine* e) {
         vf::launch_refine_begin(e->v, e->rq, e->stream);
         for (int it = 0; it < R; it++) {
             band_solve(e->rq.nres, e->rq.z, e->rq.stop);
-            if (e->x_used > 0) {
-                vf::View a = e->v;
-                a.delta = e->rq.z;
-                a.stop_on = 1;
-                a.done = e->rq.stop;
-                vf::launch_extra_combine(a, far_Z, far_zstride, e->x_used, e->stream);
-            }
+            if (e->x_used > 0)
+                vf::launch_extra_combine(vf::on_buffers(e->v, nullptr, e->rq.z, e->rq.stop), far_Z, far_zstride, e->x_used, e->stream);
             vf::launch_refine_step(e->v, e->rq, e->refine_stop(), e->stream);
             // How many corrections a window needs grows with its length (4 at 1 600 keyframes, 12 at 10 000): after the
             // 4th, 6th, ... the stop flags are read back, and once every window has stopped the rest are not issued
@@ -200,9 +189,7 @@ static int retract(vf_engine* e) {
 // non-monotone LM: a failed excursion has put the point it started from back into the current buffer; its factors are
 // linearised again (the kernels skip every window whose flag is clear)
 static int relinearize_restored(vf_engine* e) {
-    vf::View a = e->v;
-    a.relin_only = 1;
-    vf::launch_linearize(a, 0, e->stream);
+    vf::launch_linearize(vf::restored_only(e->v), 0, e->stream);
     HIPCHK(hipMemsetAsync(e->v.relin, 0, e->v.B * sizeof(int), e->stream));
     return VF_OK;
 }
@@ -228,11 +215,8 @@ static int decide(vf_engine* e, int init) {
     vf::launch_decide(e->v, init ? 1 : 0, e->stream);
     if (e->v.nm_W > 0 && !init)
         if (int rc = relinearize_restored(e)) return rc;
-    if (e->hybrid && e->v.stop_on) {          // what the next K4 launch gates on (and the list its sweeps take their windows from)
-        vf::View c = e->v;
-        c.act = e->act_list;
-        vf::launch_count_active(c, e->stream);
-    }
+    // what the next K4 launch gates on (and the list its sweeps take their windows from)
+    if (e->hybrid && e->v.stop_on) vf::launch_count_active(vf::from_active_list(e->v, e->act_list), e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
 }

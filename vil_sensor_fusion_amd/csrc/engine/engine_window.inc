@@ -23,9 +23,7 @@ int vf_engine_marginalize(vf_engine* e) {
     if (e->async_far()) {
         // far factors alive: on the main stream (the kernel reads and rewrites their lists, which the host re-sends there), behind
         // the linearisation of the ones the prior is about to absorb; what it finds wrong goes into the sticky word
-        vf::View a = e->v;
-        a.stop_on = 0;
-        vf::launch_linearize_extra(a, 0, e->stream);
+        vf::launch_linearize_extra(vf::every_window(e->v), 0, e->stream);
         vf::launch_marginalize(e->v, e->x_used, e->sticky_dev + 1, e->stream);
         HIPCHK(hipGetLastError());
         e->marg_since_drop = true;
@@ -47,11 +45,8 @@ int vf_engine_marginalize(vf_engine* e) {
     HIPCHK(hipMemsetAsync(e->status_dev, 0, sizeof(int), e->stream));
     // far factors the prior is about to absorb: their linearisation at the current states (a compaction, a transport or any
     // other re-sending of the list since the last solve has zeroed the buffers)
-    if (e->x_used > 0) {
-        vf::View a = e->v;
-        a.stop_on = 0;       // (a window the termination rule finished in the last solve still has its `done` flag up: linearise it all the same)
-        vf::launch_linearize_extra(a, 0, e->stream);
-    }
+    // (a window the termination rule finished in the last solve still has its `done` flag up: linearise it all the same)
+    if (e->x_used > 0) vf::launch_linearize_extra(vf::every_window(e->v), 0, e->stream);
     vf::launch_marginalize(e->v, e->x_used, e->status_dev, e->stream);
     HIPCHK(hipGetLastError());
     int status = 0;

@@ -60,8 +60,7 @@ void launch_linearize_tail(const View& v, int nslid, hipStream_t s) {
 }
 // K3 for the partitioned half of a hybrid solve whose sweep half assembles its own rows (see k_assemble)
 void launch_assemble_for_partitioned(const View& v, hipStream_t s) {
-    View a = v;
-    a.gate = 2;
+    const View a = hybrid_half(v, 2);
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)(v.M / AT), (unsigned)v.B), dim3(K3_NT), 0, s, a);
 }
 void launch_assemble(const View& v, hipStream_t s) {
@@ -71,12 +70,7 @@ void launch_assemble(const View& v, hipStream_t s) {
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)(v.M / AT), (unsigned)v.B), dim3(K3_NT), 0, s, v);
 }
 void launch_assemble_window(const View& v, int window, hipStream_t s) {
-    // (gate = 2: K3 ignores `fresh`; stop_on = 0: a window the termination rule has finished is assembled too)
-    View a = v;
-    a.gate = 2;
-    a.gate_T = 1 << 30;          // ... and gated_off() lets a gate-2 launch run while n_active <= gate_T
-    a.stop_on = 0;
-    a.w_first = window;
+    const View a = one_window_k3(v, window);
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)(v.M / AT), 1u), dim3(K3_NT), 0, s, a);
 }
 void launch_partitioned_local(const View& v, hipStream_t s) {
@@ -128,11 +122,7 @@ static void launch_band_forward(const View& v, Sweep f, hipStream_t s) {
     else hipLaunchKernelGGL(k_band_forward, dim3(v.B), dim3(64), 0, s, v);
 }
 void launch_band_solve(const View& v, const View& vp, const SolvePlan& plan, hipStream_t s) {
-    View a = v, b = vp;
-    if (plan.hybrid()) {
-        a.gate = 1;
-        b.gate = 2;
-    }
+    const View a = plan.hybrid() ? hybrid_half(v, 1) : v, b = plan.hybrid() ? hybrid_half(vp, 2) : vp;
     // few windows: two waves per window from both ends (latency); many: one wave per window (throughput).  (a.act, when the
     // engine hands it to a hybrid's sweep: the active windows are visited first)
     switch (plan.sweep) {

@@ -20,6 +20,7 @@
 
 #include "../../include/vilfusion.h"
 #include "vf_kernels.hpp"
+#include "vf_launch_view.hpp"
 #include "vf_device_buf.hpp"
 #include "vf_engine_memory.hpp"
 
@@ -90,7 +91,7 @@ struct EngineHandle {
 
 // ... and everything else belongs to the device ARRAYS (and what the host knows about them), which a grown engine replaces whole
 struct vf_engine : EngineHandle {
-    vf::View v{};
+    vf::View v{};            // holds the neutral value of every per-launch word, always: launches that differ take a copy (vf_launch_view.hpp)
     vf::SolveMemory mem;     // what the arrays still hold from the last solve
     vf_engine_opts opts{};
     vf_engine_tuning tune{};
@@ -162,17 +163,7 @@ struct vf_engine : EngineHandle {
     double *h_Vp = nullptr, *h_sep = nullptr, *h_sepL = nullptr;
     int* act_list = nullptr;   // compacted list of the windows still taking trials (vf_engine_opts.hybrid_active_list): handed to the hybrid's
                                // sweeps and to k_count_active only -- every other launch sees View::act = null
-    vf::View partitioned_view() const {
-        vf::View p = v;
-        p.P = hybrid_P;
-        p.P_fit = 1;
-        p.Vp = h_Vp;
-        p.sepR = h_sep;
-        p.sepS = h_sep + vf::SEPM;
-        p.sepC = h_sep + 2 * vf::SEPM;
-        p.sepL = h_sepL;
-        return p;
-    }
+    vf::View partitioned_view() const { return vf::partitioned_form(v, hybrid_P, h_Vp, h_sep, h_sepL); }
 
     // The arrays of an engine are carved out of ONE device allocation made at creation (reserve(): a hipMalloc costs 0.1-0.3 ms
     // whatever its size, and an engine has forty arrays -- creating the 6-window column engine of a first loop closure inside a

@@ -27,6 +27,7 @@
 // chunk for K4 / K4p (panel factorisation in registers with v_readlane / DPP broadcasts,
 // trailing window in LDS, Schur / spike products on v_mfma_f64_16x16x4).
 #include "vf_kernels.hpp"
+#include "vf_launch_view.hpp"
 #include "vf_jstream.hpp"
 #include "vf_math.hpp"
 #include <cstdlib>
