@@ -345,6 +345,53 @@ int vf_engine_propagate_tail(vf_engine* e, const int32_t* step_off, const double
 int vf_engine_read_propagated(vf_engine* e, int window, double* state16, double* cov225);
 /* ... and the last call's copy / kernel times from HIP events (synchronises on the kernel's event) */
 int vf_engine_propagate_status(vf_engine* e, float* h2d_ms, float* kernel_ms);
+/* Innovation gate: what the window as solved, and the IMU since, say about a between factor BEFORE it is added (no reference code:
+ * the estimation-theoretic counterpart of the reference's degerate_odometry_filter, which drops odometry on a D-optimality
+ * threshold).  For every window, with i = hi[w]-1 its last keyframe, the raw samples steps7[step_off[w] .. step_off[w+1]) that follow
+ * it (packed as vf_engine_ingest_tail) and a candidate BetweenFactor<Pose3> from keyframe slot btw_a[w] to the keyframe j those
+ * samples lead to (btw_rec28[w]: the record vf_engine_ingest_tail takes; btw_a[w] = -1: none):
+ *   - the samples are integrated and x_j predicted exactly as vf_engine_propagate_tail does: state16 equals its state bit for bit;
+ *   - the joint pose covariance of (a, j) follows from the appended keyframe's linear model d_j = G d_i + B^-1 n, n ~ N(0, P):
+ *     Sigma_jj^pp from Sigma_ii and P, Cov(pose_j, pose_a) = (G_p Sigma_{i,a})[:, 0:6], Sigma_aa^pp from slot a -- the blocks the last
+ *     vf_engine_marginals_ex left (VF_MARGINALS_TAIL is enough; a far downdate is honoured as it lies);
+ *   - r, Ja, Jb: the factor's whitened residual and Jacobians at T_a of the current buffer and the predicted T_j;
+ *     xi = Log(Z^-1 T_a^-1 T_j), the unwhitened innovation in [rot, trans] order;
+ *   - S = I + Ja Sigma_aa Ja^T + Ja C^T Jb^T + Jb C Ja^T + Jb Sigma_jj Jb^T; nis = r^T S^-1 r (chi-square, 6 degrees of freedom
+ *     when the measurement is consistent); nis_measurement = r^T r, twice the factor's error at the predicted state.
+ * REACH: a = i or a = i-1.  An older keyframe would need the covariance of an earlier pose against a later full state, which the
+ * selected inversion does not keep: such a window gets VF_GATE_OUT_OF_REACH, not an error.
+ * chi2_threshold: rejected is set when nis exceeds it and it is finite and positive (else nothing is rejected).  The 6-dof quantiles
+ * a caller is likely to pass: 16.81 at 99 %, 22.46 at 99.9 %.
+ * VF_GATE_FROM_ESTIMATE: as VF_PROPAGATE_FROM_ESTIMATE.
+ * One pinned copy (buffers of this call's own) and one launch on the engine's stream, no host synchronisation.  The call writes one
+ * record per window in a buffer made by the first call, and nothing else.  VF_ERR_INVALID: unknown flags; no valid marginal
+ * covariances, or ones that do not cover the last keyframe; a time-sharded engine.  VF_ERR_BAD_KEY: an empty window. */
+#define VF_GATE_FROM_ESTIMATE 2u
+#define VF_GATE_OK 0            /* nis, nis_measurement, xi are valid */
+#define VF_GATE_NONE 1          /* btw_a = -1: nothing to test */
+#define VF_GATE_OUT_OF_REACH 2  /* a < i-1, a beyond i, a in front of the window or of the range the covariances cover */
+#define VF_GATE_DEGENERATE 3    /* a = i with no samples: a factor between a keyframe and itself */
+#define VF_GATE_NO_COVARIANCE 4 /* the window's factorisation failed, or S is not positive definite: nis is NaN (xi, nis_measurement valid) */
+/* One window's result.  state16 is valid whatever the status; nis, nis_measurement and xi are NaN unless the status says otherwise.
+ * A plain output struct: the caller fills struct_size (sizeof), the library writes no byte beyond it.  Grows at the end only. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t status;            /* VF_GATE_* */
+    int32_t rejected;          /* 1: status is VF_GATE_OK and nis > chi2_threshold */
+    int32_t reserved;
+    double nis;
+    double nis_measurement;
+    double xi[6];
+    double state16[16];
+} vf_gate_result;
+int vf_engine_gate_tail(vf_engine* e, const int32_t* step_off, const double* steps7, const vf_imu_params* p,
+                        const int32_t* btw_a, const double* btw_rec28, double chi2_threshold, unsigned flags);
+/* ... read back one window (synchronises).  VF_ERR_INVALID: no vf_engine_gate_tail since the engine was made, compacted or grown. */
+int vf_engine_read_gate(vf_engine* e, int window, vf_gate_result* out);
+/* ... every window's status and nis, B entries each, in one synchronisation; either pointer may be NULL */
+int vf_engine_read_gate_all(vf_engine* e, int32_t* status, double* nis);
+/* ... and the last call's copy / kernel times from HIP events (synchronises on the kernel's event) */
+int vf_engine_gate_status(vf_engine* e, float* h2d_ms, float* kernel_ms);
 
 /* ---- hot-path stages (asynchronous on the engine's HIP stream) ---- */
 /* K1+K2+priors: residual + whitened Jacobian of every factor, at the current (which=0) or
@@ -530,6 +577,12 @@ int vf_engine_marginals(vf_engine* e);
  * cov36 and info36 are symmetric to the bit.  A window whose factorisation failed holds NaN in all three.  Without the flag the
  * call launches what it always launched, gives the same bits and allocates nothing more. */
 #define VF_MARGINALS_POSE 2u
+/* VF_MARGINALS_TAIL: the blocks of every window's last two keyframes only (slots hi-1 and hi-2: what vf_engine_gate_tail and
+ * vf_engine_propagate_tail read).  The selected inversion walks backward from hi-1 and stops after two steps instead of hi-lo; the
+ * factorisation in front of it is the same, and the blocks written are bit for bit those of the full call.  The range the
+ * covariances cover becomes [max(lo, hi-2), hi): reads below it are refused with VF_ERR_BAD_KEY as any read outside the range is.
+ * Combined with VF_MARGINALS_FAR or VF_MARGINALS_POSE: VF_ERR_INVALID. */
+#define VF_MARGINALS_TAIL 4u
 int vf_engine_marginals_ex(vf_engine* e, unsigned flags);
 /* ... read back (synchronises): for keyframes k0 .. k0+n-1 of the range the last vf_engine_marginals saw, Sigma_kk (full
  * symmetric 15x15, row-major) and the cross block Sigma_{k+1,k} (15x15, row = dof of k+1, column = dof of k; zero for the window's
@@ -853,6 +906,20 @@ int vf_get_consistency(vf_graph* g, const double* chi2_threshold6, vf_consistenc
  * is a ready-made record (vf_add_imu_factor); `time` precedes the last reserved key's time.  Takes the graph, buffer and state
  * locks in vf_reserve_node's order: never call it from inside a callback. */
 int vf_predict_state(vf_graph* g, double time, double q[4], double t[3], double v[3], double bias[6], double cov225[225]);
+/* The innovation test of an odometry increment BEFORE vf_add_between takes it (vf_engine_gate_tail on the handle's window; its
+ * comment has the quantity, the reach and the 6-dof quantiles a caller is likely to pass: 16.81 at 99 %, 22.46 at 99.9 %).  q, t,
+ * cov36: what vf_add_between would be given -- the record is built and validated by the same routine, with the same error codes.
+ * cur_key: a reserved key in [solved key, current key]; the IMU steps are those of the queued, not yet solved factors up to
+ * cur_key, concatenated as vf_predict_state does, nothing is cut from the IMU buffer; cur_key = the solved key means no steps.
+ * prev_key: the last solved key or the one before it, still in the window -- anything else returns VF_OK with status
+ * VF_GATE_OUT_OF_REACH.  If the last solve has no covariances yet they are computed first: VF_MARGINALS_TAIL while no far factor is
+ * alive (vf_get_marginal_covariance, the scores and the covariance callbacks compute the full ones when they are asked), otherwise
+ * as vf_predict_state does, vf_graph_opts.far_covariance honoured and its refusals applied.  reference_compat handles gate from
+ * the estimate.  Nothing is consumed or staged: vf_add_between + vf_solve after a gate give the bits of a handle that never gated.
+ * Between factors of other sensors that are staged but not solved yet are not part of the prediction.  Locks and refusals as
+ * vf_predict_state (never from inside a callback); VF_ERR_BAD_KEY also for keys not reserved in order or a cur_key solved already. */
+int vf_gate_between(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q[4], const double t[3], const double cov36[36],
+                    double chi2_threshold, vf_gate_result* out);
 /* the callback of vf_set_callback plus the marginal covariance of the solved keyframe */
 typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
                                 const double bias[6], const double cov225[225]);

@@ -72,6 +72,12 @@ class BatchHealthC(C.Structure):
                 ("worst_reduced_chi2", C.c_double)]
 
 
+class GateResultC(C.Structure):
+    """one window's innovation test (include/vilfusion.h vf_gate_result); the caller fills struct_size"""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("rejected", C.c_int32), ("reserved", C.c_int32),
+                ("nis", C.c_double), ("nis_measurement", C.c_double), ("xi", C.c_double * 6), ("state16", C.c_double * 16)]
+
+
 CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                        C.POINTER(C.c_double), C.POINTER(C.c_double))
 
@@ -85,8 +91,14 @@ CHI2_999 = {6: 22.4577, 15: 37.6973, 27: 55.4760}
 
 MARGINALS_FAR = 1        # vf_engine_marginals_ex: take far factors alive into account (VF_MARGINALS_FAR)
 MARGINALS_POSE = 2       # ... leave the nav_msgs pose covariance, its inverse and the pose of every keyframe on the device (VF_MARGINALS_POSE)
+MARGINALS_TAIL = 4       # ... the blocks of every window's last two keyframes only (VF_MARGINALS_TAIL)
 PROPAGATE_COVARIANCE = 1     # vf_engine_propagate_tail: propagate the last keyframe's marginal covariance too (VF_PROPAGATE_COVARIANCE)
 PROPAGATE_FROM_ESTIMATE = 2  # ... start from the trial buffer's state, the estimate of a reference-compat engine (VF_PROPAGATE_FROM_ESTIMATE)
+GATE_FROM_ESTIMATE = 2       # vf_engine_gate_tail: as PROPAGATE_FROM_ESTIMATE (VF_GATE_FROM_ESTIMATE)
+GATE_OK, GATE_NONE, GATE_OUT_OF_REACH, GATE_DEGENERATE, GATE_NO_COVARIANCE = 0, 1, 2, 3, 4     # vf_gate_result.status (VF_GATE_*)
+GATE_STATUS = ("ok", "none", "out_of_reach", "degenerate", "no_covariance")
+# quantiles of the chi-square distribution with 6 degrees of freedom: thresholds on the gate's nis (scipy.stats.chi2.ppf(q, 6))
+CHI2_6_99, CHI2_6_999 = 16.81, 22.46
 SCORE_COVARIANCE, SCORE_INFORMATION = 0, 1     # vf_engine_marginal_scores / vf_get_degeneracy_scores: which of the two is scored
 
 COV_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -111,6 +123,7 @@ SYMBOLS = [
     "vf_engine_time_stage", "vf_engine_time_iterate", "vf_engine_counts",
     "vf_engine_preintegrate", "vf_engine_get_imu", "vf_engine_ingest_tail", "vf_engine_ingest_status",
     "vf_engine_propagate_tail", "vf_engine_read_propagated", "vf_engine_propagate_status",
+    "vf_engine_gate_tail", "vf_engine_read_gate", "vf_engine_read_gate_all", "vf_engine_gate_status",
     "vf_engine_marginalize", "vf_engine_drop_oldest", "vf_engine_read_marginal", "vf_engine_compact", "vf_engine_grow",
     "vf_engine_set_stream", "vf_engine_set_shard", "vf_engine_shard_info", "vf_engine_solve_local",
     "vf_engine_solve_global", "vf_engine_reset_lambda",
@@ -120,7 +133,7 @@ SYMBOLS = [
     "vf_engine_isam_step", "vf_engine_predict_from_estimate", "vf_engine_get_estimate", "vf_engine_incremental_info", "vf_engine_set_async", "vf_engine_read_result", "vf_engine_marginalize_ahead",
     "vf_graph_default_opts", "vf_graph_default_opts_sized", "vf_create", "vf_destroy", "vf_add_imu", "vf_reserve_node",
     "vf_add_between", "vf_solve", "vf_get_state", "vf_get_bias", "vf_most_recent_pose_time",
-    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_predict_state", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
+    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_predict_state", "vf_gate_between", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
     "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged",
     "vf_degeneracy_batch", "vf_degeneracy_spectrum_batch", "vf_degeneracy_scores_batch", "vf_dopt_filter_f32",
 ]
@@ -146,7 +159,9 @@ def lib():
         l.vf_engine_marginals_ex.argtypes = [C.c_void_p, C.c_uint]
         l.vf_engine_marginal_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint]
         l.vf_engine_propagate_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]
+        l.vf_engine_gate_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint]
         l.vf_predict_state.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.vf_gate_between.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         l.vf_get_degeneracy_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.c_int, C.c_void_p]
         l.vf_engine_factor_errors.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
         l.vf_get_factor_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -261,6 +261,7 @@ void vf_engine_destroy(vf_engine* e) {
     for (void* p : e->allocs) (void)hipFree(p);
     for (auto ev : e->in_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto ev : e->prop_ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto ev : e->gate_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->far_columns) { vf_engine_destroy(e->far_columns); e->far_columns = nullptr; }
     if (e->stream2) { (void)hipStreamSynchronize(e->stream2); (void)hipStreamDestroy(e->stream2); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);

@@ -16,11 +16,16 @@
 // solve's own Woodbury columns take on that engine, x_Z): that case is one group.  With eight closures per window (m = 48) it
 // makes groups of about 180 windows of 1 024 slots instead of asking for 6 GB.
 constexpr size_t FARCOV_BUDGET = (size_t)1 << 30;
+// VF_MARGINALS_TAIL: the selected inversion stops after the last two keyframes of every window -- what the innovation gate reads
+// (engine/engine_gate.inc).  sig_lo says so, and every reader's range check refuses what was not computed.
+constexpr int MARGINALS_TAIL_DEPTH = 2;
 int vf_engine_marginals(vf_engine* e) { return vf_engine_marginals_ex(e, 0); }
 int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
-    if (flags & ~(unsigned)(VF_MARGINALS_FAR | VF_MARGINALS_POSE)) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
-    const bool far = (flags & VF_MARGINALS_FAR) != 0, pose = (flags & VF_MARGINALS_POSE) != 0;
+    if (flags & ~(unsigned)(VF_MARGINALS_FAR | VF_MARGINALS_POSE | VF_MARGINALS_TAIL)) return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: unknown flags 0x%x", flags);
+    const bool far = (flags & VF_MARGINALS_FAR) != 0, pose = (flags & VF_MARGINALS_POSE) != 0, tail = (flags & VF_MARGINALS_TAIL) != 0;
+    if (tail && (far || pose))
+        return fail(VF_ERR_INVALID, "vf_engine_marginals_ex: VF_MARGINALS_TAIL goes with neither VF_MARGINALS_FAR (the downdate corrects whole windows) nor VF_MARGINALS_POSE (records of every keyframe)");
     Entry entry_(e, Entry::reads, Entry::leaves_result);      // (nothing here touches the result block of the last solve)
     if (int rc = not_sharded(e, "vf_engine_marginals")) return rc;
     e->recount_far();
@@ -66,7 +71,7 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     const vf::SolvePlan plan = vf::solve_plan(solve_inputs(e, false));
     if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
     vf::launch_band_factor(a, plan, e->stream);
-    vf::launch_selinv(a, e->sig_fail(), e->sig, e->stream);
+    vf::launch_selinv(a, e->sig_fail(), e->sig, tail ? MARGINALS_TAIL_DEPTH : 0, e->stream);
     for (int w0 = 0; w0 < e->v.B && m > 0; w0 += group) {
         vf::FarCov fc{};
         fc.Z = e->fc_scratch;
@@ -84,7 +89,9 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     HIPCHK(hipGetLastError());
     e->sig_lo = e->h_lo;
     e->sig_hi = e->h_hi;
-    e->mem.covariances_computed(pose);
+    for (int w = 0; w < e->v.B && tail; w++) e->sig_lo[w] = std::max(e->h_lo[w], e->h_hi[w] - MARGINALS_TAIL_DEPTH);
+    if (tail) e->mem.covariances_computed_tail();
+    else e->mem.covariances_computed(pose);
     return VF_OK;
 }
 

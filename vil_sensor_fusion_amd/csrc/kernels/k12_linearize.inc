@@ -208,24 +208,14 @@ __global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_imu(View v, in
     linearize_imu_factor<false>(v, which, (long)blockIdx.x * K1_BLOCK + threadIdx.x);
 }
 
-// BetweenFactor<Pose3> between the keyframes in slots ga -> gk at the states of buffer b: whitened residual (6) and
-// Jacobians (Ja 36, Jb 36) written to out[f * ostride], record read from in[f * istride].  `jac` = false: residual only.
-template <bool SH>
-__device__ __forceinline__ void between_core(const View& v, const int b, const long ga, const long gk,
-                                             const double* __restrict__ in, const size_t istride,
-                                             double* __restrict__ out, const size_t ostride, const bool jac) {
-#define IN(f) in[(size_t)(f) * istride]
-    struct NtRef { double* p; VF_DI void operator=(double x) const { __builtin_nontemporal_store(x, p); } };
-    struct NtJac { double* p; bool on; VF_DI void operator=(double x) const { if (!SH || on) __builtin_nontemporal_store(x, p); } };
-#define OUT(f) (NtRef{out + (size_t)(f) * ostride})
-#define JOUT(f) (NtJac{out + (size_t)(f) * ostride, jac})
-
-    const Q4 qa = q4(XS(b, 0, ga), XS(b, 1, ga), XS(b, 2, ga), XS(b, 3, ga));
-    const V3 ta = v3(XS(b, 4, ga), XS(b, 5, ga), XS(b, 6, ga));
-    const Q4 qb = q4(XS(b, 0, gk), XS(b, 1, gk), XS(b, 2, gk), XS(b, 3, gk));
-    const V3 tb = v3(XS(b, 4, gk), XS(b, 5, gk), XS(b, 6, gk));
-    const Q4 qm = q4(IN(0), IN(1), IN(2), IN(3));
-    const V3 tm = v3(IN(4), IN(5), IN(6));
+// BetweenFactor<Pose3> on values: the poses (qa, ta) -> (qb, tb), the record's 28 words answered by rec(f) (measured pose 7, square-root
+// information 21).  The whitened residual goes to sink.r(row, x), the whitened Jacobians to sink.ja / sink.jb(row * 6 + col, x), in the
+// order K2 has always stored them; the unwhitened residual [rot, trans] is returned.  K2 calls it on the window's states
+// (between_core); k_gate_between (kernels/kgate.inc) with a predicted pose in registers.
+template <class Rec, class Sink>
+__device__ __forceinline__ Xi6 between_values(const Q4 qa, const V3 ta, const Q4 qb, const V3 tb, const Rec& rec, Sink& sink) {
+    const Q4 qm = q4(rec(0), rec(1), rec(2), rec(3));
+    const V3 tm = v3(rec(4), rec(5), rec(6));
 
     // hx = T_a^-1 T_b ; err = measured^-1 hx ; r = Logmap(err)
     const M3 Ra = qrot(qa), Rm = qrot(qm);
@@ -244,14 +234,14 @@ __device__ __forceinline__ void between_core(const View& v, const int b, const l
 
     double Rw[21];
 #pragma unroll
-    for (int i = 0; i < 21; i++) Rw[i] = IN(7 + i);
+    for (int i = 0; i < 21; i++) Rw[i] = rec(7 + i);
     const double ru[6] = {xi.w.x, xi.w.y, xi.w.z, xi.u.x, xi.u.y, xi.u.z};
 #pragma unroll
     for (int r = 0; r < 6; r++) {
         double s = 0.0;
 #pragma unroll
         for (int c = r; c < 6; c++) s = fma(Rw[off6(r) + c - r], ru[c], s);
-        OUT(r) = s;
+        sink.r(r, s);
     }
 #pragma unroll
     for (int c = 0; c < 6; c++) {
@@ -278,13 +268,39 @@ __device__ __forceinline__ void between_core(const View& v, const int b, const l
                 sa = fma(Rw[off6(r) + l - r], ua[l], sa);
                 sb = fma(Rw[off6(r) + l - r], ub[l], sb);
             }
-            JOUT(6 + r * 6 + c) = sa;
-            JOUT(42 + r * 6 + c) = sb;
+            sink.ja(r * 6 + c, sa);
+            sink.jb(r * 6 + c, sb);
         }
     }
-#undef IN
-#undef OUT
-#undef JOUT
+    return xi;
+}
+
+// ... between the keyframes in slots ga -> gk at the states of buffer b (the loads): whitened residual (6) and
+// Jacobians (Ja 36, Jb 36) written to out[f * ostride], record read from in[f * istride].  `jac` = false: residual only.
+template <bool SH>
+__device__ __forceinline__ void between_core(const View& v, const int b, const long ga, const long gk,
+                                             const double* __restrict__ in, const size_t istride,
+                                             double* __restrict__ out, const size_t ostride, const bool jac) {
+    struct Rec {
+        const double* __restrict__ in;
+        size_t istride;
+        VF_DI double operator()(int f) const { return in[(size_t)f * istride]; }
+    };
+    struct Sink {
+        double* __restrict__ out;
+        size_t ostride;
+        bool jac;
+        VF_DI void r(int f, double x) { __builtin_nontemporal_store(x, out + (size_t)f * ostride); }
+        VF_DI void j(int f, double x) { if (!SH || jac) __builtin_nontemporal_store(x, out + (size_t)f * ostride); }
+        VF_DI void ja(int e, double x) { j(6 + e, x); }
+        VF_DI void jb(int e, double x) { j(42 + e, x); }
+    };
+    const Q4 qa = q4(XS(b, 0, ga), XS(b, 1, ga), XS(b, 2, ga), XS(b, 3, ga));
+    const V3 ta = v3(XS(b, 4, ga), XS(b, 5, ga), XS(b, 6, ga));
+    const Q4 qb = q4(XS(b, 0, gk), XS(b, 1, gk), XS(b, 2, gk), XS(b, 3, gk));
+    const V3 tb = v3(XS(b, 4, gk), XS(b, 5, gk), XS(b, 6, gk));
+    Sink sink{out, ostride, jac};
+    between_values(qa, ta, qb, tb, Rec{in, istride}, sink);
 }
 
 template <bool SH>

@@ -14,10 +14,12 @@
 // the way to a shorter step.
 // Output per slot (View-sized array sig, SIG_SLOT doubles): Sigma_kk as its lower triangle (h_tri order), then Sigma_{k+1,k}
 // (15 x 15 row-major, row = dof of k+1; zero for the window's last keyframe).  Windows whose sweep failed are left alone.
+// depth > 0: the recursion stops after that many keyframes -- the blocks of the tail cost their own steps only, and are the bits of
+// the whole-window call (each step reads what the steps behind it left, nothing in front).
 constexpr int SI_LD = 16, SS_LD = 28;
 constexpr int SI_ENT = 42 * 15;                    // panel entries used: 27 rows of B, 15 rows of U (the rhs row is not)
 constexpr int SI_PF = (SI_ENT + 63) / 64;          // ... per lane
-__global__ void __launch_bounds__(64) k_band_selinv(View v, const int* __restrict__ failed, double* __restrict__ sig) {
+__global__ void __launch_bounds__(64) k_band_selinv(View v, const int* __restrict__ failed, double* __restrict__ sig, const int depth) {
     const int w = blockIdx.x, lane = threadIdx.x;
     const int lo = v.lo[w], hi = v.hi[w];
     if (hi - lo <= 0 || hi > v.M || lo < 0 || failed[w]) return;
@@ -38,7 +40,8 @@ __global__ void __launch_bounds__(64) k_band_selinv(View v, const int* __restric
     };
     fetch(hi - 1);
     int cur = 0;
-    for (int k = hi - 1; k >= lo; k--) {
+    const int stop = depth > 0 && hi - depth > lo ? hi - depth : lo;     // (the tail only: vf_engine_marginals_ex, VF_MARGINALS_TAIL)
+    for (int k = hi - 1; k >= stop; k--) {
 #pragma unroll
         for (int t = 0; t < SI_PF; t++) {
             const int e = lane + 64 * t, r = e / 15, c = e - 15 * (e / 15);
@@ -90,6 +93,6 @@ __global__ void __launch_bounds__(64) k_band_selinv(View v, const int* __restric
     }
 }
 void launch_band_factor(const View& v, const SolvePlan& plan, hipStream_t s) { launch_band_forward(v, plan.factor, s); }
-void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s) {
-    hipLaunchKernelGGL(k_band_selinv, dim3(v.B), dim3(64), 0, s, v, failed, sig);
+void launch_selinv(const View& v, const int* failed, double* sig, int depth, hipStream_t s) {
+    hipLaunchKernelGGL(k_band_selinv, dim3(v.B), dim3(64), 0, s, v, failed, sig, depth);
 }

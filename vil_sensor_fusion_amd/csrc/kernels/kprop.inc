@@ -16,35 +16,16 @@
 // F, P, Sigma, A and the products live in LDS (5 x 225 + 2 x 54 doubles, 9.9 KB), thread (i, j) owns entry (i, j); no scratch (pick9).
 // No samples: the keyframe's state and Sigma_ii are copied, bit for bit -- F = I, P = 0 pass through no arithmetic.
 // out: [B][16 + 225].  A window whose marginals failed (sig_failed) gets a NaN covariance and a valid state; an empty window NaNs.
-__global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict__ off, const double* __restrict__ steps, ImuCov prm,
-                                                  int with_cov, int from_estimate, const double* __restrict__ sig,
-                                                  const int* __restrict__ sig_failed, double* __restrict__ out) {
-    const int w = blockIdx.x, tid = threadIdx.x;
-    if (w >= v.B) return;
-    __shared__ double sF[225], sP[225], sT[225], sS[225], sA[225], sH[54], sHn[54];
+//
+// Steps (a), (b) and the entries of A are routines of their own, one copy each: k_gate_between (kernels/kgate.inc) calls them too.
+// (a): the samples steps[s0 .. s1), s1 > s0, integrated from zero with the biases (bacc, bgyr).  Every thread of the 256-thread workgroup calls it; on return P is in sP, the
+// 9 x 6 bias Jacobians in sH (behind a barrier), the mean and the summed dt in every thread's registers.  sF, sT, sHn: scratch.
+struct PropMean { V3 th, pos, vel; double dtij; };
+__device__ __forceinline__ PropMean prop_integrate(const double* __restrict__ steps, const int s0, const int s1, const V3 bacc, const V3 bgyr,
+                                                   const ImuCov& prm, double* sF, double* sP, double* sT, double* sH, double* sHn) {
+    const int tid = threadIdx.x;
     const int i = tid / 15, j = tid - i * 15;          // entry of the 15x15 matrices (tid < 225)
     const int hi_ = tid / 6, hj = tid - hi_ * 6;       // entry of the 9x6 bias Jacobian (tid < 54)
-    double* o = out + (size_t)w * (16 + 225);
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    const int hi_w = v.hi[w], lo_w = v.lo[w];
-    if (hi_w <= lo_w || hi_w > v.M) {                  // empty window: nothing to start from
-        if (tid < 241) o[tid] = qnan;
-        return;
-    }
-    const long gk = (long)w * v.M + hi_w - 1;
-    const int b = v.sel[w], bs = from_estimate ? b ^ 1 : b;
-    const bool cov_nan = with_cov && sig_failed[w] != 0;
-    const double* sg = with_cov ? sig + (size_t)gk * SIG_SLOT : nullptr;
-    const int s0 = off[w], s1 = off[w + 1];
-    if (s1 <= s0) {
-        if (tid < 16) o[tid] = XS(bs, tid, gk);
-        if (tid < 225) o[16 + tid] = !with_cov || cov_nan ? qnan : sg[i >= j ? h_tri(i, j) : h_tri(j, i)];
-        return;
-    }
-    double bh[6];
-#pragma unroll
-    for (int c = 0; c < 6; c++) bh[c] = XS(b, 10 + c, gk);
-    const V3 bacc = v3(bh[0], bh[1], bh[2]), bgyr = v3(bh[3], bh[4], bh[5]);
     V3 th = v3(0, 0, 0), pos = v3(0, 0, 0), vel = v3(0, 0, 0);
     double dtij = 0.0;
     if (tid < 225) sP[tid] = 0.0;
@@ -113,11 +94,68 @@ __global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict
         dtij += dt;
         __syncthreads();
     }
+    return PropMean{th, pos, vel, dtij};
+}
+// (b) the prediction from keyframe i's state si: the record's words taken from where prop_integrate left them
+__device__ __forceinline__ ImuPrediction prop_predict(const View& v, const State& si, const PropMean& pm, const double (&bh)[6], const double* sH) {
+    const V3 th = pm.th, pos = pm.pos, vel = pm.vel;
+    const double dtij = pm.dtij;
+    const double mean[9] = {th.x, th.y, th.z, pos.x, pos.y, pos.z, vel.x, vel.y, vel.z};
+    return imu_predict(v, si, [&](int f) { return f == 0 ? dtij : (f < 10 ? mean[f - 1] : (f < 16 ? bh[f - 10] : sH[f - 16])); });
+}
+// (c) entry (i, j) of A, the unwhitened Jacobian of the combined-IMU factor's residual with respect to keyframe i at x_j = predicted
+// (sj, p: the predicted state and the prediction it was made from; sH: the bias Jacobians prop_integrate left)
+__device__ __forceinline__ double prop_A_entry(const State& sj, const ImuPrediction& p, const double* sH, const int i, const int j) {
+    const M3 Rj = qrot(sj.q);
+    const M3 Rji = mulTA(Rj, p.Ri);             // R_j^T R_i
+    const int bi = i / 3, r = i - bi * 3, bj = j / 3, c = j - bj * 3;
+    double x = 0.0;
+    if (i >= 9) x = i == j ? 1.0 : 0.0;        // bias rows: b_i - b_j
+    else if (j < 9) {
+        if (bj == 0) {
+            const M3 X = bi == 0 ? transpose(qrot(qexp(p.tht))) : mulSkew(Rji, neg(bi == 1 ? p.pt : p.vt));   // E^T, -R_ji [p~]x, -R_ji [v~]x
+            x = pick9(X, r * 3 + c);
+        } else if (bj == 1) x = bi == 1 ? pick9(Rji, r * 3 + c) : 0.0;
+        else x = bi == 1 ? p.dt * pick9(Rj, c * 3 + r) : (bi == 2 ? pick9(Rj, c * 3 + r) : 0.0);
+    } else {
+        const int cb = j - 9;
+        const V3 h = v3(sH[(bi * 3 + 0) * 6 + cb], sH[(bi * 3 + 1) * 6 + cb], sH[(bi * 3 + 2) * 6 + cb]);
+        x = vget(bi == 0 ? mul(so3_jr(p.tht), h) : mul(Rji, h), r);
+    }
+    return x;
+}
+__global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict__ off, const double* __restrict__ steps, ImuCov prm,
+                                                  int with_cov, int from_estimate, const double* __restrict__ sig,
+                                                  const int* __restrict__ sig_failed, double* __restrict__ out) {
+    const int w = blockIdx.x, tid = threadIdx.x;
+    if (w >= v.B) return;
+    __shared__ double sF[225], sP[225], sT[225], sS[225], sA[225], sH[54], sHn[54];
+    const int i = tid / 15, j = tid - i * 15;          // entry of the 15x15 matrices (tid < 225)
+    double* o = out + (size_t)w * (16 + 225);
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const int hi_w = v.hi[w], lo_w = v.lo[w];
+    if (hi_w <= lo_w || hi_w > v.M) {                  // empty window: nothing to start from
+        if (tid < 241) o[tid] = qnan;
+        return;
+    }
+    const long gk = (long)w * v.M + hi_w - 1;
+    const int b = v.sel[w], bs = from_estimate ? b ^ 1 : b;
+    const bool cov_nan = with_cov && sig_failed[w] != 0;
+    const double* sg = with_cov ? sig + (size_t)gk * SIG_SLOT : nullptr;
+    const int s0 = off[w], s1 = off[w + 1];
+    if (s1 <= s0) {
+        if (tid < 16) o[tid] = XS(bs, tid, gk);
+        if (tid < 225) o[16 + tid] = !with_cov || cov_nan ? qnan : sg[i >= j ? h_tri(i, j) : h_tri(j, i)];
+        return;
+    }
+    double bh[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) bh[c] = XS(b, 10 + c, gk);
+    const V3 bacc = v3(bh[0], bh[1], bh[2]), bgyr = v3(bh[3], bh[4], bh[5]);
+    const PropMean pm = prop_integrate(steps, s0, s1, bacc, bgyr, prm, sF, sP, sT, sH, sHn);
     // (b) the state (b_i - bhat is zero unless from_estimate)
     const State si = load_state(v, bs, gk);
-    const double mean[9] = {th.x, th.y, th.z, pos.x, pos.y, pos.z, vel.x, vel.y, vel.z};
-    const ImuPrediction p =
-        imu_predict(v, si, [&](int f) { return f == 0 ? dtij : (f < 10 ? mean[f - 1] : (f < 16 ? bh[f - 10] : sH[f - 16])); });
+    const ImuPrediction p = prop_predict(v, si, pm, bh, sH);
     const State sj = predicted_state(si, p);
     if (tid == 0) {
         o[0] = sj.q.w; o[1] = sj.q.x; o[2] = sj.q.y; o[3] = sj.q.z;
@@ -132,23 +170,7 @@ __global__ void __launch_bounds__(256) k_propagate(View v, const int* __restrict
     }
     // (c) A (DESIGN.md "K1" at r_theta = 0) into sA, Sigma_ii into sS
     if (tid < 225) {
-        const M3 Rj = qrot(sj.q);
-        const M3 Rji = mulTA(Rj, p.Ri);             // R_j^T R_i
-        const int bi = i / 3, r = i - bi * 3, bj = j / 3, c = j - bj * 3;
-        double x = 0.0;
-        if (i >= 9) x = i == j ? 1.0 : 0.0;        // bias rows: b_i - b_j
-        else if (j < 9) {
-            if (bj == 0) {
-                const M3 X = bi == 0 ? transpose(qrot(qexp(p.tht))) : mulSkew(Rji, neg(bi == 1 ? p.pt : p.vt));   // E^T, -R_ji [p~]x, -R_ji [v~]x
-                x = pick9(X, r * 3 + c);
-            } else if (bj == 1) x = bi == 1 ? pick9(Rji, r * 3 + c) : 0.0;
-            else x = bi == 1 ? p.dt * pick9(Rj, c * 3 + r) : (bi == 2 ? pick9(Rj, c * 3 + r) : 0.0);
-        } else {
-            const int cb = j - 9;
-            const V3 h = v3(sH[(bi * 3 + 0) * 6 + cb], sH[(bi * 3 + 1) * 6 + cb], sH[(bi * 3 + 2) * 6 + cb]);
-            x = vget(bi == 0 ? mul(so3_jr(p.tht), h) : mul(Rji, h), r);
-        }
-        sA[tid] = x;
+        sA[tid] = prop_A_entry(sj, p, sH, i, j);
         sS[tid] = sg[i >= j ? h_tri(i, j) : h_tri(j, i)];
     }
     __syncthreads();

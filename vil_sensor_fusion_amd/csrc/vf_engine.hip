@@ -229,6 +229,13 @@ struct vf_engine : EngineHandle {
     vf::DeviceBuf<double> prop_out;
     hipEvent_t prop_ev[3] = {nullptr, nullptr, nullptr};
     bool prop_pending = false;
+    // vf_engine_gate_tail (engine/engine_gate.inc): the same again, of its own -- neither Kprop's nor the ingest's, either may be in
+    // flight -- and the output, [B] records of vf_gate_result's layout.  Whether it holds anything is SolveMemory's to say (gate_valid).
+    vf::PinnedBuf<char> gate_host;
+    vf::DeviceBuf<char> gate_dev;
+    vf::DeviceBuf<char> gate_out;
+    hipEvent_t gate_ev[3] = {nullptr, nullptr, nullptr};
+    bool gate_pending = false;
     // far between factors (View::x_*): host mirror of how many slots are in use (the low-rank correction solves 6 right-hand
     // sides per slot in use), the right-hand-side scratch and the solved columns Z
     int x_used = 0;
@@ -407,5 +414,6 @@ extern "C" {
 #include "engine/engine_read.inc"
 #include "engine/engine_marginals.inc"
 #include "engine/engine_propagate.inc"
+#include "engine/engine_gate.inc"
 #include "engine/engine_errors.inc"
 }  // extern "C"

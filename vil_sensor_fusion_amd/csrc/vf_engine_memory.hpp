@@ -7,7 +7,8 @@
 // the pose records, the scores: each only with the one before it).  A sixth outlives the arrays' next solve too: the last IMU-rate
 // propagation (vf_engine_propagate_tail), which only a grown engine loses.  A seventh is a fact about the residuals rather than a
 // saving: whether the current buffer's whitened residuals are those of the current states, so that vf_engine_factor_errors may read
-// them as they lie (residuals_vouched), with the per-factor errors that call left (errors_valid).  Every entry point of the engine
+// them as they lie (residuals_vouched), with the per-factor errors that call left (errors_valid).  An eighth is the innovation gate's result
+// (vf_engine_gate_tail: gate_valid), which a compacted or grown engine loses.  Every entry point of the engine
 // says what it did through one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
 #pragma once
 
@@ -86,9 +87,9 @@ class SolveMemory {
         warm_ = ahead_valid_ = res_current_ = false;
     }
     // the window was compacted: the covariance blocks stay in the slots they were computed for
-    void compacted() { rewritten(), covariances_started(), err_valid_ = false; }
+    void compacted() { rewritten(), covariances_started(), err_valid_ = gate_valid_ = false; }
     // the engine was grown: new arrays, nothing linearised in them yet, no covariances
-    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = err_valid_ = false; }
+    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = err_valid_ = gate_valid_ = false; }
     // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
     void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
     void stash_committed() { ahead_valid_ = false; }
@@ -102,10 +103,12 @@ class SolveMemory {
     // an entry point ran: the cached result is void, unless the entry point leaves the result block alone
     void entry_ran(bool leaves_result) { res_cached_ = res_cached_ && leaves_result; }
     // vf_engine_marginals_ex is about to free or overwrite what the last one left: void from here on, whether or not it gets through
-    void covariances_started() { sig_valid_ = pose_valid_ = false, score_rows_ = 0; }
+    void covariances_started() { sig_valid_ = pose_valid_ = sig_tail_ = false, score_rows_ = 0; }
     // ... it got through, with the pose records (VF_MARGINALS_POSE) or, as the plain vf_engine_marginals, without; scores are of the
     // records of one call: none yet
-    void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, score_rows_ = 0, residuals_current(); }
+    void covariances_computed(bool pose = false) { sig_valid_ = true, pose_valid_ = pose, sig_tail_ = false, score_rows_ = 0, residuals_current(); }
+    // ... it got through with VF_MARGINALS_TAIL: the blocks of every window's last two keyframes only, no pose records
+    void covariances_computed_tail() { covariances_computed(false), sig_tail_ = true; }
     // vf_engine_marginal_scores left `rows` rows of scores (0: it is about to overwrite them)
     void scores_computed(int rows) { score_rows_ = rows; }
     // vf_engine_propagate_tail left a propagation in its own buffer, with or without the covariance.  It is of the arrays it was
@@ -115,6 +118,9 @@ class SolveMemory {
     // They are of the call that wrote them: later solves leave them, a compacted or grown engine loses them
     void errors_started() { err_valid_ = false; }
     void errors_computed() { err_valid_ = true; }
+    // vf_engine_gate_tail left a result for every window in its own buffer.  It is of the call that wrote it: later solves leave
+    // it, a compacted or grown engine loses it
+    void gated() { gate_valid_ = true; }
 
     // ---- queries
     // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
@@ -135,6 +141,9 @@ class SolveMemory {
     // the current buffer's residuals are those of the current states (never on engines with excursions or incremental updates)
     bool residuals_vouched() const { return res_current_ && !excursions && !incremental; }
     bool errors_valid() const { return err_valid_; }
+    // the covariances are valid, but of every window's tail only (its last two keyframes)
+    bool covariances_tail_only() const { return sig_valid_ && sig_tail_; }
+    bool gate_valid() const { return gate_valid_; }
 
   private:
     // what rewritten() does to the savings, for the events that are rewrites inside but say themselves what becomes of the residuals
@@ -152,6 +161,7 @@ class SolveMemory {
     int score_rows_ = 0;
     bool prop_valid_ = false, prop_cov_ = false;
     bool res_current_ = false, err_valid_ = false;
+    bool sig_tail_ = false, gate_valid_ = false;
 };
 
 }  // namespace vf

@@ -232,7 +232,7 @@ int vf_set_initial_state(vf_graph* g, const double state16[16]) {
     int rc;
     if ((rc = vf_engine_set_states(g->eng, 0, 0, 1, st)) || (rc = vf_engine_set_prior(g->eng, 0, 0, rec))) return rc;
     memcpy(g->state, st, sizeof(st));
-    g->cov_valid = g->err_valid = false;
+    g->cov_valid = g->cov_tail = g->err_valid = false;
     memcpy(g->anchor, st, sizeof(st));
     return VF_OK;
 }
@@ -365,16 +365,23 @@ int vf_most_recent_pose_time(vf_graph* g, double* time, uint64_t* key) {
     return VF_OK;
 }
 
+// the 28-double record of a between factor from what the caller hands in, validated: vf_add_between and vf_gate_between
+// (vf_graph_gate.cpp) refuse the same inputs with the same codes
+int vf_between_record_(const double q[4], const double t[3], const double cov[36], double rec[VF_BTW_RECORD]) {
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(n > 0.0) || !std::isfinite(n)) return gerr(VF_ERR_INVALID, "between rotation is not a quaternion");
+    for (int i = 0; i < 4; i++) rec[i] = q[i] / n;  // gtsam::Rot3(w,x,y,z) normalises
+    for (int i = 0; i < 3; i++) rec[4 + i] = t[i];
+    if (!sqrt_info_upper6(cov, rec + 7)) return gerr(VF_ERR_NOT_SPD, "between covariance is not symmetric positive definite");
+    return VF_OK;
+}
+
 int vf_add_between(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36]) {
     if (!g || !q || !t || !cov) return gerr(VF_ERR_INVALID, "null argument");
     PendingBetween b;
     b.a = prev;
     b.b = cur;
-    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(n > 0.0) || !std::isfinite(n)) return gerr(VF_ERR_INVALID, "between rotation is not a quaternion");
-    for (int i = 0; i < 4; i++) b.rec[i] = q[i] / n;  // gtsam::Rot3(w,x,y,z) normalises
-    for (int i = 0; i < 3; i++) b.rec[4 + i] = t[i];
-    if (!sqrt_info_upper6(cov, b.rec + 7)) return gerr(VF_ERR_NOT_SPD, "between covariance is not symmetric positive definite");
+    if (int rc = vf_between_record_(q, t, cov, b.rec)) return rc;
     std::lock_guard<std::mutex> lk(g->graph_mutex);  // GraphManager.cpp:85
     if (prev >= cur || cur > g->current_key) return gerr(VF_ERR_BAD_KEY, "between factor keys (%llu, %llu) not reserved in order", (unsigned long long)prev, (unsigned long long)cur);
     bool band = cur - prev <= VF_MAX_BANDWIDTH && !g->has_band_end(cur);
@@ -466,9 +473,10 @@ static int marginal_covariance(vf_graph* g, uint64_t key, double* cov225) {
     if (!g->solved_once) return gerr(VF_ERR_INVALID, "no solve yet: there is no covariance to report");
     if (key > g->solved_key) return gerr(VF_ERR_BAD_KEY, "key %llu not solved yet (last solved key %llu)", (unsigned long long)key, (unsigned long long)g->solved_key);
     if (key < oldest_key(g)) return gerr(VF_ERR_BAD_KEY, "key %llu has left the window (oldest key %llu)", (unsigned long long)key, (unsigned long long)oldest_key(g));
-    if (!g->cov_valid) {
+    if (!g->cov_valid || g->cov_tail) {      // (tail-only covariances, left by vf_gate_between, answer for the last two keys only: the full ones are computed)
         // (far_covariance: far factors alive, loop closures and what the marginalisation has left of them, downdate the band's
         // covariances; without it they are refused as they always were)
+        g->cov_valid = g->cov_tail = false;
         if (int rc = g->opts.far_covariance ? vf_engine_marginals_ex(g->eng, VF_MARGINALS_FAR) : vf_engine_marginals(g->eng)) return rc;
         g->cov_valid = true;
         g->cov_pose = false;
@@ -742,7 +750,7 @@ int vf_solve(vf_graph* g) {
     int rc, fails = 0, flags = 0;
     {
         std::lock_guard<std::mutex> sl(g->state_mutex);  // :117
-        g->cov_valid = g->err_valid = false;
+        g->cov_valid = g->cov_tail = g->err_valid = false;
         (rc = refuse_late(g, t)) || (rc = make_room(g, t, lap)) || (rc = marginalise(g, t, lap)) || (rc = stage_imu(g, t, lap)) || (rc = stage_band(g, t, lap)) ||
             (rc = adopt_engine_far_list(g, t)) || (rc = stage_far_list(g, t, lap)) || (rc = vf_engine_set_range(g->eng, 0, g->lo, slot_of(g, t.last_key) + 1));
         t.requeue = rc != VF_OK;    // up to here a failure gives the take back; the optimisation consumes it, whatever it returns

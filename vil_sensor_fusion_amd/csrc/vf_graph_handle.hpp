@@ -70,9 +70,12 @@ struct vf_graph {
     std::vector<std::pair<vf_cov_callback, void*>> cov_callbacks;
     bool solved_once = false;   // a vf_solve has succeeded
     bool cov_valid = false;     // the engine holds the covariances of the window as the last solve left it (vf_engine_marginals)
+    bool cov_tail = false;      // ... of the last two keys only (VF_MARGINALS_TAIL, vf_graph_gate.cpp): whoever needs more computes the full ones
     bool cov_pose = false;      // ... computed with VF_MARGINALS_POSE: the nav_msgs records are there too (vf_graph_scores.cpp)
     bool err_valid = false;     // the engine holds the per-factor errors of the window as the last solve left it (vf_graph_errors.cpp)
 };
+
+extern "C" int vf_between_record_(const double q[4], const double t[3], const double cov[36], double rec[VF_BTW_RECORD]);   // vf_graph.cpp
 
 // key -> keyframe slot of the handle's one window, and the oldest key still in it
 static inline int slot_of(const vf_graph* g, uint64_t key) { return (int)(key - g->key_base); }

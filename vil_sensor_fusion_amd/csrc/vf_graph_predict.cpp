@@ -58,7 +58,7 @@ int vf_predict_state(vf_graph* g, double time, double q[4], double t[3], double 
             // (as vf_get_marginal_covariance: far_covariance takes far factors alive into account; without it they are refused)
             if (int rc = g->opts.far_covariance ? vf_engine_marginals_ex(g->eng, VF_MARGINALS_FAR) : vf_engine_marginals(g->eng)) return rc;
             g->cov_valid = true;
-            g->cov_pose = false;
+            g->cov_pose = g->cov_tail = false;
         }
         flags |= VF_PROPAGATE_COVARIANCE;
     }

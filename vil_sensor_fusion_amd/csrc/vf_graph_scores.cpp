@@ -36,6 +36,7 @@ int vf_get_degeneracy_scores(vf_graph* g, int source, int metric, unsigned subse
         // nav_msgs records: they are computed again with them, the same bits)
         if (int rc = vf_engine_marginals_ex(g->eng, VF_MARGINALS_POSE | (g->opts.far_covariance ? VF_MARGINALS_FAR : 0u))) return rc;
         g->cov_valid = g->cov_pose = true;
+        g->cov_tail = false;
     }
     if (int rc = vf_engine_marginal_scores(g->eng, source, metric, subset_mask)) return rc;
     return vf_engine_read_marginal_scores(g->eng, 0, slot_of(g, key0), n, out);

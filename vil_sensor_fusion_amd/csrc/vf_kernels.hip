@@ -18,6 +18,9 @@
 //   K5 k_retract, k_decide  x (+) delta, cost reduction, LM accept/reject
 //   a2 k_predict, k_slide   PreintegrationBase::predict initial values (GraphManager.cpp:152-160)
 //   k_propagate             the state between two solves at IMU rate, with its propagated covariance (no reference code)
+//   k_gate_between          the innovation test of a between factor before it enters the graph: chi-square of an odometry increment
+//                           against the solved window and the IMU since (no reference code: the estimation-theoretic counterpart
+//                           of the reference's degerate_odometry_filter)
 //   k_factor_errors, k_batch_health
 //                           every factor's chi-square error from the residuals the solve left, a summary per window, the
 //                           batch's health (no reference code: factor->error, graph.error, printErrors of GTSAM)
@@ -143,5 +146,6 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
 #include "kernels/k4_selinv_far.inc"
 #include "kernels/kpose.inc"
 #include "kernels/kprop.inc"
+#include "kernels/kgate.inc"
 #include "kernels/kerr.inc"
 }  // namespace vf

@@ -324,7 +324,9 @@ void launch_count_active(const View& v, hipStream_t s);
 // Sigma_{k+1,k}); windows flagged in `failed` are skipped
 constexpr int SIG_SLOT = 120 + 225;
 void launch_band_factor(const View& v, const SolvePlan& plan, hipStream_t s);
-void launch_selinv(const View& v, const int* failed, double* sig, hipStream_t s);
+// depth: keyframes from the window's end whose blocks are wanted (the recursion runs backward from hi - 1), 0: the whole window; the
+// blocks written are the bits of the whole-window call
+void launch_selinv(const View& v, const int* failed, double* sig, int depth, hipStream_t s);
 // ... with far factors alive (vf_engine_marginals_ex, VF_MARGINALS_FAR): the low-rank downdate of sig (k4_selinv_far.inc) for the
 // windows [w0, w0 + nw), whose scratch FarCov holds; m = 6 x slots in use
 struct FarCov {
@@ -344,6 +346,13 @@ void launch_pose_marginals(const View& v, const int* failed, const double* sig, 
 // out: [B][16 + 225]
 void launch_propagate(const View& v, const int* off, const double* steps, const ImuCov& prm, int with_cov, int from_estimate,
                       const double* sig, const int* sig_failed, double* out, hipStream_t s);
+// Innovation gate (kernels/kgate.inc): for every window, the chi-square (6 dof) of a candidate between factor from slot btw_a[w] to the
+// keyframe the samples lead to, against the window's covariances in sig; reach_lo: [B] the first slot sig covers; out: [B] records of
+// GATE_RECORD bytes (vf_gate_result's layout)
+constexpr size_t GATE_RECORD = 208;
+void launch_gate_between(const View& v, const int* off, const double* steps, const ImuCov& prm, const int* btw_a, const int* reach_lo,
+                         const double* btw_rec, double threshold, int from_estimate, const double* sig, const int* sig_failed,
+                         void* out, hipStream_t s);
 // Per-factor chi-square errors (kernels/kerr.inc; vf_engine_factor_errors): e = 0.5 |whitened residual|^2 of every factor of the
 // current buffer, -1 where a slot holds none, a summary per window and one block for the batch.  ErrSummary and BatchHealth are
 // the device twins of vf_consistency and vf_batch_health (include/vilfusion.h), byte for byte: the word of struct_size is unused.

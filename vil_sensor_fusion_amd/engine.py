@@ -238,6 +238,43 @@ class Engine:
         check(self._l.vf_engine_propagate_status(self._h, C.byref(h), C.byref(k)))
         return h.value, k.value
 
+    def gate_tail(self, step_off, steps, imu_cov, btw_a, btw_rec, threshold=None, from_estimate=False):
+        """Innovation gate for all windows (vf_engine_gate_tail): the chi-square (6 dof) of a candidate between factor from slot
+        btw_a[w] (the window's last keyframe or the one before it; -1: none) to the keyframe the raw samples
+        steps[step_off[w]:step_off[w+1]] lead to, against the window as solved -- marginals() or marginals(tail=True) first.
+        threshold: a window is marked rejected when its nis exceeds it (None: never; _lib.CHI2_6_99 = 16.81, CHI2_6_999 = 22.46).
+        Writes a buffer of its own, nothing else.  Asynchronous; read with read_gate / read_gate_all."""
+        off = np.ascontiguousarray(step_off, dtype=np.int32)
+        st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
+        a = np.ascontiguousarray(btw_a, dtype=np.int32)
+        r = np.ascontiguousarray(btw_rec, dtype=np.float64).reshape(-1, BTW_RECORD)
+        assert off.size == self.windows + 1 and st.shape[0] >= off[-1] and a.size == self.windows and r.shape[0] == self.windows
+        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
+                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
+        check(self._l.vf_engine_gate_tail(self._h, _i(off), _d(st) if st.size else None, C.byref(p), _i(a), _d(r),
+                                          0.0 if threshold is None else float(threshold), _lib.GATE_FROM_ESTIMATE if from_estimate else 0))
+
+    def read_gate(self, window):
+        """the last gate_tail's result for `window` as a dict: status (a name of _lib.GATE_STATUS), rejected, nis, nis_measurement,
+        xi (6,) in [rot, trans] order, state (16,).  Synchronises."""
+        g = _lib.GateResultC()
+        g.struct_size = C.sizeof(g)
+        check(self._l.vf_engine_read_gate(self._h, window, C.byref(g)))
+        return dict(status=_lib.GATE_STATUS[g.status], rejected=bool(g.rejected), nis=g.nis, nis_measurement=g.nis_measurement,
+                    xi=np.array(g.xi[:]), state=np.array(g.state16[:]))
+
+    def read_gate_all(self):
+        """(status (B,) int32 of _lib.GATE_*, nis (B,)) of the last gate_tail, one synchronisation"""
+        s, n = np.zeros(self.windows, dtype=np.int32), np.zeros(self.windows)
+        check(self._l.vf_engine_read_gate_all(self._h, _i(s), _d(n)))
+        return s, n
+
+    def gate_status(self):
+        """waits for the last gate_tail, returns (h2d_ms, kernel_ms) of that call"""
+        h, k = C.c_float(), C.c_float()
+        check(self._l.vf_engine_gate_status(self._h, C.byref(h), C.byref(k)))
+        return h.value, k.value
+
     def get_imu(self, window, k0, n):
         r = np.zeros((n, IMU_RECORD))
         check(self._l.vf_engine_get_imu(self._h, window, k0, n, _d(r)))
@@ -425,13 +462,15 @@ class Engine:
         check(self._l.vf_engine_read_panels(self._h, window, k0, n, _d(p)))
         return p
 
-    def marginals(self, far=False, pose=False):
+    def marginals(self, far=False, pose=False, tail=False):
         """Enqueue the marginal covariances of every window's keyframes at the current states (vf_engine_marginals): undamped
         factorisation + selected inversion.  Leaves the LM state as it was; read them with read_marginals.  far=True
         (vf_engine_marginals_ex with VF_MARGINALS_FAR): far factors alive, linear ones included, correct the covariances by a
         low-rank downdate instead of being refused.  pose=True (VF_MARGINALS_POSE): the same call also leaves every keyframe's
-        pose covariance in nav_msgs order, its inverse and its pose on the device (read_pose_marginals, marginal_scores)."""
-        flags = (_lib.MARGINALS_FAR if far else 0) | (_lib.MARGINALS_POSE if pose else 0)
+        pose covariance in nav_msgs order, its inverse and its pose on the device (read_pose_marginals, marginal_scores).
+        tail=True (VF_MARGINALS_TAIL; with neither of the others): the blocks of every window's last two keyframes only, the bits of
+        the full call at two steps of the selected inversion instead of one per keyframe -- what gate_tail and propagate_tail read."""
+        flags = (_lib.MARGINALS_FAR if far else 0) | (_lib.MARGINALS_POSE if pose else 0) | (_lib.MARGINALS_TAIL if tail else 0)
         if flags:
             check(self._l.vf_engine_marginals_ex(self._h, flags))
         else:

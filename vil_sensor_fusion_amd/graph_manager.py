@@ -158,6 +158,23 @@ class GraphManager:
         check(self._l.vf_predict_state(self._h, C.c_double(time), _d(q), _d(t), _d(v), _d(b), _d(cov) if covariance else None))
         return ((q, t), v, b, cov) if covariance else ((q, t), v, b)
 
+    def gate_between(self, previousKey, currentKey, betweenPose, noiseCovariance, threshold=None):
+        """The innovation test of a between factor before addBetweenFactor takes it (vf_gate_between): how many sigmas the odometry
+        increment lies from where the window as solved, and the queued IMU factors up to currentKey, expect it.  Arguments as
+        addBetweenFactor's; previousKey must be the last solved key or the one before it (else status "out_of_reach").  Returns a
+        dict: status (a name of _lib.GATE_STATUS), rejected (nis > threshold; None: never -- 16.81 is the 99 % quantile of
+        chi-square with 6 degrees of freedom, 22.46 the 99.9 % one), nis, nis_measurement, xi (6,) [rot, trans], state (16,).
+        Consumes and stages nothing.  Not from inside a callback."""
+        q = np.ascontiguousarray(betweenPose[0], dtype=np.float64)
+        t = np.ascontiguousarray(betweenPose[1], dtype=np.float64)
+        cov = np.ascontiguousarray(noiseCovariance, dtype=np.float64).reshape(6, 6)
+        g = _lib.GateResultC()
+        g.struct_size = C.sizeof(g)
+        check(self._l.vf_gate_between(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q), _d(t), _d(cov),
+                                      0.0 if threshold is None else float(threshold), C.byref(g)))
+        return dict(status=_lib.GATE_STATUS[g.status], rejected=bool(g.rejected), nis=g.nis, nis_measurement=g.nis_measurement,
+                    xi=np.array(g.xi[:]), state=np.array(g.state16[:]))
+
     def degeneracy_scores(self, metric, subsets=("all", "trans", "rot"), information=False, key0=None, n=None):
         """One degeneracy metric (a name of degeneracy.ALL_METRICS) on `subsets` of the nav_msgs pose covariance (or,
         information=True, its inverse) of the solved keys key0 .. key0+n-1, computed on the device from the covariances of the

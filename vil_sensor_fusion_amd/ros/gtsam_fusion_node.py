@@ -16,6 +16,9 @@ the reference's identity / at rest, GraphManager.cpp:20-35), reference_compat (p
 (constant-covariance order quirk; both default to true = what the reference does), publish_imu_rate (default
 false; true: every IMU message after the first solve also publishes the state predicted at its stamp, with the propagated
 covariance, as nav_msgs/Odometry on ~odometry_imu -- GraphManager.predict; ~odometry and TF stay as they are).
+sensors/<name>/innovation_gate_chi2 (absent by default: no gate; a chi-square threshold, 6 degrees of freedom -- 16.81 at 99 %,
+22.46 at 99.9 % -- on the innovation of every odometry increment of that sensor before it becomes a factor,
+sensor_manager.SensorManager.innovation_gate).
 NOTE the default solver/lag = 1000 is a deviation: the reference smooths an unbounded iSAM2 graph (= solver/lag 0 here).
 
 Threading: roscpp's ros::spin() runs every callback of the reference node on ONE thread (gtsam_fusion_node.cpp:101).
@@ -86,7 +89,8 @@ class FusionNode:
             sm = SensorManager(self.graph, bool(cfg["optimize_after_odom"]), use_cov,
                                0.0 if use_cov else float(cfg["covariance_linear"]),      # SensorManagerRos.h:50-54
                                0.0 if use_cov else float(cfg["covariance_angular"]),
-                               float(cfg.get("max_time_skip", float("inf"))), reference_compat=compat, noise_order_compat=noise_compat)
+                               float(cfg.get("max_time_skip", float("inf"))), reference_compat=compat, noise_order_compat=noise_compat,
+                               innovation_gate=cfg.get("innovation_gate_chi2"))
             self.sensor_managers[name] = sm
             msg_type = msgs.PointCloud2 if kind == "PointCloud2" else msgs.Image
             self.subs.append(rospy.Subscriber(cfg["sensor_topic"], msg_type, queue_size=1,                    # SensorManagerRos.h:59

@@ -52,7 +52,7 @@ class Odometry:
 class SensorManager:
     def __init__(self, graph_manager, optimize_after_odom, use_odom_covariance=False,
                  covariance_linear=0.1, covariance_angular=0.1, max_time_skip=0.1, reference_compat=True,
-                 noise_order_compat=True):
+                 noise_order_compat=True, innovation_gate=None):
         self.gm = graph_manager
         self.optimize_after_odom = optimize_after_odom
         self.use_odom_covariance = use_odom_covariance
@@ -73,6 +73,14 @@ class SensorManager:
         self.last_valid_key = None
         self.has_received_odometry = False
         self.warnings = deque(maxlen=keep)
+        # Innovation gate (GraphManager.gate_between; no reference code): a chi-square threshold on the nis of every odometry
+        # increment before it becomes a factor -- 16.81 is the 99 % quantile of 6 degrees of freedom, 22.46 the 99.9 % one.  An
+        # increment the gate can test and rejects is not added: (stamp, (previous key, key), nis) goes to `gated`.  One it cannot
+        # test (out of reach, no covariance, no solve yet, ...) is added as always and counted in `ungated`.  None (the default):
+        # the gate is never called.
+        self.innovation_gate = None if innovation_gate is None else float(innovation_gate)
+        self.gated = deque(maxlen=keep)
+        self.ungated = 0
 
     # SensorManagerRos.h:91-103
     def sensorCallback(self, stamp):
@@ -108,6 +116,22 @@ class SensorManager:
             self.warnings.append(f"between factor ({a}, {b}) not added: {exc}")
             return False
 
+    def _gate_rejects(self, stamp, a, b, pose, cov):
+        """True: the increment a -> b failed the innovation test and must not be added"""
+        from ._lib import VilFusionError
+        try:
+            g = self.gm.gate_between(a, b, pose, cov, self.innovation_gate)
+        except VilFusionError as exc:
+            self.ungated += 1
+            self.warnings.append(f"between factor ({a}, {b}) not gated: {exc}")
+            return False
+        if g["status"] != "ok":
+            self.ungated += 1
+            return False
+        if g["rejected"]:
+            self.gated.append((stamp, (a, b), g["nis"]))
+        return g["rejected"]
+
     # SensorManagerRos.cpp:11-120
     def odometryCallback(self, msg: Odometry):
         if not self.has_received_odometry:
@@ -138,7 +162,8 @@ class SensorManager:
                 cov_ros = np.diag([self.covariance_linear] * 3 + [self.covariance_angular] * 3)
             else:                           # Pose3 tangent order [rot, trans]
                 cov_ros = np.diag([self.covariance_angular] * 3 + [self.covariance_linear] * 3)
-            added = self._add_between(self.last_valid_key, found[1], (q, t), cov_ros)
+            if self.innovation_gate is None or not self._gate_rejects(msg.stamp, self.last_valid_key, found[1], (q, t), cov_ros):
+                added = self._add_between(self.last_valid_key, found[1], (q, t), cov_ros)
             if added and self.optimize_after_odom:
                 self.gm.solve()
         self.last_valid_odom = msg
