@@ -777,6 +777,25 @@ int vf_degeneracy_scores_batch(const void* mats, const void* pose, int count, in
  * either is below its threshold (fusion_params.yaml:35-36: 11.5 / 28.9). */
 int vf_dopt_filter_f32(const float* hessians36, int count, float rot_thr, float trans_thr, float* rot_dopt,
                        float* trans_dopt, unsigned char* keep);
+/* Deweight instead of drop: the covariance of an odometry increment from the scan-matching Hessian of its scan, which keeps
+ * what the scan observed and lets go of what it did not (no reference code: the shipped gate above drops the message).
+ *   Hs = (H + H^T) / 2;  H' = D Hs D, D = diag(trans_thr^-1/2 x 3, rot_thr^-1/2 x 3);  H' = V diag(l') V^T;
+ *   g_i = clamp(l'_i, floor, 1);  Sigma = N + N^1/2 [sum_i (1 / g_i - 1) v_i v_i^T] N^1/2,  N = diag(nom6);
+ *   R = chol_upper(Sigma^-1), Sigma^-1 = N^-1/2 V diag(g) V^T N^-1/2 formed without an inversion.
+ * hessians36: (count,6,6) row-major in LOAM / ROS order [trans 3, rot 3], dtype 0 = f64, 1 = f32 (promoted on load: all
+ * arithmetic and every output is float64, and a float32 call returns the bits of the float64 call on the promoted values).
+ * nom6: the nominal covariance of each axis in the same order, > 0; trans_thr, rot_thr > 0: the eigenvalue at and above
+ * which a direction counts as observed (exp(28.9 / 3) and exp(11.5 / 3) give a 3x3 block with every eigenvalue at the
+ * threshold the log det the shipped gate tests); floor in (0, 1]: the least share of the nominal information a direction keeps.
+ * out_order 0: outputs in the input order; 1: in the Pose3 tangent order [rot, trans] of vf_add_between (Sigma is permuted
+ * before R is taken).  The Hessian is read in the frame of the increment's tangent; no frame change is made.
+ * cov36: (count,36) row-major, symmetric to the bit; sqrt_info21 (may be NULL): (count,21), the upper triangle of R by rows --
+ * words 7 .. 27 of a between record; eig6 (may be NULL): (count,6) eigenvalues of Hs (not H'), ascending; deweighted: (count)
+ * the number of g_i < 1.  Where it is 0, Sigma is N and R is diag(1 / sqrt(nom6)), bit for bit.  A message with a non-finite
+ * entry gets deweighted = -1, Sigma = N / floor, the matching R, and NaN in eig6.  count = 0 returns VF_OK without a device. */
+int vf_degeneracy_remap_batch(const void* hessians36, int count, int dtype, const double nom6[6], double trans_thr,
+                              double rot_thr, double floor, int out_order, double* cov36, double* sqrt_info21,
+                              double* eig6, int32_t* deweighted, int reps, float* kernel_ms);
 
 /* ===================================================================== GraphManager surface
  * Drop-in for VILFusion::GraphManager + VILFusion::IMUManager.  ROS-free, usable in simulated

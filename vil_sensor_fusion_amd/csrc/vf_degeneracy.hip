@@ -16,7 +16,8 @@
 // take blocks and return values (spectrum_metrics: the three of SPECTRUM); then what owns memory: stage_series_tile (HBM ->
 // LDS image), pick_block (image -> registers), score_block with Put (values -> output rows), and the three kernels --
 // k_degeneracy (one subset, image in two halves: more waves per SIMD), k_degeneracy_scores (any subsets of a mask from one
-// image) and k_degeneracy_scores_windows (the same over an engine's windows) -- and the C entry points.
+// image) and k_degeneracy_scores_windows (the same over an engine's windows) --, the covariance remapping of a scan's Hessian
+// (jacobi_eig6: cyclic Jacobi WITH eigenvectors; k_remap_covariance, vf_degeneracy_remap_batch) and the C entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -859,6 +860,236 @@ __global__ void k_dopt_filter(const float* __restrict__ h, int count, float rot_
     keep[i] = !(r < rot_thr || t < trans_thr);
 }
 
+// ---- covariance remapping (vf_degeneracy_remap_batch): the directions a scan did not observe are deweighted, not dropped.
+//   Hs = (H + H^T) / 2,  H' = D Hs D with D = diag(trans_thr^-1/2 x 3, rot_thr^-1/2 x 3),  H' = V diag(l') V^T,
+//   g_i = clamp(l'_i, floor, 1),  Sigma = N + N^1/2 [sum_i (1 / g_i - 1) v_i v_i^T] N^1/2,
+//   M = Sigma^-1 = N^-1/2 G N^-1/2 with G = I + sum_i (g_i - 1) v_i v_i^T,  R = chol_upper(M) = chol_upper(G) N^-1/2.
+// Both sums are ADDITIVE corrections of the nominal: with every g_i = 1 their weights are exact zeros, Sigma is N and R is
+// diag(nom^-1/2) to the bit.  Every product under the sums is written so that it does not depend on which of (r, c) comes
+// first (w * (a * b), F * (s_r * s_c)): the block permutation of out_order = 1 permutes bits.
+struct RemapParams {
+    double d[6];        // D, input order [trans 3, rot 3]
+    double nom[6];      // N, input order
+    double s[6];        // N^1/2
+    double is[6];       // N^-1/2 = 1 / sqrt(nom)
+    double floor;
+    int out_order;      // 1: outputs in [rot, trans]
+};
+
+// Cyclic two-sided Jacobi on the symmetric 6 x 6 held as its upper triangle u[21] (entry (r, c), r <= c, at UT(r, c)), with the
+// rotations accumulated into v (columns = eigenvectors, v = I on entry); the eigenvalues are left on the diagonal.  A lane
+// rotates a pair only where that pair still needs it, under its own branch: what a lane computes does not depend on the lanes
+// beside it, and the sweeps a converged lane sits through leave its registers alone.  The sweep loop ends for the whole wave
+// (as jacobi_svd's) once no active lane has rotated.
+#define UT(r, c) ((r) * 6 - (r) * ((r) + 1) / 2 + (c))
+DI void jacobi_eig6(double (&u)[21], double (&v)[36], bool active) {
+    double nrm2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = r; c < 6; c++) nrm2 = fma(u[UT(r, c)], (r == c ? 1.0 : 2.0) * u[UT(r, c)], nrm2);
+    constexpr double tol2 = Lim<double>::eps * Lim<double>::eps;
+    // below this an off-diagonal entry is rounding of the matrix itself (pairs whose diagonal product is zero or negative --
+    // eigenvalues at or below zero -- have no relative scale of their own)
+    const double tiny = tol2 * nrm2;
+#pragma unroll 1
+    for (int sweep = 0; sweep < Lim<double>::sweeps; sweep++) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 5; p++)
+#pragma unroll
+            for (int q = p + 1; q < 6; q++) {
+                const double app = u[UT(p, p)], aqq = u[UT(q, q)], apq = u[UT(p, q)];
+                const double scale = t_abs(app * aqq);
+                const bool need = apq * apq > tol2 * (scale > tiny ? scale : tiny);
+                if (need) {
+                    rotated = true;
+                    double t, c, s;
+                    jacobi_cs<double>(0.5 * (aqq - app), apq, t, c, s);
+                    u[UT(p, p)] = fma(-t, apq, app);
+                    u[UT(q, q)] = fma(t, apq, aqq);
+                    u[UT(p, q)] = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        if (k != p && k != q) {
+                            double& akp = u[k < p ? UT(k, p) : UT(p, k)];
+                            double& akq = u[k < q ? UT(k, q) : UT(q, k)];
+                            const double x = akp, y = akq;
+                            akp = fma(c, x, -(s * y));
+                            akq = fma(s, x, c * y);
+                        }
+                        const double x = v[k * 6 + p], y = v[k * 6 + q];
+                        v[k * 6 + p] = fma(c, x, -(s * y));
+                        v[k * 6 + q] = fma(s, x, c * y);
+                    }
+                }
+            }
+        if (__all(!active || !rotated)) break;
+    }
+}
+
+// ascending order of six values by a fixed network of 12 compare-exchanges (Bose-Nelson)
+DI void sort6(double (&x)[6]) {
+#define CX(i, j) { const double lo = x[i] < x[j] ? x[i] : x[j], hi = x[i] < x[j] ? x[j] : x[i]; x[i] = lo; x[j] = hi; }
+    CX(1, 2) CX(4, 5) CX(0, 2) CX(3, 5) CX(0, 1) CX(3, 4) CX(2, 5) CX(0, 3) CX(1, 4) CX(2, 4) CX(1, 3) CX(2, 3)
+#undef CX
+}
+
+// The wave's rows of W doubles, one per lane, from the LDS image (row of lane l at l * (W | 1): an odd stride, every bank) to
+// dst, the first of them, as 16-byte vectors: n rows, consecutive lanes to consecutive vectors.  dst is 16-byte aligned (a tile
+// begins at a multiple of 64 rows).
+template <int W>
+DI void flush_rows(const double* __restrict__ lds, double* __restrict__ dst, int n, int lane) {
+    constexpr int SW = W | 1;
+    using vec_t = double __attribute__((ext_vector_type(2)));
+    const int total = n * W;
+#pragma unroll 1
+    for (int e = 2 * lane; e + 1 < total; e += 128) {
+        const int m0 = e / W, m1 = (e + 1) / W;
+        vec_t x;
+        x[0] = lds[m0 * SW + (e - m0 * W)];
+        x[1] = lds[m1 * SW + (e + 1 - m1 * W)];
+        *reinterpret_cast<vec_t*>(dst + e) = x;
+    }
+    if ((total & 1) && lane == 0) dst[total - 1] = lds[(n - 1) * SW + W - 1];
+}
+
+// hess: (count, 6, 6) of T, promoted to float64 on load (all arithmetic is float64: a float32 call has the bits of the float64
+// call on the promoted values).  One lane per message, one wave per 64.  cov (count, 36), sqrt_info (count, 21: the upper
+// triangle of R by rows) or null, eig (count, 6: eigenvalues of Hs, ascending) or null, deweighted (count).  Lanes past the end
+// and lanes whose matrix is not finite run on the identity; the latter report -1, Sigma = N / floor, the matching R, NaN.
+template <typename T>
+__global__ void __launch_bounds__(64) k_remap_covariance(const T* __restrict__ hess, int count, RemapParams P, double* __restrict__ cov,
+                                                         double* __restrict__ sqrt_info, double* __restrict__ eig, int* __restrict__ deweighted) {
+    __shared__ double lds[65 * MSTRIDE];
+    const int lane = threadIdx.x, base = blockIdx.x * 64;
+    const int i = base + lane, n = count - base < 64 ? count - base : 64;
+    const bool active = i < count;
+    stage_series_tile<T, false, 64, 0>(reinterpret_cast<T*>(lds), hess, base, count, lane);
+    __syncthreads();
+    T raw[36];
+    pick_block<T, 6>(reinterpret_cast<const T*>(lds) + (lane + 1) * MSTRIDE, 0, active, raw);
+    __syncthreads();          // every lane has its matrix: the image is free for the outputs
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 36; k++) finite = finite && t_abs((double)raw[k]) < (double)INFINITY;
+    const bool solve = active && finite;
+    double hs[36], u[21], v[36];
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            hs[r * 6 + c] = solve ? 0.5 * ((double)raw[r * 6 + c] + (double)raw[c * 6 + r]) : double(r == c);
+            v[r * 6 + c] = double(r == c);
+        }
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = r; c < 6; c++) u[UT(r, c)] = solve ? hs[r * 6 + c] * (P.d[r] * P.d[c]) : double(r == c);
+    const bool want_eig = eig != nullptr;
+    double ev[6];
+    if (want_eig) {           // (uniform) eigenvalues of Hs itself: values only, the solve the metrics use
+        sym_eig<double, 6>(hs, ev, solve);
+        sort6(ev);
+    }
+    jacobi_eig6(u, v, solve);
+    // the weights of the two additive sums: exact zeros where g = 1
+    double wc[6], wm[6];
+    int dw = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const double l = u[UT(k, k)];
+        const double g = l < P.floor ? P.floor : (l > 1.0 ? 1.0 : l);
+        dw += g < 1.0;
+        wc[k] = 1.0 / g - 1.0;
+        wm[k] = g - 1.0;
+    }
+    double fc[21], fm[21];       // upper triangles of sum w v v^T
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = r; c < 6; c++) {
+            double a = 0.0, b = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const double vv = v[r * 6 + k] * v[c * 6 + k];
+                a = fma(wc[k], vv, a);
+                b = fma(wm[k], vv, b);
+            }
+            fc[UT(r, c)] = (r == c ? P.nom[r] : 0.0) + a * (P.s[r] * P.s[c]);
+            fm[UT(r, c)] = (r == c ? 1.0 : 0.0) + b;
+        }
+    if (!finite) {
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = r; c < 6; c++) {
+                fc[UT(r, c)] = r == c ? P.nom[r] / P.floor : 0.0;
+                fm[UT(r, c)] = r == c ? P.floor : 0.0;
+            }
+        dw = -1;
+#pragma unroll
+        for (int k = 0; k < 6; k++) ev[k] = (double)NAN;
+    }
+    // entry (r, c) of the output order, r <= c: out_order 1 swaps the two halves of the index range
+    const bool sw = P.out_order == 1;
+#define PUT(f, r, c) (sw ? f[((r) + 3) % 6 < ((c) + 3) % 6 ? UT(((r) + 3) % 6, ((c) + 3) % 6) : UT(((c) + 3) % 6, ((r) + 3) % 6)] : f[UT(r, c)])
+    double* mine = lds + lane * MSTRIDE;
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = r; c < 6; c++) {
+            const double x = PUT(fc, r, c);
+            mine[r * 6 + c] = x;
+            mine[c * 6 + r] = x;
+        }
+    __syncthreads();
+    flush_rows<36>(lds, cov + (size_t)base * 36, n, lane);
+    if (active) deweighted[i] = dw;
+    if (sqrt_info != nullptr) {     // (uniform)
+        // R' = chol_upper(G) row by row, R = R' N^-1/2; G has its eigenvalues in [floor, 1]
+        double g[21], R[21];
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = r; c < 6; c++) g[UT(r, c)] = PUT(fm, r, c);
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            double d = g[UT(j, j)];
+#pragma unroll
+            for (int k = 0; k < j; k++) d = fma(-R[UT(k, j)], R[UT(k, j)], d);
+            const double rjj = sqrt(d);
+            const double inv = 1.0 / rjj;
+            R[UT(j, j)] = rjj;
+#pragma unroll
+            for (int c = j + 1; c < 6; c++) {
+                double x = g[UT(j, c)];
+#pragma unroll
+                for (int k = 0; k < j; k++) x = fma(-R[UT(k, j)], R[UT(k, c)], x);
+                R[UT(j, c)] = x * inv;
+            }
+        }
+        __syncthreads();
+        double* row = lds + lane * 21;
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = r; c < 6; c++) row[UT(r, c)] = R[UT(r, c)] * (sw ? P.is[(c + 3) % 6] : P.is[c]);
+        __syncthreads();
+        flush_rows<21>(lds, sqrt_info + (size_t)base * 21, n, lane);
+    }
+#undef PUT
+    if (want_eig) {
+        __syncthreads();
+        double* row = lds + lane * 7;
+#pragma unroll
+        for (int k = 0; k < 6; k++) row[k] = ev[k];
+        __syncthreads();
+        flush_rows<6>(lds, eig + (size_t)base * 6, n, lane);
+    }
+}
+#undef UT
+
 int derr(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1032,6 +1263,65 @@ int vf_dopt_filter_f32(const float* hessians, int count, float rot_thr, float tr
     HIPCHK(hipMemcpy(rot_dopt, d_r, count * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(trans_dopt, d_t, count * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(keep, d_k, count, hipMemcpyDeviceToHost));
+    return VF_OK;
+}
+
+int vf_degeneracy_remap_batch(const void* hessians36, int count, int dtype, const double nom6[6], double trans_thr, double rot_thr,
+                              double floor, int out_order, double* cov36, double* sqrt_info21, double* eig6, int32_t* deweighted,
+                              int reps, float* kernel_ms) {
+    if (!hessians36 || !nom6 || !cov36 || !deweighted || count < 0) return derr(VF_ERR_INVALID, "null argument");
+    if (dtype != 0 && dtype != 1) return derr(VF_ERR_INVALID, "dtype must be 0 (f64) or 1 (f32)");
+    if (out_order != 0 && out_order != 1) return derr(VF_ERR_INVALID, "out_order must be 0 (input order) or 1 ([rot, trans])");
+    if (!(trans_thr > 0.0) || !(rot_thr > 0.0) || !std::isfinite(trans_thr) || !std::isfinite(rot_thr))
+        return derr(VF_ERR_INVALID, "eigenvalue thresholds must be positive and finite (trans %g, rot %g)", trans_thr, rot_thr);
+    if (!(floor > 0.0 && floor <= 1.0)) return derr(VF_ERR_INVALID, "floor %g: must lie in (0, 1]", floor);
+    for (int k = 0; k < 6; k++)
+        if (!(nom6[k] > 0.0) || !std::isfinite(nom6[k])) return derr(VF_ERR_INVALID, "nom6[%d] = %g: the nominal covariance must be positive and finite", k, nom6[k]);
+    if (count == 0) return VF_OK;
+    if (int rc = check_device()) return rc;
+    RemapParams P;
+    for (int k = 0; k < 6; k++) {
+        P.d[k] = 1.0 / std::sqrt(k < 3 ? trans_thr : rot_thr);
+        P.nom[k] = nom6[k];
+        P.s[k] = std::sqrt(nom6[k]);
+        P.is[k] = 1.0 / std::sqrt(nom6[k]);
+    }
+    P.floor = floor;
+    P.out_order = out_order;
+    const size_t n = (size_t)count, esz = dtype == 0 ? sizeof(double) : sizeof(float);
+    vf::DeviceBuf<char> d_h;
+    vf::DeviceBuf<double> d_c, d_r, d_e;
+    vf::DeviceBuf<int> d_w;
+    HIPCHK(d_h.ensure(n * 36 * esz));
+    HIPCHK(d_c.ensure(n * 36 * sizeof(double)));
+    if (sqrt_info21) HIPCHK(d_r.ensure(n * 21 * sizeof(double)));
+    if (eig6) HIPCHK(d_e.ensure(n * 6 * sizeof(double)));
+    HIPCHK(d_w.ensure(n * sizeof(int)));
+    HIPCHK(hipMemcpy(d_h, hessians36, n * 36 * esz, hipMemcpyHostToDevice));
+    const dim3 grid((count + 63) / 64);
+    auto launch = [&]() {
+        if (dtype == 0) hipLaunchKernelGGL((k_remap_covariance<double>), grid, dim3(64), 0, 0, (const double*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
+        else hipLaunchKernelGGL((k_remap_covariance<float>), grid, dim3(64), 0, 0, (const float*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
+    };
+    launch();
+    HIPCHK(hipDeviceSynchronize());
+    if (kernel_ms && reps > 0) {
+        Event e0, e1;
+        HIPCHK(hipEventCreate(&e0.ev));
+        HIPCHK(hipEventCreate(&e1.ev));
+        HIPCHK(hipEventRecord(e0.ev, 0));
+        for (int r = 0; r < reps; r++) launch();
+        HIPCHK(hipEventRecord(e1.ev, 0));
+        HIPCHK(hipEventSynchronize(e1.ev));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0.ev, e1.ev));
+        *kernel_ms = ms / reps;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(cov36, d_c, n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+    if (sqrt_info21) HIPCHK(hipMemcpy(sqrt_info21, d_r, n * 21 * sizeof(double), hipMemcpyDeviceToHost));
+    if (eig6) HIPCHK(hipMemcpy(eig6, d_e, n * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(deweighted, d_w, n * sizeof(int), hipMemcpyDeviceToHost));
     return VF_OK;
 }
 

@@ -106,6 +106,43 @@ def spectrum(matrix, matrix_subset="all", dtype=np.float64, reps=0):
     return (res, ms.value) if reps > 0 else res
 
 
+def eigen_threshold(log_det_threshold):
+    """the eigenvalue at which a 3x3 block with three equal eigenvalues has exactly the log det the shipped gate tests"""
+    return float(np.exp(float(log_det_threshold) / 3.0))
+
+
+REMAP_ORDERS = {"loam": 0, "pose3": 1}      # out_order of vf_degeneracy_remap_batch: [trans, rot] as the input / [rot, trans]
+POSE3_FROM_LOAM = np.array([3, 4, 5, 0, 1, 2])     # the block permutation between the two (its own inverse)
+
+
+def remap_covariance(hessians, nom6, trans_thr=eigen_threshold(TRANS_DEGEN_THRESHOLD), rot_thr=eigen_threshold(ROT_DEGEN_THRESHOLD),
+                     floor=1e-6, order="loam", dtype=np.float64, reps=0):
+    """Deweight what a scan did not observe (vf_degeneracy_remap_batch; no reference code): (n,36) or (n,6,6) scan-matching
+    Hessians in LOAM order [trans 3, rot 3] and the nominal covariance nom6 of the six axes in that order -> (cov (n,6,6),
+    sqrt_info (n,21), eig (n,6), deweighted (n,)).  An eigen-direction of the threshold-scaled Hessian whose eigenvalue l' is
+    below 1 keeps the share clamp(l', floor, 1) of its nominal information; the others keep all of it, and where deweighted is
+    0 cov is diag(nom6) to the bit.  sqrt_info is the upper triangle of R = chol(cov^-1) by rows (words 7 .. 27 of a between
+    record), eig the eigenvalues of the symmetrised Hessian itself, ascending.  order="pose3": cov and sqrt_info in the
+    factor's tangent order [rot, trans].  dtype: what the Hessians are handed over as (float32 is promoted on the device; all
+    outputs are float64).  A non-finite Hessian gives deweighted -1, cov = diag(nom6) / floor and NaN eigenvalues.  With
+    reps > 0 also returns the kernel time in ms."""
+    if order not in REMAP_ORDERS:
+        raise ValueError(f"order must be one of {sorted(REMAP_ORDERS)}")
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    h =np.ascontiguousarray(hessians, dtype=dtype).reshape(-1, 36)
+    nom = np.ascontiguousarray(nom6, dtype=np.float64).reshape(-1)
+    if nom.size != 6:
+        raise ValueError("nom6 must hold six values")
+    n = h.shape[0]
+    cov, sq, eig, dw = np.zeros((n, 6, 6)), np.zeros((n, 21)), np.zeros((n, 6)), np.zeros(n, np.int32)
+    ms = C.c_float(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(_lib.lib().vf_degeneracy_remap_batch(vp(h), n, 0 if np.dtype(dtype) == np.float64 else 1, vp(nom), float(trans_thr), float(rot_thr),
+                                               float(floor), REMAP_ORDERS[order], vp(cov), vp(sq), vp(eig), vp(dw), reps, C.byref(ms)))
+    return (cov, sq, eig, dw, ms.value) if reps > 0 else (cov, sq, eig, dw)
+
+
 def dopt_filter(hessians, rot_thr=ROT_DEGEN_THRESHOLD, trans_thr=TRANS_DEGEN_THRESHOLD):
     """(T,36) or (T,6,6) float32 LOAM Hessians -> (rot_dopt, trans_dopt, keep) like the shipped node."""
     h = np.ascontiguousarray(hessians, dtype=np.float32).reshape(-1, 36)

@@ -19,6 +19,9 @@ covariance, as nav_msgs/Odometry on ~odometry_imu -- GraphManager.predict; ~odom
 sensors/<name>/innovation_gate_chi2 (absent by default: no gate; a chi-square threshold, 6 degrees of freedom -- 16.81 at 99 %,
 22.46 at 99.9 % -- on the innovation of every odometry increment of that sensor before it becomes a factor,
 sensor_manager.SensorManager.innovation_gate).
+sensors/<name>/odom_covariance_order ("reference" by default: the message's twist covariance is copied as the reference copies
+it; "ros": it is read as (x, y, z, rx, ry, rz) and permuted to the factor's [rot, trans] -- what a covariance
+remapped by the odometry filter's ~filter/mode = deweight needs to mean what it says; use_odom_covariance only).
 NOTE the default solver/lag = 1000 is a deviation: the reference smooths an unbounded iSAM2 graph (= solver/lag 0 here).
 
 Threading: roscpp's ros::spin() runs every callback of the reference node on ONE thread (gtsam_fusion_node.cpp:101).
@@ -90,7 +93,8 @@ class FusionNode:
                                0.0 if use_cov else float(cfg["covariance_linear"]),      # SensorManagerRos.h:50-54
                                0.0 if use_cov else float(cfg["covariance_angular"]),
                                float(cfg.get("max_time_skip", float("inf"))), reference_compat=compat, noise_order_compat=noise_compat,
-                               innovation_gate=cfg.get("innovation_gate_chi2"))
+                               innovation_gate=cfg.get("innovation_gate_chi2"),
+                               odom_covariance_order=cfg.get("odom_covariance_order", "reference"))
             self.sensor_managers[name] = sm
             msg_type = msgs.PointCloud2 if kind == "PointCloud2" else msgs.Image
             self.subs.append(rospy.Subscriber(cfg["sensor_topic"], msg_type, queue_size=1,                    # SensorManagerRos.h:59

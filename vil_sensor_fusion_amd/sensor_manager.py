@@ -37,6 +37,9 @@ def ros_duration_sec(later_ns: int, earlier_ns: int) -> float:
     return float(sec) + 1e-9 * float(nsec)
 
 
+_TANGENT_FROM_ROS = [3, 4, 5, 0, 1, 2]      # entry k of the factor's tangent [rot, trans] in a nav_msgs (x, y, z, rx, ry, rz) covariance
+
+
 class Odometry:
     """The fields of nav_msgs/Odometry the reference reads.  stamp_ns: header.stamp as integer nanoseconds (what ros::Time
     holds); when absent it is the float stamp rounded to the nanosecond (exact for simulated time, not for epoch stamps)."""
@@ -52,7 +55,7 @@ class Odometry:
 class SensorManager:
     def __init__(self, graph_manager, optimize_after_odom, use_odom_covariance=False,
                  covariance_linear=0.1, covariance_angular=0.1, max_time_skip=0.1, reference_compat=True,
-                 noise_order_compat=True, innovation_gate=None):
+                 noise_order_compat=True, innovation_gate=None, odom_covariance_order="reference"):
         self.gm = graph_manager
         self.optimize_after_odom = optimize_after_odom
         self.use_odom_covariance = use_odom_covariance
@@ -65,6 +68,13 @@ class SensorManager:
         # covariance_angular.  True reproduces that (benign in config/carla: 0.2 / 0.2, 0.1 / 0.1; not in config/san_rafael:
         # 1e-6 / 1e-7, 1e-3 / 1e-4); False puts each where its name says.
         self.noise_order_compat = noise_order_compat
+        # use_odom_covariance only.  "reference": the message's 36 values are copied as the reference copies them (:87), so a
+        # covariance filled as nav_msgs says, (x, y, z, rx, ry, rz), lands on a factor whose tangent order is [rot, trans]
+        # with its blocks crossed (the same SURVEY 3.5-2).  "ros": the message is read as nav_msgs says and its blocks are
+        # permuted to [rot, trans]: a covariance that is not isotropic (DegeneracyGate(mode="deweight")) needs this.
+        if odom_covariance_order not in ("reference", "ros"):
+            raise ValueError('odom_covariance_order must be "reference" or "ros"')
+        self.odom_covariance_order = odom_covariance_order
         # diagnostics kept for the caller, bounded (a node runs for hours: the last `keep` entries of each)
         keep = 4096
         self.skipped = deque(maxlen=keep)    # (previous stamp, stamp) of consecutive odometry messages the max_time_skip test refused
@@ -156,7 +166,9 @@ class SensorManager:
             self.skipped.append((self.last_valid_odom.stamp, msg.stamp))
         if within:
             q, t, tw = self.poseDiff(self.last_valid_odom, msg)
-            if self.use_odom_covariance:
+            if self.use_odom_covariance and self.odom_covariance_order == "ros":
+                cov_ros = tw[np.ix_(_TANGENT_FROM_ROS, _TANGENT_FROM_ROS)].copy()
+            elif self.use_odom_covariance:
                 cov_ros = tw.T.copy()       # std::copy into a column-major Matrix66 (:87)
             elif self.noise_order_compat:   # :91-97, filled [lin,lin,lin,ang,ang,ang] as the reference does
                 cov_ros = np.diag([self.covariance_linear] * 3 + [self.covariance_angular] * 3)
