@@ -232,8 +232,8 @@ int vf_engine_retract(vf_engine* e) { VF_ENTER(e, Entry::rewrites); return retra
 int vf_engine_decide(vf_engine* e, int init) { VF_ENTER(e, Entry::rewrites); return decide(e, init); }
 int vf_engine_close_excursions(vf_engine* e) { VF_ENTER(e, Entry::reads); return close_excursions(e); }
 static int iterate_sequence(vf_engine* e, int iterations) {
-    // every solve starts from lambda0, as a fresh LevenbergMarquardtOptimizer would (k_reset_lambda: but for a window whose
-    // previous solve ended inside an excursion)
+    // every solve starts from lambda0, as a fresh LevenbergMarquardtOptimizer would (k_reset_lambda: but on an engine that runs
+    // excursions, where close_excursions has marked every window to keep its damping)
     int rc;
     const int slid = e->mem.tail();
     vf::launch_reset_lambda(e->v, e->lambda0_dev, slid ? 1 : 0, e->stream);

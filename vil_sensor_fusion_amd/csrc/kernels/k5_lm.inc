@@ -182,13 +182,16 @@ __global__ void __launch_bounds__(1024) k_close_excursion(View v) {
         const int cc = e / (hi - lo), k = lo + e - cc * (hi - lo);
         XS(b, cc, (long)w * v.M + k) = v.x_best[(size_t)cc * v.G + (size_t)w * v.M + k];
     }
-    // (relin doubles as "this solve ended inside an excursion": the next solve then keeps the damping the excursion had reached
-    // instead of starting from lambda0 again -- k_reset_lambda -- or a window that needs more trials than one solve has would
-    // repeat the same first trials for ever)
+    // (carry: the next solve keeps the damping the excursion had reached instead of starting from lambda0 again -- k_reset_lambda --
+    // or a window that needs more trials than one solve has would repeat the same first trials for ever.  The host marks EVERY
+    // window of an engine that runs excursions behind this kernel, vf_engine_close_excursions: this store alone would carry
+    // only the windows cut off inside an excursion)
     if (tid == 0) { v.cost[w] = v.ref_cost[w]; v.prov[w] = 0; v.relin[w] = 1; v.fresh[w] = 1; v.carry[w] = 1; }
 }
-// every solve starts from lambda0, as a fresh LevenbergMarquardtOptimizer would -- except a window whose previous solve was cut
-// off inside an excursion (non-monotone LM), which goes on from the damping it had reached
+// every solve starts from lambda0, as a fresh LevenbergMarquardtOptimizer would -- except on an engine that runs non-monotone LM
+// (lm_excursion > 0): there every window goes on from the damping its previous solve ended with, whether or not that solve was cut
+// off inside an excursion (vf_engine_close_excursions sets carry[] for all windows; include/vilfusion.h "lambda PERSISTS";
+// tests/test_gpu_lm_trace.py::test_damping_carries_between_solves)
 // (clear_done: a warm solve's "no window is converged yet" rides along -- one launch less in front of k_linearize_tail)
 __global__ void __launch_bounds__(256) k_reset_lambda(View v, const double* __restrict__ lambda0, int clear_done) {
     const int w = blockIdx.x * 256 + threadIdx.x;

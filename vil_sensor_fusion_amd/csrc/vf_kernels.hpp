@@ -181,7 +181,7 @@ struct View {
     int* prov;          // [B] provisional trials since the reference point (0: the current point is the reference)
     int* n_prov;        // [B] provisional trials over the life of the engine
     int* relin;         // [B] the current buffer was restored: linearise it again
-    int* carry;         // [B] the last solve ended inside an excursion: the next one keeps its lambda (k_reset_lambda)
+    int* carry;         // [B] the next solve keeps this window's lambda (k_reset_lambda): set for every window at the end of a solve that runs excursions
     int relin_only;     // the linearisation kernels skip windows whose relin flag is clear
     double gauge_floor; // k_marginalize: eigenvalues of the marginal prior's information about the window's global translation and yaw
                         // that have decayed below this are lifted back to it (vf_engine_opts.gauge_floor; 0 = off)
