@@ -297,6 +297,34 @@ int vf_engine_get_extra_between(vf_engine* e, int window, int* n, int32_t* a, in
 int vf_engine_get_linear_far(vf_engine* e, int window, int* n, int32_t* far_end);
 /* the three priors of GraphManager.cpp:27-35 as one diagonal 15-row factor on keyframe k */
 int vf_engine_set_prior(vf_engine* e, int window, int k, const double* rec31);
+/* Robust loss on band between factors (no reference code of its own: GraphManager::addBetweenFactor takes any SharedNoiseModel,
+ * noiseModel::Robust over a Gaussian among them; conventions of GTSAM's mEstimator classes).  With s the norm of the whitened
+ * residual and k > 0 the loss's parameter:
+ *   VF_LOSS_HUBER          rho(s) = s^2 / 2 up to s = k, k (s - k / 2) beyond       weight rho'/s = 1, k / s
+ *   VF_LOSS_CAUCHY         rho(s) = (k^2 / 2) log(1 + s^2 / k^2)                    k^2 / (k^2 + s^2)
+ *   VF_LOSS_GEMAN_MCCLURE  rho(s) = (1 / 2) k^2 s^2 / (k^2 + s^2)                   k^4 / (k^2 + s^2)^2
+ * K2 writes such a factor in its square-root form, r^ = alpha r and J^ = (alpha I + gamma r r^T) J with alpha = sqrt(2 rho) / s and
+ * gamma = alpha' / s: an ordinary least-squares factor whose cost 0.5 |r^|^2 IS rho(s) and whose gradient J^^T r^ is (rho'/s) J^T r,
+ * the gradient GTSAM's reweighting gives.  Everything behind K2 -- the cost of an LM trial (vf_engine_read_lm reports the sum of
+ * rho), the predicted decrease, every solve form, the refined solve, the marginalisation, vf_engine_factor_errors (rho(s), what
+ * NonlinearFactor::error returns under noiseModel::Robust) -- sees that factor and knows nothing of losses.  The Gauss-Newton
+ * matrix differs from GTSAM's (w J^T J): along r it weighs by rho'^2 / (2 rho), across r by 2 rho / s^2; the optimum is the same.
+ * A Huber factor with s <= k is the Gaussian factor to the bit.  A robust factor that is marginalised enters the marginal prior at
+ * the linearisation, hence the weight, it has at that moment.  The innovation gate (vf_engine_gate_tail) stays Gaussian. */
+#define VF_LOSS_NONE 0
+#define VF_LOSS_HUBER 1
+#define VF_LOSS_CAUCHY 2
+#define VF_LOSS_GEMAN_MCCLURE 3
+/* the loss of the band between factors ending at slots b[0..n): an attribute of the SLOT.  A slot without a factor keeps it inertly;
+ * vf_engine_set_between, vf_engine_ingest_tail and vf_engine_clear_between reset the slots they write to VF_LOSS_NONE, so the loss
+ * is set AFTER the record is staged; vf_engine_compact moves it with its slot and vf_engine_grow carries it.  The first call that
+ * sets a loss other than VF_LOSS_NONE makes the two per-slot arrays; an engine that never saw one launches what it always has.
+ * A mutating call like vf_engine_set_between (on an asynchronous engine, n <= 4 enqueues and returns).  VF_ERR_INVALID: a loss id
+ * outside 0..3, k not finite or <= 0 (ignored for VF_LOSS_NONE), a null pointer, a time-sharded engine; VF_ERR_BAD_KEY: a slot
+ * outside the capacity.  Far factors (vf_engine_set_extra_between) take no loss. */
+int vf_engine_set_between_loss(vf_engine* e, int window, int n, const int32_t* b, const int32_t* loss, const double* k);
+/* ... of slots k0 .. k0+n-1 (synchronises); VF_LOSS_NONE and k = 0 everywhere on an engine without the arrays.  Either output may be NULL. */
+int vf_engine_get_between_loss(vf_engine* e, int window, int k0, int n, int32_t* loss, double* k);
 
 /* K0: IMU preintegration on the device.  Factor i (keyframe k0+i) integrates
  * steps[step_off[i] .. step_off[i+1]) (7 doubles each: dt, acc xyz, gyro xyz) with bias estimate
@@ -536,6 +564,7 @@ int vf_engine_solve_form(vf_engine* e, int* form);
 
 /* ---- read-back (synchronises) ---- */
 int vf_engine_read_imu_lin(vf_engine* e, int window, int which, int k0, int n, double* r15, double* J450);
+/* (a factor with a robust loss, vf_engine_set_between_loss, reads back as K2 wrote it: r^ and J^ of its square-root form) */
 int vf_engine_read_between_lin(vf_engine* e, int window, int which, int k0, int n, double* r6,
                                double* Ja36, double* Jb36);
 int vf_engine_read_normal(vf_engine* e, int window, int k0, int n, double* Hband, double* g15);
@@ -871,6 +900,14 @@ int vf_reserve_node(vf_graph* g, double time, uint64_t* key_out);
  * factor (vf_engine_set_extra_between), of which vf_graph_opts.max_far_factors may be alive at once -- VF_ERR_CAPACITY beyond. */
 int vf_add_between(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q_wxyz[4],
                    const double t[3], const double cov36[36]);
+/* GraphManager::addBetweenFactor with noiseModel::Robust over that Gaussian: loss = VF_LOSS_* with its parameter k ("Robust loss on
+ * band between factors" above; vf_engine_set_between_loss behind the record at the solve, on the synchronous and the asynchronous
+ * staging path alike).  Validates as vf_add_between does, with the same codes, and VF_ERR_INVALID for an unknown loss or a k that is
+ * not finite and > 0; loss = VF_LOSS_NONE is vf_add_between.  Band factors only: a pair the band cannot hold (wider than
+ * VF_MAX_BANDWIDTH keyframes, or a second factor ending at cur_key) would be a far factor, which takes no loss -- refused with
+ * VF_ERR_INVALID, nothing staged.  Late odometry that a solve gives back keeps its loss. */
+int vf_add_between_robust(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q_wxyz[4], const double t[3],
+                          const double cov36[36], int loss, double k);
 /* GraphManager::addFactor(const CombinedImuFactor&) (GraphManager.cpp:90-94): queue a READY-MADE preintegrated factor
  * X(key-1),V(key-1),X(key),V(key),B(key-1),B(key) as its 190-double record (layout at the top of this file; e.g. what
  * vf_get_imu_factor returns) instead of cutting one from the IMU buffer.  key must be the next key (current + 1); the
@@ -959,6 +996,9 @@ int vf_graph_staged(vf_graph* g, int* staged_factors, int* queued_imu_factors);
  * pointer may be null.  VF_ERR_BAD_KEY beyond the end. */
 int vf_graph_get_staged(vf_graph* g, int index, int* kind, uint64_t* key1, uint64_t* key2, double q[4], double t[3],
                         double cov36[36]);
+/* ... and its loss (the companion of vf_graph_get_staged, same index): VF_LOSS_NONE and 0 for the priors and for a Gaussian factor.
+ * Either output pointer may be null.  VF_ERR_BAD_KEY beyond the end. */
+int vf_graph_get_staged_loss(vf_graph* g, int index, int* loss, double* k);
 /* diagnostics (extra): cost after the last solve and the LM trials accepted / rejected / failed (normal equations not
  * positive definite) over the life of the handle */
 int vf_graph_lm_stats(vf_graph* g, double* cost, int* accepted, int* rejected, int* solve_failures);

@@ -142,6 +142,12 @@ int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, con
             memcpy(arg.r, rec + (size_t)i * vf::BTW_IN, sizeof(arg.r));
             vf::launch_put_between(e->v, (long)window * M + b[i], a[i], arg, e->stream);
         }
+        if (e->v.btw_loss && n > 0) {              // (a new record is a Gaussian factor until it is given a loss)
+            vf::BtwLossArg la{};
+            la.n = n;
+            for (int i = 0; i < n; i++) la.g[i] = (long)window * M + b[i];
+            vf::launch_put_between_loss(e->v, la, e->stream);
+        }
         HIPCHK(hipGetLastError());
         return VF_OK;
     }
@@ -159,6 +165,7 @@ int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, con
         vf::launch_scatter(e->stage, e->v.btw_in, g0, cnt, vf::BTW_IN, e->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(e->v.btw_a + g0, a + i, cnt * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        if ((rc = e->reset_loss(g0, cnt))) return rc;
         HIPCHK(hipStreamSynchronize(e->stream));
         i = j;
     }
@@ -252,6 +259,7 @@ int vf_engine_clear_between(vf_engine* e, int window, int k0, int n) {
     if (rc) return rc;
     if (n == 0) return VF_OK;
     HIPCHK(hipMemsetAsync(e->v.btw_a + (long)window * e->v.M + k0, 0xff, n * sizeof(int), e->stream));
+    if ((rc = e->reset_loss((long)window * e->v.M + k0, n))) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return VF_OK;
 }
@@ -367,6 +375,7 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
     vf::ImuCov c{p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int};
     vf::launch_ingest_tail(e->v, (const int*)d, (const double*)(d + off_b + a_b + rec_b), (const int*)(d + off_b),
                            (const double*)(d + off_b + a_b), c, e->in_status, e->stream);
+    if (e->v.btw_loss) vf::launch_reset_tail_loss(e->v, e->stream);     // (the slot a record has just been written to)
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->in_ev[2], e->stream));
     e->in_pending = true;

@@ -309,6 +309,17 @@ int vf_engine_compact(vf_engine* e, int shift) {
         vf::launch_shift_btw_a(v.btw_a, v.G, v.M, shift, e->stream);
         HIPCHK(hipGetLastError());
     }
+    // ... and their losses with them; the slots freed at the end hold none
+    for (int w = 0; w < v.B && v.btw_loss; w++) {
+        int* li = v.btw_loss + (size_t)w * v.M;
+        double* lk = v.btw_loss_k + (size_t)w * v.M;
+        HIPCHK(hipMemcpyAsync(e->stage, li + shift, keepk * sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(li, e->stage, keepk * sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(li + keepk, 0, (size_t)shift * sizeof(int), e->stream));
+        HIPCHK(hipMemcpyAsync(e->stage, lk + shift, keepk * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(lk, e->stage, keepk * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(lk + keepk, 0, (size_t)shift * sizeof(double), e->stream));
+    }
     // window ranges and prior keys
     std::vector<int> lo(v.B), hi(v.B), pk(v.B);
     HIPCHK(hipMemcpyAsync(pk.data(), v.prior_k, v.B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -419,6 +430,12 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
                 return rc;
             }
         n->recount_far();
+    }
+    if (e->v.btw_loss) {          // the losses of the band between factors, with their slots
+        if ((rc = n->ensure_loss())) { vf_engine_destroy(n); return rc; }
+        cp2(n->v.btw_loss, e->v.btw_loss, sizeof(int));
+        cp2(n->v.btw_loss_k, e->v.btw_loss_k, sizeof(double));
+        if ((rc = copied())) return rc;
     }
     // what the solver remembers from solve to solve: the non-monotone rule's damping / excursion state (a whole-history handle
     // grows again and again: each solve after a grow would otherwise restart from lambda0)

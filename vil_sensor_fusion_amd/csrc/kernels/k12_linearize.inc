@@ -303,12 +303,58 @@ __device__ __forceinline__ void between_core(const View& v, const int b, const l
     between_values(qa, ta, qb, tb, Rec{in, istride}, sink);
 }
 
-template <bool SH>
+// Robust loss on a band between factor (View::btw_loss; DESIGN.md "4i"): the factor in its square-root form, an ordinary least-squares
+// factor with residual r^ = alpha(s) r, s = |r|, and Jacobian J^ = (alpha I + gamma r r^T) J (vf_robust.hpp), written where r and J
+// are written -- 0.5 |r^|^2 = rho(s) and J^^T r^ = (rho' / s) J^T r, so nothing that reads btw_out knows about losses.
+// It is applied BEHIND between_core, to the 78 words the lane has just stored, and not in a sink of between_values: a sink that
+// keeps r and a column in registers changes how the compiler contracts the multiply-adds in front of it (measured: the last
+// residual row and the translation rows of J of a slot WITHOUT a loss came out an ulp off the kernels that know no losses).  This
+// way the words of a slot without a loss, and of a Huber inlier (s <= k, s = k included), are those kernels' code and bits, and
+// only a factor the loss changes pays the second pass: r (6), then column by column the 6 + 6 entries of Ja / Jb and their dots
+// r^T Ja[:, c], r^T Jb[:, c] -- read back from the lane's own words (same lane, same addresses: program order).
+__device__ __forceinline__ void robustify_between(double* out, const int loss, const double k) {
+    asm volatile("" ::: "memory");            // (the words are read back, not kept in 78 registers across between_core)
+    double rr[6];
+    double s2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) { rr[i] = out[(size_t)i * TILE]; s2 = fma(rr[i], rr[i], s2); }
+    const double s = sqrt(s2);
+    if (loss == LOSS_HUBER && s <= k) return;       // (a NaN norm is no inlier: alpha is NaN and so is every word below)
+    const double alpha = robust_alpha(loss, s, k), gamma = robust_gamma(loss, s, k);
+#pragma unroll
+    for (int i = 0; i < 6; i++) __builtin_nontemporal_store(alpha * rr[i], out + (size_t)i * TILE);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        double pa[6], pb[6], da = 0.0, db = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            pa[i] = out[(size_t)(6 + i * 6 + c) * TILE];
+            pb[i] = out[(size_t)(42 + i * 6 + c) * TILE];
+            da = fma(rr[i], pa[i], da);
+            db = fma(rr[i], pb[i], db);
+        }
+        da *= gamma;
+        db *= gamma;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            __builtin_nontemporal_store(fma(da, rr[i], alpha * pa[i]), out + (size_t)(6 + i * 6 + c) * TILE);
+            __builtin_nontemporal_store(fma(db, rr[i], alpha * pb[i]), out + (size_t)(42 + i * 6 + c) * TILE);
+        }
+    }
+}
+
+// RB: the engine holds losses (View::btw_loss is not null; never on a time-sharded engine).  The kernels without them are the
+// RB = false instances, which read neither array: what they were before losses existed.
+template <bool SH, bool RB = false>
 __device__ __forceinline__ void linearize_between_factor(const View& v, int which, const long gk) {
+    static_assert(!(SH && RB), "losses on time-sharded windows are not built");
     if (gk >= v.G) return;
     const int w = (int)(gk / v.M), k = (int)(gk - (long)w * v.M);
     const int lo = v.lo[w], w_hi = v.hi[w], w_sel = v.sel[w], w_done = v.stop_on ? v.done[w] : 0;
     const int a = v.btw_a[gk];                 // (all five requested together: one round trip)
+    int loss = LOSS_NONE;
+    double loss_k = 0.0;
+    if (RB) { loss = v.btw_loss[gk]; loss_k = v.btw_loss_k[gk]; }
     if (k <= lo || k >= w_hi || w_done) return;
     if (v.relin_only && !v.relin[w]) return;
     if (v.inc_on && k < v.inc_k[w]) return;
@@ -318,4 +364,5 @@ __device__ __forceinline__ void linearize_between_factor(const View& v, int whic
     const double* __restrict__ in = v.btw_in + (size_t)(gk >> 6) * BTW_IN * TILE + (gk & 63);
     double* __restrict__ out = v.btw_out + ((size_t)b * (size_t)(v.G >> 6) + (size_t)(gk >> 6)) * BTW_OUT * TILE + (gk & 63);
     between_core<SH>(v, b, (long)w * v.M + a, gk, in, TILE, out, TILE, jac);
+    if (RB && loss != LOSS_NONE) robustify_between(out, loss, loss_k);
 }

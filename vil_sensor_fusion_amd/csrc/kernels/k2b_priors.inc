@@ -98,6 +98,24 @@ __global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_all(View v, in
     else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * K1_BLOCK + (int)threadIdx.x);
 }
 
+// ... and the three K2 launches of an engine that holds losses (View::btw_loss; linearize_between_factor<.., true>): kernels of
+// their own, chosen on the host (launch.inc), so that the ones above stay what they were
+__global__ void __launch_bounds__(256) k_linearize_between_robust(View v, int which) {
+    linearize_between_factor<false, true>(v, which, (long)blockIdx.x * 256 + threadIdx.x);
+}
+__global__ void __launch_bounds__(256) k_linearize_between_prior_robust(View v, int which, int nb_pri) {
+    const int bx = blockIdx.x;
+    if (bx < nb_pri) {
+        if (threadIdx.x < 64) linearize_prior_window(v, which, bx * 64 + (int)threadIdx.x);
+    } else linearize_between_factor<false, true>(v, which, (long)(bx - nb_pri) * 256 + threadIdx.x);
+}
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_all_robust(View v, int which, int nb_imu, int nb_btw) {
+    const int bx = blockIdx.x;
+    if (bx < nb_imu) linearize_imu_factor<false>(v, which, (long)bx * K1_BLOCK + threadIdx.x);
+    else if (bx < nb_imu + nb_btw) linearize_between_factor<false, true>(v, which, (long)(bx - nb_imu) * K1_BLOCK + threadIdx.x);
+    else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * K1_BLOCK + (int)threadIdx.x);
+}
+
 // Warm start of a fixed-lag update (vf_engine_slide directly after a solve): the linearisation of every factor that was
 // in the window is still the one of the current states (an accepted trial's records became current with its states, a
 // rejected one left both alone), so only the factors of the `nslid` appended keyframes and the priors (the marginal prior
@@ -112,6 +130,21 @@ __global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_tail(View v, i
         if (t < nslid) linearize_between_factor<false>(v, 0, (long)w * v.M + v.hi[w] - 1 - t);
     } else {
         const int w = (bx - 2 * v.B) * 64 + t;      // one wave of windows per workgroup
+        if (t < 64) {
+            if (w < v.B) v.fresh[w] = v.fresh[w] ? 1 : 1 + nslid;
+            linearize_prior_window(v, 0, w);
+        }
+    }
+}
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_tail_robust(View v, int nslid) {
+    const int bx = blockIdx.x, t = threadIdx.x;
+    if (bx < v.B) {
+        if (t < nslid) linearize_imu_factor<false>(v, 0, (long)bx * v.M + v.hi[bx] - 1 - t);
+    } else if (bx < 2 * v.B) {
+        const int w = bx - v.B;
+        if (t < nslid) linearize_between_factor<false, true>(v, 0, (long)w * v.M + v.hi[w] - 1 - t);
+    } else {
+        const int w = (bx - 2 * v.B) * 64 + t;
         if (t < 64) {
             if (w < v.B) v.fresh[w] = v.fresh[w] ? 1 : 1 + nslid;
             linearize_prior_window(v, 0, w);

@@ -388,6 +388,29 @@ struct vf_engine : EngineHandle {
     }
     size_t err_bytes() const { return (2 * (size_t)v.G + (size_t)v.B * 2 * x_cap) * sizeof(double) + (size_t)v.B * sizeof(vf::ErrSummary) + sizeof(vf::BatchHealth); }
     std::vector<int> err_lo, err_hi;
+    // robust losses of the band between factors (engine/engine_robust.inc; View::btw_loss, btw_loss_k): [G] ids and [G] parameters,
+    // made by the first vf_engine_set_between_loss that sets a loss other than VF_LOSS_NONE.  From then on the K2 launches are the
+    // kernels that read them -- another launch sequence, so a captured one is void
+    vf::DeviceBuf<int> loss_id;
+    vf::DeviceBuf<double> loss_k;
+    int ensure_loss() {
+        if (v.btw_loss) return VF_OK;
+        HIPCHK(loss_id.ensure((size_t)v.G * sizeof(int)));
+        HIPCHK(loss_k.ensure((size_t)v.G * sizeof(double)));
+        HIPCHK(hipMemsetAsync(loss_id, 0, (size_t)v.G * sizeof(int), stream));
+        HIPCHK(hipMemsetAsync(loss_k, 0, (size_t)v.G * sizeof(double), stream));
+        v.btw_loss = loss_id;
+        v.btw_loss_k = loss_k;
+        epoch++;
+        return VF_OK;
+    }
+    // NONE for the slots [g0, g0 + n) whose record a staging call has just written or cleared (nothing on an engine without losses)
+    int reset_loss(long g0, long n) {
+        if (!v.btw_loss || n <= 0) return VF_OK;
+        HIPCHK(hipMemsetAsync(v.btw_loss + g0, 0, (size_t)n * sizeof(int), stream));
+        HIPCHK(hipMemsetAsync(v.btw_loss_k + g0, 0, (size_t)n * sizeof(double), stream));
+        return VF_OK;
+    }
     // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
     void swap_arrays(vf_engine& o) { std::swap(*this, o), std::swap<EngineHandle>(*this, o); }
 };
@@ -416,4 +439,5 @@ extern "C" {
 #include "engine/engine_propagate.inc"
 #include "engine/engine_gate.inc"
 #include "engine/engine_errors.inc"
+#include "engine/engine_robust.inc"
 }  // extern "C"

@@ -41,6 +41,7 @@ struct SolveTake {
     LateFactor late_far, late_band;         // dropped: a far factor that was late when the solve began; a band factor (its end key is to be unmarked)
     bool fars_changed = false;              // `fars` is no longer what the handle's list holds
     bool requeue = false;                   // the solve failed before the optimisation: everything goes back
+    vf_between_loss_setter set_loss = nullptr;   // the handle's set_between_loss as it stood at the take (read under graph_mutex, where it is written)
 };
 
 struct Lap {   // VF_SOLVE_TIMING: "[vf_solve] <label> <us>" on stderr behind every step of a solve (tools/gm_lap_summary.py reads the labels)
@@ -377,16 +378,27 @@ int vf_between_record_(const double q[4], const double t[3], const double cov[36
 }
 
 int vf_add_between(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36]) {
+    return vf_add_between_(g, prev, cur, q, t, cov, VF_LOSS_NONE, 0.0, nullptr);
+}
+// ... with a robust loss (vf_add_between_robust, vf_graph_robust.cpp, which has checked loss and loss_k)
+int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36], int loss, double loss_k,
+                    vf_between_loss_setter setter) {
     if (!g || !q || !t || !cov) return gerr(VF_ERR_INVALID, "null argument");
     PendingBetween b;
     b.a = prev;
     b.b = cur;
+    b.loss = loss;
+    b.loss_k = loss == VF_LOSS_NONE ? 0.0 : loss_k;
     if (int rc = vf_between_record_(q, t, cov, b.rec)) return rc;
     std::lock_guard<std::mutex> lk(g->graph_mutex);  // GraphManager.cpp:85
     if (prev >= cur || cur > g->current_key) return gerr(VF_ERR_BAD_KEY, "between factor keys (%llu, %llu) not reserved in order", (unsigned long long)prev, (unsigned long long)cur);
     bool band = cur - prev <= VF_MAX_BANDWIDTH && !g->has_band_end(cur);
     for (const auto& s : g->staged_between)
         if (s.b == cur) band = false;
+    if (!band && loss != VF_LOSS_NONE)
+        return gerr(VF_ERR_INVALID, "between factor (%llu, %llu) spans %llu keyframes or shares its end key: it would be a far factor, and far factors take no robust loss",
+                    (unsigned long long)prev, (unsigned long long)cur, (unsigned long long)(cur - prev));
+    if (setter) g->set_between_loss = setter;
     if (band) {
         g->staged_between.push_back(b);
     } else {
@@ -405,6 +417,8 @@ int vf_add_between(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], 
     memcpy(sf.q, b.rec, sizeof(sf.q));
     memcpy(sf.t, t, sizeof(sf.t));
     memcpy(sf.cov, cov, sizeof(sf.cov));
+    sf.loss = b.loss;
+    sf.loss_k = b.loss_k;
     g->staged_log.push_back(sf);
     return VF_OK;
 }
@@ -510,6 +524,7 @@ static void take(vf_graph* g, SolveTake& t) {
     std::lock_guard<std::mutex> lk(g->graph_mutex);
     t.imus.swap(g->imu_queue);
     t.betweens.swap(g->staged_between);
+    t.set_loss = g->set_between_loss;
     for (const auto& bt : t.betweens) g->set_band_end(bt.b, 1);   // these keys now carry their band factor (a second one goes to the far list)
     // (keys below the window can never be named again by a factor that is accepted: their marks are let go)
     while (!g->band_end.empty() && g->band_base < oldest_key(g)) { g->band_end.pop_front(); g->band_base++; }
@@ -657,6 +672,16 @@ static int stage_band(vf_graph* g, SolveTake& t, Lap& lap) {
     }
     if (int rc = vf_engine_set_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
     lap("set_between");
+    // the losses behind the records (the engine resets the slots it writes): only when one of these factors has a loss
+    bool robust = false;
+    for (const auto& f : betweens) robust = robust || f.loss != VF_LOSS_NONE;
+    if (robust && t.set_loss) {
+        std::vector<int32_t> loss(betweens.size());
+        std::vector<double> k(betweens.size());
+        for (size_t i = 0; i < order.size(); i++) { loss[i] = betweens[order[i]].loss; k[i] = betweens[order[i]].loss_k; }
+        if (int rc = t.set_loss(g->eng, 0, (int)b.size(), b.data(), loss.data(), k.data())) return rc;
+        lap("set_between_loss");
+    }
     return VF_OK;
 }
 // the engine has marginalised the far factors whose older key left together with that key (they are linear rows of its own now):

@@ -1,5 +1,5 @@
 // vf_graph_handle.hpp -- the GraphManager handle (struct vf_graph) as the translation units behind its C ABI see it: vf_graph.cpp,
-// which owns the bookkeeping, and vf_graph_scores.cpp and vf_graph_errors.cpp, whose entry points need engine calls that vf_graph.cpp must not reference
+// which owns the bookkeeping, and vf_graph_scores.cpp, vf_graph_errors.cpp and vf_graph_robust.cpp, whose entry points need engine calls that vf_graph.cpp must not reference
 // (the host tests link vf_graph.cpp against a stand-in engine that has only what vf_graph.cpp calls).  Internal: not installed,
 // not part of include/vilfusion.h.  Host code, no HIP.
 #pragma once
@@ -21,9 +21,11 @@ struct PendingImu {            // one queued CombinedImuFactor (GraphManager::_i
     std::vector<double> record; // non-empty: a ready-made factor handed in through vf_add_imu_factor (addFactor), 190 doubles
     bool staged = false;        // preintegrated on the device already, at reserveNode time (where the reference preintegrates: GraphManager.cpp:59-66)
 };
-struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device = false; };
-// a between factor as the caller handed it in: what GraphManager::graph() shows until the next solve (vf_graph_get_staged)
-struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; };
+// (loss, loss_k: the robust loss of a band factor, vf_add_between_robust; a Gaussian factor by default)
+struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device = false; int loss = VF_LOSS_NONE; double loss_k = 0.0; };
+// a between factor as the caller handed it in: what GraphManager::graph() shows until the next solve (vf_graph_get_staged, vf_graph_get_staged_loss)
+struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; int loss = VF_LOSS_NONE; double loss_k = 0.0; };
+typedef int (*vf_between_loss_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*);   // vf_engine_set_between_loss
 
 struct vf_graph {
     vf_engine* eng = nullptr;
@@ -35,6 +37,10 @@ struct vf_graph {
     std::deque<ImuSample> buffer;
     std::deque<PendingImu> imu_queue;
     std::vector<PendingBetween> staged_between;
+    // how the solve's staging step hands the losses of band factors to the engine, behind their records: null until the first robust
+    // factor is added (vf_graph_robust.cpp hands it to vf_add_between_, which writes it under graph_mutex; a solve reads it under graph_mutex too,
+    // in its take, with the factors; vf_graph.cpp never names the engine call), and nothing is called
+    vf_between_loss_setter set_between_loss = nullptr;
     // Between factors the band cannot hold -- wider than VF_MAX_BANDWIDTH keyframes, or a second one ending at a key (loop
     // closures; iSAM2 takes any pair of keys, GraphManager.cpp:83-88): handed to the engine as "far" factors
     // (vf_engine_set_extra_between) at every solve.  When the older key of one leaves the fixed-lag window the engine
@@ -75,6 +81,9 @@ struct vf_graph {
     bool err_valid = false;     // the engine holds the per-factor errors of the window as the last solve left it (vf_graph_errors.cpp)
 };
 
+// vf_add_between with a loss (vf_graph.cpp): VF_LOSS_NONE is vf_add_between itself; any other loss is for band factors only
+extern "C" int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36], int loss, double loss_k,
+                               vf_between_loss_setter setter);
 extern "C" int vf_between_record_(const double q[4], const double t[3], const double cov[36], double rec[VF_BTW_RECORD]);   // vf_graph.cpp
 
 // key -> keyframe slot of the handle's one window, and the oldest key still in it

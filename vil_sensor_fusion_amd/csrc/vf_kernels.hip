@@ -33,6 +33,7 @@
 #include "vf_launch_view.hpp"
 #include "vf_jstream.hpp"
 #include "vf_math.hpp"
+#include "vf_robust.hpp"
 #include <cstdlib>
 
 namespace vf {

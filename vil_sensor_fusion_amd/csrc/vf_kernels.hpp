@@ -148,6 +148,8 @@ struct View {
     int sh_r, sh_G;
     int sh_all_jac;     // != 0: a time-sharded rank writes the Jacobian of EVERY factor, not only of those that feed its rows (the
                         // refined solve applies J as an operator on whole increments, replicated on every rank)
+    int nm_W;           // non-monotone LM, see x_best below (the word sits here, and x_max below, so that the argument block is 712 bytes with
+                        // btw_loss / btw_loss_k in it as it was without them: two words that were padding)
     double* Vp;         // [G][15][32]         spikes: L^-1 (coupling of the chunk interior to its left separator)
     // the three below point into ONE buffer [P][B][SEPK] (at offsets 0, SEPM, 2 SEPM of a slot): element (c, w) of each sits
     // ((size_t)c * B + w) * SEPK further on
@@ -175,7 +177,9 @@ struct View {
     // provisionally (an "excursion"); the first one saves the point it left (x_best, ref_cost).  A later trial whose cost is
     // below ref_cost ends the excursion with everything accepted; the nm_W + 1-th that is not restores x_best (relin[w] = 1:
     // its factors are linearised again by the conditional launch that follows k_decide).
-    int nm_W;
+    // Robust loss of the band between factor ending at each slot (vf_engine_set_between_loss): LOSS_* and its parameter k.  Both null on
+    // an engine that was never given a loss: the K2 kernels of such an engine read neither (the launchers choose, launch.inc)
+    int* btw_loss;      // [G]
     double* x_best;     // [16][G]
     double* ref_cost;   // [B]
     int* prov;          // [B] provisional trials since the reference point (0: the current point is the reference)
@@ -183,6 +187,7 @@ struct View {
     int* relin;         // [B] the current buffer was restored: linearise it again
     int* carry;         // [B] the next solve keeps this window's lambda (k_reset_lambda): set for every window at the end of a solve that runs excursions
     int relin_only;     // the linearisation kernels skip windows whose relin flag is clear
+    int x_max;          // far between factors (below): slots per window, 0 until vf_engine_set_extra_between is first called
     double gauge_floor; // k_marginalize: eigenvalues of the marginal prior's information about the window's global translation and yaw
                         // that have decayed below this are lifted back to it (vf_engine_opts.gauge_floor; 0 = off)
     int w_first;        // K3 only: the first window of its grid (launch_assemble_window: H and g of ONE window on demand)
@@ -213,7 +218,7 @@ struct View {
     unsigned* place;    // [PLACE_CELLS] per-CU claims of the two-wave sweep's launch (which SIMDs have their eliminator): k_band_forward_asm2
     // "far" between factors: BetweenFactor<Pose3> on any pair of keyframes of a window (wider than the band, or a second factor
     // on an end key), at most x_max per window; kept out of the banded H and solved as a low-rank correction
-    int x_max;          // 0 until vf_engine_set_extra_between is first called
+    double* btw_loss_k; // [G]  (see btw_loss)
     int* x_a;           // [B][x_max] window-local slots of the two keyframes, -1 = empty
     int* x_b;
     double* x_in;       // [B][x_max][28]
@@ -251,6 +256,9 @@ struct View {
     double* ck;         // [G / CK][CK_SZ] checkpoints (slot k -> entry k / CK of its window, written by every sweep that passes it)
     double wildfire;    // back substitution: an increment that changes by at most this in every component counts as unchanged
 };
+// the kernel argument block: a member added here moves every kernel's argument loads (profiles/robust_resource_usage.txt was taken at
+// this size; btw_loss / btw_loss_k sit in what were two padding words, which is why nm_W and x_max stand where they do)
+static_assert(sizeof(View) == 712, "View: the kernel argument block");
 __host__ __device__ inline int xl_ld(const View& v) { return 27 + 6 * v.x_max; }   // row stride of View::xl_U
 // Do the dense far systems (the Woodbury combine, the marginals' C, the joint marginalisation) take their device-memory form?  The
 // form follows the slots IN USE, not the engine's capacity: an engine made for 32 far factors that holds eight or fewer takes the
@@ -409,6 +417,9 @@ struct SolveResult { double state[16]; double cost; int n_acc, n_rej, n_fail, st
 void launch_set_range(const View& v, int window, int lo, int hi, hipStream_t s);
 void launch_bump_lo(const View& v, hipStream_t s);
 void launch_put_between(const View& v, long g, int a, const BtwArg& rec, hipStream_t s);
+struct BtwLossArg { long g[4]; double k[4]; int loss[4]; int n; };      // up to four slots' losses by value (View::btw_loss)
+void launch_put_between_loss(const View& v, const BtwLossArg& a, hipStream_t s);
+void launch_reset_tail_loss(const View& v, hipStream_t s);      // NONE for the slot behind every window's end (vf_engine_ingest_tail)
 void launch_read_result(const View& v, int window, int slot, int which, int* sticky, SolveResult* out, hipStream_t s);
 void launch_marginalize(const View& v, int far_slots_in_use, int* status, hipStream_t s);
 constexpr int MARG_STASH_DOUBLES = 729 + 27 + 48 + 4;     // per window: what k_marginalize leaves in a stash (information, gradient, linearisation states)

@@ -18,7 +18,8 @@
 // COPY made by one of the functions below, each of which writes the words it owns and no other -- none resets what it does not own:
 // the invariant makes that unnecessary, and they compose (vf_engine's solve() launches 2 o 4 o 9).  What the engine does assign in
 // its own View is engine state, not launch words: creation and vf_engine_grow, vf_engine_set_convergence (stop_on and the
-// tolerances), attach_far / ensure_far, ensure_excursion, vf_engine_set_shard, sh_all_jac in linearize(), nm_W in decide().
+// tolerances), attach_far / ensure_far, ensure_excursion, ensure_loss (btw_loss / btw_loss_k, the robust losses' arrays: the launchers
+// choose the K2 kernels by them), vf_engine_set_shard, sh_all_jac in linearize(), nm_W in decide().
 #pragma once
 #include "vf_kernels.hpp"
 

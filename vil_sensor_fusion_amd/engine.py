@@ -178,6 +178,24 @@ class Engine:
     def clear_between(self, window, k0, n):
         check(self._l.vf_engine_clear_between(self._h, window, k0, n))
 
+    def set_between_loss(self, window, b, loss, k=None):
+        """robust loss of the band between factors ending at slots b (vf_engine_set_between_loss; call it AFTER the records are
+        staged): loss by name or id (robust.py), one for all slots or one each; k likewise (None: robust.DEFAULT_K)"""
+        from . import robust
+        b = np.atleast_1d(np.ascontiguousarray(b, dtype=np.int32))
+        ids = [robust.loss_id(x) for x in (loss if isinstance(loss, (list, tuple, np.ndarray)) else [loss] * b.size)]
+        ks = [robust.DEFAULT_K.get(i, 0.0) for i in ids] if k is None else np.broadcast_to(np.asarray(k, dtype=np.float64), (b.size,))
+        li = np.ascontiguousarray(ids, dtype=np.int32)
+        kk = np.ascontiguousarray(ks, dtype=np.float64)
+        assert li.size == b.size == kk.size
+        check(self._l.vf_engine_set_between_loss(self._h, window, b.size, _i(b), _i(li), _d(kk)))
+
+    def get_between_loss(self, window, k0, n):
+        """(loss ids (n,), k (n,)) of keyframe slots k0 .. k0+n-1; none and 0 on an engine that was never given a loss"""
+        li, kk = np.zeros(n, dtype=np.int32), np.zeros(n)
+        check(self._l.vf_engine_get_between_loss(self._h, window, k0, n, _i(li), _d(kk)))
+        return li, kk
+
     def set_prior(self, window, k, rec):
         r = np.ascontiguousarray(rec, dtype=np.float64).reshape(PRIOR_RECORD)
         check(self._l.vf_engine_set_prior(self._h, window, k, _d(r)))

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import robust as robust_losses
 from ._lib import check
 
 # gtsam_fusion/config/carla/fusion_params.yaml:22-27
@@ -65,6 +66,7 @@ class GraphManager:
         # downdate) instead of refusing while one is alive
         o.far_covariance = int(bool(far_covariance))
         self._h = C.c_void_p()
+        self._robust = {}          # end key -> (loss id, k) of the robust band factors added (between_weights)
         check(self._l.vf_create(C.byref(p), C.byref(o), C.byref(self._h)))
         self._cbs = []
 
@@ -101,12 +103,35 @@ class GraphManager:
         check(self._l.vf_most_recent_pose_time(self._h, C.byref(t), C.byref(k)))
         return t.value, k.value
 
-    def addBetweenFactor(self, previousKey, currentKey, betweenPose, noiseCovariance):
+    def addBetweenFactor(self, previousKey, currentKey, betweenPose, noiseCovariance, robust=None):
+        """robust: None (noiseModel::Gaussian::Covariance, as the reference's sensor managers build it), or a loss over that
+        Gaussian (noiseModel::Robust) as ("huber", 1.345) / ("cauchy", k) / ("geman_mcclure", k) -- band factors only
+        (vf_add_between_robust; robust.py has the names and the losses' arithmetic)"""
         q = np.ascontiguousarray(betweenPose[0], dtype=np.float64)
         t = np.ascontiguousarray(betweenPose[1], dtype=np.float64)
         cov = np.ascontiguousarray(noiseCovariance, dtype=np.float64).reshape(6, 6)
-        check(self._l.vf_add_between(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q),
-                                     _d(t), _d(cov)))
+        loss, k = robust_losses.parse(robust)
+        if loss == robust_losses.NONE:
+            check(self._l.vf_add_between(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q),
+                                         _d(t), _d(cov)))
+            return
+        check(self._l.vf_add_between_robust(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q), _d(t), _d(cov), C.c_int(loss), C.c_double(k)))
+        self._robust[int(currentKey)] = (loss, k)
+
+    def between_weights(self, key0=None, n=None):
+        """how far the last solve's optimum has down-weighted the band between factor ending at each of the keys key0 .. key0+n-1
+        (defaults: the window, as factor_errors): rho'/s, the weight GTSAM's reweighting would have given it -- 1 for a Gaussian
+        factor and for an inlier, towards 0 for an outlier, nan where no factor ends.  From factor_errors alone
+        (robust.weight_from_error): nothing else is read from the device."""
+        key0, n = self._window_keys(key0, n)
+        _, eb, _ = self.factor_errors(key0, n)
+        self._robust = {k: v for k, v in self._robust.items() if k >= key0}
+        out = np.full(n, np.nan)
+        for i in range(n):
+            if eb[i] >= 0.0:
+                loss, k = self._robust.get(key0 + i, (robust_losses.NONE, 0.0))
+                out[i] = robust_losses.weight_from_error(loss, k, eb[i])
+        return out
 
     def addFactor(self, key, record190):
         """GraphManager::addFactor(const CombinedImuFactor&): queue a ready-made preintegrated factor ending at `key`
@@ -258,7 +283,7 @@ class GraphManager:
 
     def graph(self):
         """GraphManager::graph() (GraphManager.cpp:46-49): the staged factors as a list of dicts -- kind ("prior_pose" |
-        "prior_velocity" | "prior_bias" | "between"), keys, measured (q_wxyz, t), covariance (6 x 6)."""
+        "prior_velocity" | "prior_bias" | "between"), keys, measured (q_wxyz, t), covariance (6 x 6), robust (None, or (loss name, k): noiseModel::Robust)."""
         n = self.graphSize()
         names = ("prior_pose", "prior_velocity", "prior_bias", "between")
         out = []
@@ -266,7 +291,10 @@ class GraphManager:
             kind, k1, k2 = C.c_int(), C.c_uint64(), C.c_uint64()
             q, t, cov = np.zeros(4), np.zeros(3), np.zeros((6, 6))
             check(self._l.vf_graph_get_staged(self._h, i, C.byref(kind), C.byref(k1), C.byref(k2), _d(q), _d(t), _d(cov)))
-            out.append(dict(kind=names[kind.value], keys=(k1.value, k2.value), measured=(q, t), covariance=cov))
+            loss, k = C.c_int(), C.c_double()
+            check(self._l.vf_graph_get_staged_loss(self._h, i, C.byref(loss), C.byref(k)))
+            out.append(dict(kind=names[kind.value], keys=(k1.value, k2.value), measured=(q, t), covariance=cov,
+                            robust=None if loss.value == robust_losses.NONE else (robust_losses.NAMES[loss.value], k.value)))
         return out
 
     def incrementalInfo(self):

@@ -19,6 +19,9 @@ covariance, as nav_msgs/Odometry on ~odometry_imu -- GraphManager.predict; ~odom
 sensors/<name>/innovation_gate_chi2 (absent by default: no gate; a chi-square threshold, 6 degrees of freedom -- 16.81 at 99 %,
 22.46 at 99.9 % -- on the innovation of every odometry increment of that sensor before it becomes a factor,
 sensor_manager.SensorManager.innovation_gate).
+sensors/<name>/robust_loss and robust_k (absent by default: Gaussian factors, as the reference; "huber" / "cauchy" / "geman_mcclure" and
+the loss's parameter in standard deviations of the whitened residual, default robust.DEFAULT_K -- noiseModel::Robust over the
+sensor's Gaussian, sensor_manager.SensorManager.robust; with innovation_gate_chi2 the gate decides first).
 sensors/<name>/odom_covariance_order ("reference" by default: the message's twist covariance is copied as the reference copies
 it; "ros": it is read as (x, y, z, rx, ry, rz) and permuted to the factor's [rot, trans] -- what a covariance
 remapped by the odometry filter's ~filter/mode = deweight needs to mean what it says; use_odom_covariance only).
@@ -94,7 +97,9 @@ class FusionNode:
                                0.0 if use_cov else float(cfg["covariance_angular"]),
                                float(cfg.get("max_time_skip", float("inf"))), reference_compat=compat, noise_order_compat=noise_compat,
                                innovation_gate=cfg.get("innovation_gate_chi2"),
-                               odom_covariance_order=cfg.get("odom_covariance_order", "reference"))
+                               odom_covariance_order=cfg.get("odom_covariance_order", "reference"),
+                               robust=None if not cfg.get("robust_loss") else
+                               ((cfg["robust_loss"], float(cfg["robust_k"])) if "robust_k" in cfg else str(cfg["robust_loss"])))
             self.sensor_managers[name] = sm
             msg_type = msgs.PointCloud2 if kind == "PointCloud2" else msgs.Image
             self.subs.append(rospy.Subscriber(cfg["sensor_topic"], msg_type, queue_size=1,                    # SensorManagerRos.h:59

@@ -55,7 +55,7 @@ class Odometry:
 class SensorManager:
     def __init__(self, graph_manager, optimize_after_odom, use_odom_covariance=False,
                  covariance_linear=0.1, covariance_angular=0.1, max_time_skip=0.1, reference_compat=True,
-                 noise_order_compat=True, innovation_gate=None, odom_covariance_order="reference"):
+                 noise_order_compat=True, innovation_gate=None, odom_covariance_order="reference", robust=None):
         self.gm = graph_manager
         self.optimize_after_odom = optimize_after_odom
         self.use_odom_covariance = use_odom_covariance
@@ -91,6 +91,11 @@ class SensorManager:
         self.innovation_gate = None if innovation_gate is None else float(innovation_gate)
         self.gated = deque(maxlen=keep)
         self.ungated = 0
+        # Robust loss on this sensor's odometry factors (GraphManager.addBetweenFactor(robust=); robust.py): None (the default, the
+        # reference's Gaussian factors), or ("huber", 1.345) and the like.  It combines with the gate, which decides first: an
+        # increment the gate rejects never becomes a factor; one that passes, or that the gate could not test, gets the loss.
+        from . import robust as robust_losses
+        self.robust = None if robust_losses.parse(robust)[0] == robust_losses.NONE else robust_losses.parse(robust)
 
     # SensorManagerRos.h:91-103
     def sensorCallback(self, stamp):
@@ -118,6 +123,16 @@ class SensorManager:
         message (:41-45 warns and carries on the same way)."""
         from ._lib import VilFusionError
         try:
+            if self.robust is not None:
+                try:
+                    self.gm.addBetweenFactor(a, b, pose, cov, robust=self.robust)
+                    return True
+                except VilFusionError as exc:
+                    # VF_ERR_INVALID with this message: the band cannot hold the pair, and far factors take no loss.  (Any other
+                    # VF_ERR_INVALID -- a rotation that is no quaternion, ... -- is the caller's to see, as without a loss.)
+                    if exc.code != -1 or "far factors take no robust loss" not in str(exc):
+                        raise
+                    self.warnings.append(f"between factor ({a}, {b}) added without its robust loss: {exc}")
             self.gm.addBetweenFactor(a, b, pose, cov)
             return True
         except VilFusionError as exc:
