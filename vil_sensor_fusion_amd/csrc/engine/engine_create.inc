@@ -146,8 +146,8 @@ static int create_engine(const vf_engine_opts* o_in, const vf_engine_tuning* t_i
     }
     if (on_stream) { e->stream = given; e->own_stream = false; }
     else HIPCHK(hipStreamCreate(&e->stream));
-    HIPCHK(hipEventCreate(&e->ev0));
-    HIPCHK(hipEventCreate(&e->ev1));
+    HIPCHK(e->ev0.ensure());
+    HIPCHK(e->ev1.ensure());
     const size_t G = (size_t)v.G, tiles = G / 64;
     int rc = VF_OK;
     {
@@ -259,15 +259,8 @@ void vf_engine_destroy(vf_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     e->drop_graph();
     for (void* p : e->allocs) (void)hipFree(p);
-    for (auto ev : e->in_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : e->prop_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : e->gate_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->far_columns) { vf_engine_destroy(e->far_columns); e->far_columns = nullptr; }
     if (e->stream2) { (void)hipStreamSynchronize(e->stream2); (void)hipStreamDestroy(e->stream2); }
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream && e->own_stream) (void)hipStreamDestroy(e->stream);
-    delete e;      // (frees what owns itself, vf_device_buf.hpp, while entry_ still holds the engine's device current)
+    delete e;      // (frees what owns itself, buffers and events, vf_device_buf.hpp, while entry_ still holds the engine's device current)
 }

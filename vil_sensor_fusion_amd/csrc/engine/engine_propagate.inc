@@ -10,46 +10,24 @@ int vf_engine_propagate_tail(vf_engine* e, const int32_t* step_off, const double
     Entry entry_(e, Entry::reads, Entry::leaves_result);
     if (!e || !step_off || !p) return fail(VF_ERR_INVALID, "null argument");
     if (flags & ~(unsigned)(VF_PROPAGATE_COVARIANCE | VF_PROPAGATE_FROM_ESTIMATE)) return fail(VF_ERR_INVALID, "vf_engine_propagate_tail: unknown flags 0x%x", flags);
-    if (int rc = not_sharded(e, "vf_engine_propagate_tail")) return rc;
     const bool cov = (flags & VF_PROPAGATE_COVARIANCE) != 0;
     const int B = e->v.B;
-    const int total = step_off[B];
-    if (step_off[0] != 0 || (total > 0 && !steps)) return fail(VF_ERR_INVALID, "bad step offsets");
-    if (cov && !e->mem.covariances_valid())
-        return fail(VF_ERR_INVALID, "vf_engine_propagate_tail: VF_PROPAGATE_COVARIANCE needs the marginal covariances of the last keyframes: call vf_engine_marginals_ex first");
-    for (int w = 0; w < B; w++) {
-        if (step_off[w + 1] < step_off[w]) return fail(VF_ERR_INVALID, "bad step offsets (window %d)", w);
-        const int hi = e->h_hi[w], lo = e->h_lo[w];
-        if (hi <= lo) return fail(VF_ERR_BAD_KEY, "window %d is empty", w);
-        if (cov && (hi - 1 < e->sig_lo[w] || hi > e->sig_hi[w]))
-            return fail(VF_ERR_INVALID, "vf_engine_propagate_tail: window %d: the covariances were computed for the keyframes [%d,%d), the last keyframe is %d",
-                        w, e->sig_lo[w], e->sig_hi[w], hi - 1);
-    }
+    if (int rc = check_tail_steps(e, "vf_engine_propagate_tail", step_off, steps, !cov ? nullptr :
+                                  "VF_PROPAGATE_COVARIANCE needs the marginal covariances of the last keyframes: call vf_engine_marginals_ex first")) return rc;
     // one packed block: [offsets B + 1][steps 7 x total]
-    const size_t off_b = ((size_t)(B + 1) * sizeof(int) + 7) & ~(size_t)7, st_b = (size_t)total * 7 * sizeof(double);
-    const size_t bytes = off_b + st_b;
-    if (!e->prop_ev[0])
-        for (auto& ev : e->prop_ev) HIPCHK(hipEventCreate(&ev));
-    if (bytes > e->prop_host.bytes() || bytes > e->prop_dev.bytes()) {
-        if (e->prop_pending) HIPCHK(hipEventSynchronize(e->prop_ev[2]));      // (the copy out of, and the kernel on, the blocks about to go)
-        HIPCHK(e->prop_host.ensure(bytes, vf::twice));
-        HIPCHK(e->prop_dev.ensure(bytes, vf::twice));
-    }
+    vf::Packed blk;
+    const size_t st_b = (size_t)step_off[B] * 7 * sizeof(double), off_at = blk.add((size_t)(B + 1) * sizeof(int)), st_at = blk.add(st_b);
     HIPCHK(e->prop_out.ensure((size_t)B * (16 + 225) * sizeof(double)));
-    if (e->prop_pending) HIPCHK(hipEventSynchronize(e->prop_ev[1]));          // the previous call's copy has left the pinned buffer: long done
-    char* h = e->prop_host;
-    memcpy(h, step_off, (size_t)(B + 1) * sizeof(int));
-    if (total > 0) memcpy(h + off_b, steps, st_b);
-    char* d = e->prop_dev;
-    HIPCHK(hipEventRecord(e->prop_ev[0], e->stream));
-    HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->prop_ev[1], e->stream));
-    vf::ImuCov c{p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int};
-    vf::launch_propagate(e->v, (const int*)d, (const double*)(d + off_b), c, cov ? 1 : 0, (flags & VF_PROPAGATE_FROM_ESTIMATE) ? 1 : 0,
+    char* h = nullptr;
+    HIPCHK(e->prop.open(blk.bytes, &h));
+    memcpy(h + off_at, step_off, (size_t)(B + 1) * sizeof(int));
+    if (st_b > 0) memcpy(h + st_at, steps, st_b);
+    HIPCHK(e->prop.send(blk.bytes, e->stream, true));
+    const char* d = e->prop.device();
+    vf::launch_propagate(e->v, (const int*)(d + off_at), (const double*)(d + st_at), imu_cov(p), cov ? 1 : 0, (flags & VF_PROPAGATE_FROM_ESTIMATE) ? 1 : 0,
                          cov ? e->sig.get() : nullptr, cov ? e->sig_fail() : nullptr, e->prop_out, e->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->prop_ev[2], e->stream));
-    e->prop_pending = true;
+    HIPCHK(e->prop.launched(e->stream));
     e->mem.propagated(cov);
     return VF_OK;
 }
@@ -70,11 +48,6 @@ int vf_engine_read_propagated(vf_engine* e, int window, double* state16, double*
 
 int vf_engine_propagate_status(vf_engine* e, float* h2d_ms, float* kernel_ms) {
     VF_ENTER(e, Entry::reads, Entry::leaves_result);
-    if (h2d_ms) *h2d_ms = 0.f;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (!e->prop_pending) return VF_OK;
-    HIPCHK(hipEventSynchronize(e->prop_ev[2]));
-    if (h2d_ms) HIPCHK(hipEventElapsedTime(h2d_ms, e->prop_ev[0], e->prop_ev[1]));
-    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, e->prop_ev[1], e->prop_ev[2]));
+    HIPCHK(e->prop.timings(h2d_ms, kernel_ms));
     return VF_OK;
 }

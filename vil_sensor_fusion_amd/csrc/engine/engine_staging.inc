@@ -12,6 +12,23 @@ static int not_sharded(vf_engine* e, const char* what) {
                     "include/vilfusion.h \"time-sharded windows\")", what, e->v.sh_r, e->v.sh_G);
     return VF_OK;
 }
+// What vf_engine_propagate_tail and vf_engine_gate_tail (`who`) ask alike: whole windows, offsets from 0 that do not decrease, no empty
+// window and, where the call reads the marginal covariances (cov_needs: how `who` says so), that they are valid and cover the last keyframe
+static int check_tail_steps(vf_engine* e, const char* who, const int32_t* step_off, const double* steps, const char* cov_needs) {
+    if (int rc = not_sharded(e, who)) return rc;
+    const int B = e->v.B;
+    if (step_off[0] != 0 || (step_off[B] > 0 && !steps)) return fail(VF_ERR_INVALID, "bad step offsets");
+    if (cov_needs && !e->mem.covariances_valid()) return fail(VF_ERR_INVALID, "%s: %s", who, cov_needs);
+    for (int w = 0; w < B; w++) {
+        if (step_off[w + 1] < step_off[w]) return fail(VF_ERR_INVALID, "bad step offsets (window %d)", w);
+        const int hi = e->h_hi[w], lo = e->h_lo[w];
+        if (hi <= lo) return fail(VF_ERR_BAD_KEY, "window %d is empty", w);
+        if (cov_needs && (hi - 1 < e->sig_lo[w] || hi > e->sig_hi[w]))
+            return fail(VF_ERR_INVALID, "%s: window %d: the covariances were computed for the keyframes [%d,%d), the last keyframe is %d",
+                        who, w, e->sig_lo[w], e->sig_hi[w], hi - 1);
+    }
+    return VF_OK;
+}
 static int check_window(vf_engine* e, int window) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
     if (window < 0 || window >= e->v.B) return fail(VF_ERR_INVALID, "window %d out of range", window);
@@ -300,21 +317,19 @@ int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_
     if (e->async_base() && k0 >= e->h_hi[window]) {
         // asynchronous staging: the arguments travel through the pinned block of vf_engine_ingest_tail in ONE copy, the status
         // goes into the sticky word (vf_engine_read_result); nothing here waits for the device
-        const size_t steps_b = (size_t)(total > 0 ? total : 1) * 7 * sizeof(double), bias_b = (size_t)n * 6 * sizeof(double);
-        const size_t off_b = ((size_t)(n + 1) * sizeof(int) + 7) & ~(size_t)7, bytes = steps_b + bias_b + off_b;
-        if ((rc = e->ensure_ingest(bytes))) return rc;
-        if (e->in_pending) HIPCHK(hipEventSynchronize(e->in_ev[1]));      // (the previous copy has left the pinned buffer: long done)
-        char* h = e->in_host;
-        if (total > 0) memcpy(h, steps, (size_t)total * 7 * sizeof(double));
-        memcpy(h + steps_b, bhat, bias_b);
-        memcpy(h + steps_b + bias_b, off, (size_t)(n + 1) * sizeof(int));
-        char* d = e->in_dev;
-        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipEventRecord(e->in_ev[1], e->stream));
-        e->in_pending = true;
-        vf::ImuCov c{p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int};
-        vf::launch_preintegrate(e->v, (long)window * e->v.M + k0, n, (const int*)(d + steps_b + bias_b), (const double*)d, (const double*)(d + steps_b), c,
-                                e->sticky_dev, e->stream);
+        vf::Packed blk;       // [steps 7 x total][bias 6 x n][offsets n + 1]
+        const size_t steps_at = blk.add((size_t)(total > 0 ? total : 1) * 7 * sizeof(double)), bias_at = blk.add((size_t)n * 6 * sizeof(double));
+        const size_t off_at = blk.add((size_t)(n + 1) * sizeof(int));
+        if ((rc = e->ensure_ingest())) return rc;
+        char* h = nullptr;
+        HIPCHK(e->ingest.open(blk.bytes, &h));
+        if (total > 0) memcpy(h + steps_at, steps, (size_t)total * 7 * sizeof(double));
+        memcpy(h + bias_at, bhat, (size_t)n * 6 * sizeof(double));
+        memcpy(h + off_at, off, (size_t)(n + 1) * sizeof(int));
+        HIPCHK(e->ingest.send(blk.bytes, e->stream, false));
+        const char* d = e->ingest.device();
+        vf::launch_preintegrate(e->v, (long)window * e->v.M + k0, n, (const int*)(d + off_at), (const double*)(d + steps_at), (const double*)(d + bias_at),
+                                imu_cov(p), e->sticky_dev, e->stream);
         HIPCHK(hipGetLastError());
         return VF_OK;
     }
@@ -331,8 +346,7 @@ int vf_engine_preintegrate(vf_engine* e, int window, int k0, int n, const int32_
     if (total > 0) HIPCHK(hipMemcpyAsync(d_steps, steps, (size_t)total * 7 * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(d_bhat, bhat, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), e->stream));
-    vf::ImuCov c{p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int};
-    vf::launch_preintegrate(e->v, (long)window * e->v.M + k0, n, d_off, d_steps, d_bhat, c, d_status, e->stream);
+    vf::launch_preintegrate(e->v, (long)window * e->v.M + k0, n, d_off, d_steps, d_bhat, imu_cov(p), d_status, e->stream);
     HIPCHK(hipGetLastError());
     int status = 0;
     HIPCHK(hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -357,28 +371,23 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
         if (btw_a[w] >= 0 && hi - btw_a[w] > W) return fail(VF_ERR_CAPACITY, "window %d: between factor spans %d keyframes > bandwidth %d", w, hi - btw_a[w], W);
     }
     // one packed block: [offsets B + 1][between sources B][between records 28 B][steps 7 x total]
-    const size_t off_b = ((size_t)(B + 1) * sizeof(int) + 7) & ~(size_t)7, a_b = ((size_t)B * sizeof(int) + 7) & ~(size_t)7;
+    vf::Packed blk;
     const size_t rec_b = (size_t)B * vf::BTW_IN * sizeof(double), st_b = (size_t)total * 7 * sizeof(double);
-    const size_t bytes = off_b + a_b + rec_b + st_b;
-    int rc = e->ensure_ingest(bytes);
-    if (rc) return rc;
-    if (e->in_pending) HIPCHK(hipEventSynchronize(e->in_ev[1]));      // the previous call's copy has left the pinned buffer
-    char* h = e->in_host;
-    memcpy(h, step_off, (size_t)(B + 1) * sizeof(int));
-    memcpy(h + off_b, btw_a, (size_t)B * sizeof(int));
-    memcpy(h + off_b + a_b, btw_rec, rec_b);
-    memcpy(h + off_b + a_b + rec_b, steps, st_b);
-    char* d = e->in_dev;
-    HIPCHK(hipEventRecord(e->in_ev[0], e->stream));
-    HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->in_ev[1], e->stream));
-    vf::ImuCov c{p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int};
-    vf::launch_ingest_tail(e->v, (const int*)d, (const double*)(d + off_b + a_b + rec_b), (const int*)(d + off_b),
-                           (const double*)(d + off_b + a_b), c, e->in_status, e->stream);
+    const size_t off_at = blk.add((size_t)(B + 1) * sizeof(int)), a_at = blk.add((size_t)B * sizeof(int)), rec_at = blk.add(rec_b), st_at = blk.add(st_b);
+    if (int rc = e->ensure_ingest()) return rc;
+    char* h = nullptr;
+    HIPCHK(e->ingest.open(blk.bytes, &h));
+    memcpy(h + off_at, step_off, (size_t)(B + 1) * sizeof(int));
+    memcpy(h + a_at, btw_a, (size_t)B * sizeof(int));
+    memcpy(h + rec_at, btw_rec, rec_b);
+    memcpy(h + st_at, steps, st_b);
+    HIPCHK(e->ingest.send(blk.bytes, e->stream, true));
+    const char* d = e->ingest.device();
+    vf::launch_ingest_tail(e->v, (const int*)(d + off_at), (const double*)(d + st_at), (const int*)(d + a_at),
+                           (const double*)(d + rec_at), imu_cov(p), e->in_status, e->stream);
     if (e->v.btw_loss) vf::launch_reset_tail_loss(e->v, e->stream);     // (the slot a record has just been written to)
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->in_ev[2], e->stream));
-    e->in_pending = true;
+    HIPCHK(e->ingest.launched(e->stream));
     // Nothing inside any window changed (the records sit in slot hi, beyond every window's end): a warm engine stays warm,
     // the vf_engine_slide that follows appends the keyframe and the next solve linearises it (k_linearize_tail).
     return VF_OK;
@@ -386,12 +395,8 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
 
 int vf_engine_ingest_status(vf_engine* e, float* h2d_ms, float* k0_ms) {
     VF_ENTER(e, Entry::reads);
-    if (h2d_ms) *h2d_ms = 0.f;
-    if (k0_ms) *k0_ms = 0.f;
-    if (!e->in_pending) return VF_OK;
-    HIPCHK(hipEventSynchronize(e->in_ev[2]));
-    if (h2d_ms) HIPCHK(hipEventElapsedTime(h2d_ms, e->in_ev[0], e->in_ev[1]));
-    if (k0_ms) HIPCHK(hipEventElapsedTime(k0_ms, e->in_ev[1], e->in_ev[2]));
+    HIPCHK(e->ingest.timings(h2d_ms, k0_ms));
+    if (!e->ingest.outstanding()) return VF_OK;
     int status = 0;
     HIPCHK(hipMemcpy(&status, e->in_status, sizeof(int), hipMemcpyDeviceToHost));
     if (status) {

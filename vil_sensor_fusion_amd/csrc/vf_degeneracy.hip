@@ -1105,13 +1105,26 @@ int derr(int code, const char* fmt, ...) {
         if (_e != hipSuccess) return derr(VF_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-struct Event {       // a timing event that goes with its scope
-    hipEvent_t ev = nullptr;
-    Event() = default;
-    Event(const Event&) = delete;
-    Event& operator=(const Event&) = delete;
-    ~Event() { if (ev) (void)hipEventDestroy(ev); }
-};
+// launch() once and wait; if asked to, the time of one of `reps` further launches
+template <typename Launch>
+int run_timed(int reps, float* kernel_ms, Launch launch) {
+    launch();
+    HIPCHK(hipDeviceSynchronize());
+    if (kernel_ms && reps > 0) {
+        vf::Event e0, e1;
+        HIPCHK(e0.ensure());
+        HIPCHK(e1.ensure());
+        HIPCHK(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; r++) launch();
+        HIPCHK(hipEventRecord(e1, 0));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        *kernel_ms = ms / reps;
+    }
+    HIPCHK(hipGetLastError());
+    return VF_OK;
+}
 
 // The batch entry points: upload `count` matrices (and poses, if given), launch(mats, poses, out) once and wait, time `reps`
 // further launches if asked to, download `rows` rows of `count` values in equal shares to the host arrays of `outs`.
@@ -1126,21 +1139,7 @@ int run_batch(const void* mats, const void* pose, int count, int rows, std::init
         HIPCHK(d_p.ensure(pb));
         HIPCHK(hipMemcpy(d_p, pose, pb, hipMemcpyHostToDevice));
     }
-    launch(d_m.get(), d_p.get(), d_o.get());
-    HIPCHK(hipDeviceSynchronize());
-    if (kernel_ms && reps > 0) {
-        Event e0, e1;
-        HIPCHK(hipEventCreate(&e0.ev));
-        HIPCHK(hipEventCreate(&e1.ev));
-        HIPCHK(hipEventRecord(e0.ev, 0));
-        for (int r = 0; r < reps; r++) launch(d_m.get(), d_p.get(), d_o.get());
-        HIPCHK(hipEventRecord(e1.ev, 0));
-        HIPCHK(hipEventSynchronize(e1.ev));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0.ev, e1.ev));
-        *kernel_ms = ms / reps;
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = run_timed(reps, kernel_ms, [&]() { launch(d_m.get(), d_p.get(), d_o.get()); })) return rc;
     const char* from = (const char*)d_o.get();
     for (void* o : outs) {
         HIPCHK(hipMemcpy(o, from, ob, hipMemcpyDeviceToHost));
@@ -1299,25 +1298,10 @@ int vf_degeneracy_remap_batch(const void* hessians36, int count, int dtype, cons
     HIPCHK(d_w.ensure(n * sizeof(int)));
     HIPCHK(hipMemcpy(d_h, hessians36, n * 36 * esz, hipMemcpyHostToDevice));
     const dim3 grid((count + 63) / 64);
-    auto launch = [&]() {
-        if (dtype == 0) hipLaunchKernelGGL((k_remap_covariance<double>), grid, dim3(64), 0, 0, (const double*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
-        else hipLaunchKernelGGL((k_remap_covariance<float>), grid, dim3(64), 0, 0, (const float*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
-    };
-    launch();
-    HIPCHK(hipDeviceSynchronize());
-    if (kernel_ms && reps > 0) {
-        Event e0, e1;
-        HIPCHK(hipEventCreate(&e0.ev));
-        HIPCHK(hipEventCreate(&e1.ev));
-        HIPCHK(hipEventRecord(e0.ev, 0));
-        for (int r = 0; r < reps; r++) launch();
-        HIPCHK(hipEventRecord(e1.ev, 0));
-        HIPCHK(hipEventSynchronize(e1.ev));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0.ev, e1.ev));
-        *kernel_ms = ms / reps;
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = run_timed(reps, kernel_ms, [&]() {
+            if (dtype == 0) hipLaunchKernelGGL((k_remap_covariance<double>), grid, dim3(64), 0, 0, (const double*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
+            else hipLaunchKernelGGL((k_remap_covariance<float>), grid, dim3(64), 0, 0, (const float*)d_h.get(), count, P, d_c.get(), d_r.get(), d_e.get(), d_w.get());
+        })) return rc;
     HIPCHK(hipMemcpy(cov36, d_c, n * 36 * sizeof(double), hipMemcpyDeviceToHost));
     if (sqrt_info21) HIPCHK(hipMemcpy(sqrt_info21, d_r, n * 21 * sizeof(double), hipMemcpyDeviceToHost));
     if (eig6) HIPCHK(hipMemcpy(eig6, d_e, n * 6 * sizeof(double), hipMemcpyDeviceToHost));

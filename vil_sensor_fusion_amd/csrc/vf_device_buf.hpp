@@ -1,6 +1,6 @@
 // vf_device_buf.hpp -- the owner of a block of memory made after creation: on first use, or grown on demand.  Device memory
 // (DeviceBuf) or pinned host memory (PinnedBuf).  Move-only; the destructor frees.  The four HIP calls below are all it uses
-// (tests/native/device_buf.cpp stubs them and checks it on the CPU).
+// (tests/native/device_buf.cpp stubs them and checks it on the CPU).  Event owns an event likewise (tests/native/upload_channel.cpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -48,5 +48,23 @@ class LateBuf {
 };
 template <typename T> using DeviceBuf = LateBuf<T, false>;
 template <typename T> using PinnedBuf = LateBuf<T, true>;
+
+class Event {
+  public:
+    Event() = default;
+    Event(Event&& o) noexcept : ev_(std::exchange(o.ev_, nullptr)) {}
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) release(), ev_ = std::exchange(o.ev_, nullptr);
+        return *this;
+    }
+    ~Event() { release(); }
+    // The event as it is if there is one (whatever its flags); else one made with `flags`
+    hipError_t ensure(unsigned flags = hipEventDefault) { return ev_ ? hipSuccess : hipEventCreateWithFlags(&ev_, flags); }
+    void release() { if (ev_) (void)hipEventDestroy(std::exchange(ev_, nullptr)); }
+    operator hipEvent_t() const { return ev_; }
+
+  private:
+    hipEvent_t ev_ = nullptr;
+};
 
 }  // namespace vf

@@ -22,6 +22,7 @@
 #include "vf_kernels.hpp"
 #include "vf_launch_view.hpp"
 #include "vf_device_buf.hpp"
+#include "vf_upload_channel.hpp"
 #include "vf_engine_memory.hpp"
 
 namespace {
@@ -42,6 +43,7 @@ int fail(int code, const char* fmt, ...) {
             return fail(VF_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
                         __FILE__, __LINE__);                                                  \
     } while (0)
+vf::ImuCov imu_cov(const vf_imu_params* p) { return {p->acc_cov, p->gyro_cov, p->integration_cov, p->bias_acc_cov, p->bias_omega_cov, p->bias_acc_omega_int}; }
 }  // namespace
 
 struct vf_engine;
@@ -80,7 +82,7 @@ struct EngineHandle {
     // every entry point that is not one of those three).
     bool async_on = false, side_open = false;
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    vf::Event ev_fork, ev_join;
     vf::DeviceBuf<int> sticky_dev;
     vf::PinnedBuf<vf::SolveResult> res_host;
     long far_transported = 0, far_ended = 0, far_absorbed = 0;   // far factors moved on to the next keyframe when theirs left the window /
@@ -112,7 +114,7 @@ struct vf_engine : EngineHandle {
         graph = nullptr;
         graph_iters = -1;
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    vf::Event ev0, ev1;
     std::vector<void*> allocs;
     // What is made after creation -- on first use, or grown on demand -- owns itself (vf_device_buf.hpp): `delete` frees it, and
     // vf_engine_grow moves it with the arrays, or leaves it with the handle, like every other member
@@ -136,8 +138,8 @@ struct vf_engine : EngineHandle {
     int ensure_side() {           // the second stream (hipStreamCreate costs 9 ms: only engines that stage asynchronously get one)
         if (stream2) return VF_OK;
         HIPCHK(hipStreamCreate(&stream2));
-        HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+        HIPCHK(ev_fork.ensure(hipEventDisableTiming));
+        HIPCHK(ev_join.ensure(hipEventDisableTiming));
         return VF_OK;
     }
     int join_side() {
@@ -201,41 +203,21 @@ struct vf_engine : EngineHandle {
         HIPCHK(pre_buf.ensure(bytes, [](size_t b) { return b < (1u << 16) ? (size_t)1 << 16 : b * 2; }));
         return VF_OK;
     }
-    // vf_engine_ingest_tail: pinned host staging (so the one host->device copy of an update is asynchronous), its device
-    // twin, the events that time the copy and the kernel, and the sticky status word the kernel reports into
-    vf::PinnedBuf<char> in_host;
-    vf::DeviceBuf<char> in_dev;
+    // The argument blocks of vf_engine_ingest_tail (and of an asynchronous vf_engine_preintegrate), vf_engine_propagate_tail and
+    // vf_engine_gate_tail travel through a channel each (vf_upload_channel.hpp: pinned block, device twin, the events that time the
+    // copy and the kernel): on asynchronous engines any of them may be in flight while another is used.  Made by the first call.
+    vf::UploadChannel ingest, prop, gate;
+    // ... and what the kernels write: the sticky status word of the ingest, the propagation's [B][16 + 225], the gate's [B] records of
+    // vf_gate_result's layout.  Whether the last two hold anything is SolveMemory's to say (propagation_valid, gate_valid).
     vf::DeviceBuf<int> in_status;
-    hipEvent_t in_ev[3] = {nullptr, nullptr, nullptr};
-    bool in_pending = false;
-    int ensure_ingest(size_t bytes) {
-        if (!in_ev[0])
-            for (auto& ev : in_ev) HIPCHK(hipEventCreate(&ev));
-        if (!in_status) {
-            HIPCHK(in_status.ensure(sizeof(int)));
-            HIPCHK(hipMemsetAsync(in_status, 0, sizeof(int), stream));
-        }
-        if (bytes <= in_host.bytes() && bytes <= in_dev.bytes()) return VF_OK;
-        if (in_pending) HIPCHK(hipEventSynchronize(in_ev[1]));       // (the copy out of the block about to go)
-        HIPCHK(in_host.ensure(bytes, vf::twice));
-        HIPCHK(in_dev.ensure(bytes, vf::twice));
+    vf::DeviceBuf<double> prop_out;
+    vf::DeviceBuf<char> gate_out;
+    int ensure_ingest() {
+        if (in_status) return VF_OK;
+        HIPCHK(in_status.ensure(sizeof(int)));
+        HIPCHK(hipMemsetAsync(in_status, 0, sizeof(int), stream));
         return VF_OK;
     }
-    // vf_engine_propagate_tail (engine/engine_propagate.inc): its own pinned staging block and device twin (the ingest block may be in
-    // flight on asynchronous engines), the events that time the copy and the kernel, and the output [B][16 + 225], all made by the
-    // first call.  Whether the output holds anything is SolveMemory's to say (propagation_valid).
-    vf::PinnedBuf<char> prop_host;
-    vf::DeviceBuf<char> prop_dev;
-    vf::DeviceBuf<double> prop_out;
-    hipEvent_t prop_ev[3] = {nullptr, nullptr, nullptr};
-    bool prop_pending = false;
-    // vf_engine_gate_tail (engine/engine_gate.inc): the same again, of its own -- neither Kprop's nor the ingest's, either may be in
-    // flight -- and the output, [B] records of vf_gate_result's layout.  Whether it holds anything is SolveMemory's to say (gate_valid).
-    vf::PinnedBuf<char> gate_host;
-    vf::DeviceBuf<char> gate_dev;
-    vf::DeviceBuf<char> gate_out;
-    hipEvent_t gate_ev[3] = {nullptr, nullptr, nullptr};
-    bool gate_pending = false;
     // far between factors (View::x_*): host mirror of how many slots are in use (the low-rank correction solves 6 right-hand
     // sides per slot in use), the right-hand-side scratch and the solved columns Z
     int x_used = 0;

@@ -30,6 +30,16 @@ def _i(a):
 FACTOR_CLASSES, CHI2_999 = _lib.FACTOR_CLASSES, _lib.CHI2_999
 
 
+def _imu_params(imu_cov):
+    return _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
+                           imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
+
+
+def _tail_args(step_off, steps, imu_cov):
+    """what ingest_tail, propagate_tail and gate_tail take alike, as the library wants it: offsets int32, samples (n, 7), ImuParamsC"""
+    return np.ascontiguousarray(step_off, dtype=np.int32), np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7), _imu_params(imu_cov)
+
+
 def _thresholds(thresholds):
     """six chi-square thresholds by class as a ctypes pointer (None: none): a sequence of six, {class name: value}, or
     {rows: value} (CHI2_999: every class gets the quantile of its own number of rows); classes left out flag nothing"""
@@ -206,39 +216,35 @@ class Engine:
         st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
         n = off.size - 1
         bh = np.ascontiguousarray(np.broadcast_to(np.asarray(bias_hat, dtype=np.float64), (n, 6)))
-        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
-                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
+        p = _imu_params(imu_cov)
         check(self._l.vf_engine_preintegrate(self._h, window, k0, n, _i(off), _d(st), _d(bh), C.byref(p)))
 
     def ingest_tail(self, step_off, steps, imu_cov, btw_a, btw_rec):
         """the ingest half of a fixed-lag update for all windows (vf_engine_ingest_tail): window w's next IMU factor from its
         raw samples steps[step_off[w]:step_off[w+1]], preintegrated with the window's current bias estimate, + the between
         record ending at the new keyframe (btw_a[w] = source slot or -1).  Asynchronous."""
-        off = np.ascontiguousarray(step_off, dtype=np.int32)
-        st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
+        off, st, p = _tail_args(step_off, steps, imu_cov)
         a = np.ascontiguousarray(btw_a, dtype=np.int32)
         r = np.ascontiguousarray(btw_rec, dtype=np.float64).reshape(-1, BTW_RECORD)
         assert off.size == self.windows + 1 and a.size == self.windows and r.shape[0] == self.windows
-        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
-                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
         check(self._l.vf_engine_ingest_tail(self._h, _i(off), _d(st), C.byref(p), _i(a), _d(r)))
+
+    def _status(self, entry):
+        h, k = C.c_float(), C.c_float()
+        check(entry(self._h, C.byref(h), C.byref(k)))
+        return h.value, k.value
 
     def ingest_status(self):
         """waits for the last ingest_tail, raises what its kernel reported, returns (h2d_ms, k0_ms) of that call"""
-        h, k = C.c_float(), C.c_float()
-        check(self._l.vf_engine_ingest_status(self._h, C.byref(h), C.byref(k)))
-        return h.value, k.value
+        return self._status(self._l.vf_engine_ingest_status)
 
     def propagate_tail(self, step_off, steps, imu_cov, covariance=False, from_estimate=False):
         """IMU-rate prediction for all windows (vf_engine_propagate_tail): window w's state after the raw samples
         steps[step_off[w]:step_off[w+1]] that follow its last keyframe (none: that keyframe), and with covariance=True the
         covariance propagated from that keyframe's marginal (marginals() first).  Writes a buffer of its own, nothing else.
         Asynchronous; read with read_propagated."""
-        off = np.ascontiguousarray(step_off, dtype=np.int32)
-        st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
+        off, st, p = _tail_args(step_off, steps, imu_cov)
         assert off.size == self.windows + 1 and st.shape[0] >= off[-1]
-        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
-                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
         flags = (_lib.PROPAGATE_COVARIANCE if covariance else 0) | (_lib.PROPAGATE_FROM_ESTIMATE if from_estimate else 0)
         check(self._l.vf_engine_propagate_tail(self._h, _i(off), _d(st) if st.size else None, C.byref(p), flags))
 
@@ -252,9 +258,7 @@ class Engine:
 
     def propagate_status(self):
         """waits for the last propagate_tail, returns (h2d_ms, kernel_ms) of that call"""
-        h, k = C.c_float(), C.c_float()
-        check(self._l.vf_engine_propagate_status(self._h, C.byref(h), C.byref(k)))
-        return h.value, k.value
+        return self._status(self._l.vf_engine_propagate_status)
 
     def gate_tail(self, step_off, steps, imu_cov, btw_a, btw_rec, threshold=None, from_estimate=False):
         """Innovation gate for all windows (vf_engine_gate_tail): the chi-square (6 dof) of a candidate between factor from slot
@@ -262,13 +266,10 @@ class Engine:
         steps[step_off[w]:step_off[w+1]] lead to, against the window as solved -- marginals() or marginals(tail=True) first.
         threshold: a window is marked rejected when its nis exceeds it (None: never; _lib.CHI2_6_99 = 16.81, CHI2_6_999 = 22.46).
         Writes a buffer of its own, nothing else.  Asynchronous; read with read_gate / read_gate_all."""
-        off = np.ascontiguousarray(step_off, dtype=np.int32)
-        st = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1, 7)
+        off, st, p = _tail_args(step_off, steps, imu_cov)
         a = np.ascontiguousarray(btw_a, dtype=np.int32)
         r = np.ascontiguousarray(btw_rec, dtype=np.float64).reshape(-1, BTW_RECORD)
         assert off.size == self.windows + 1 and st.shape[0] >= off[-1] and a.size == self.windows and r.shape[0] == self.windows
-        p = _lib.ImuParamsC(imu_cov["acc"], imu_cov["gyro"], imu_cov["integration"], imu_cov["bias_acc"],
-                            imu_cov["bias_omega"], imu_cov["bias_acc_omega_int"])
         check(self._l.vf_engine_gate_tail(self._h, _i(off), _d(st) if st.size else None, C.byref(p), _i(a), _d(r),
                                           0.0 if threshold is None else float(threshold), _lib.GATE_FROM_ESTIMATE if from_estimate else 0))
 
@@ -289,9 +290,7 @@ class Engine:
 
     def gate_status(self):
         """waits for the last gate_tail, returns (h2d_ms, kernel_ms) of that call"""
-        h, k = C.c_float(), C.c_float()
-        check(self._l.vf_engine_gate_status(self._h, C.byref(h), C.byref(k)))
-        return h.value, k.value
+        return self._status(self._l.vf_engine_gate_status)
 
     def get_imu(self, window, k0, n):
         r = np.zeros((n, IMU_RECORD))
