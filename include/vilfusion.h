@@ -321,10 +321,28 @@ int vf_engine_set_prior(vf_engine* e, int window, int k, const double* rec31);
  * sets a loss other than VF_LOSS_NONE makes the two per-slot arrays; an engine that never saw one launches what it always has.
  * A mutating call like vf_engine_set_between (on an asynchronous engine, n <= 4 enqueues and returns).  VF_ERR_INVALID: a loss id
  * outside 0..3, k not finite or <= 0 (ignored for VF_LOSS_NONE), a null pointer, a time-sharded engine; VF_ERR_BAD_KEY: a slot
- * outside the capacity.  Far factors (vf_engine_set_extra_between) take no loss. */
+ * outside the capacity.  Far factors take theirs with their list (vf_engine_set_extra_between_robust). */
 int vf_engine_set_between_loss(vf_engine* e, int window, int n, const int32_t* b, const int32_t* loss, const double* k);
 /* ... of slots k0 .. k0+n-1 (synchronises); VF_LOSS_NONE and k = 0 everywhere on an engine without the arrays.  Either output may be NULL. */
 int vf_engine_get_between_loss(vf_engine* e, int window, int k0, int n, int32_t* loss, double* k);
+/* Robust loss on far between factors (loop closures: the measurement most likely to be a false match, which no innovation gate
+ * reaches).  vf_engine_set_extra_between with a loss per entry: the loss is an attribute of the list ENTRY, and as the list is
+ * replaced as a whole the losses come with it -- vf_engine_set_extra_between IS this call with VF_LOSS_NONE everywhere, so a plain
+ * re-send clears them.  k_linearize_extra writes such an entry in the square-root form above; everything that reads a far factor's
+ * rows -- gradient, Woodbury columns and combine, the cost of a trial, the refined solve, the marginals, vf_engine_factor_errors
+ * (rho(s)), the marginalisation -- sees that factor and knows nothing of losses.  A Huber entry with s <= k is the Gaussian factor to
+ * the bit.  The loss stays on its entry through vf_engine_compact, vf_engine_grow and a re-anchoring slide; an entry whose older
+ * keyframe is marginalised becomes rows of the window's LINEAR far factor (or part of the marginal prior) at the weight it has at
+ * that linearisation, and leaves the list with its loss: linear far factors have none.  The first list that carries a loss other
+ * than VF_LOSS_NONE makes the two per-entry arrays; an engine that never saw one allocates and launches what it always has.
+ * VF_ERR_INVALID with nothing touched: a loss id outside 0..3, k not finite or <= 0 (ignored for VF_LOSS_NONE), a null pointer, a
+ * time-sharded engine (and vf_engine_set_shard refuses an engine that holds far losses); otherwise the codes of
+ * vf_engine_set_extra_between. */
+int vf_engine_set_extra_between_robust(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec28,
+                                       const int32_t* loss, const double* k);
+/* ... read back: max_far_factors entries each (VF_MAX_EXTRA by default), in the order of vf_engine_get_extra_between; VF_LOSS_NONE
+ * and k = 0 behind the list's end and on an engine without the arrays.  Either output may be NULL. */
+int vf_engine_get_extra_between_loss(vf_engine* e, int window, int32_t* loss, double* k);
 
 /* K0: IMU preintegration on the device.  Factor i (keyframe k0+i) integrates
  * steps[step_off[i] .. step_off[i+1]) (7 doubles each: dt, acc xyz, gyro xyz) with bias estimate
@@ -567,6 +585,11 @@ int vf_engine_read_imu_lin(vf_engine* e, int window, int which, int k0, int n, d
 /* (a factor with a robust loss, vf_engine_set_between_loss, reads back as K2 wrote it: r^ and J^ of its square-root form) */
 int vf_engine_read_between_lin(vf_engine* e, int window, int which, int k0, int n, double* r6,
                                double* Ja36, double* Jb36);
+/* ... its far twin: the linearisation of every entry of the window's far list (vf_engine_get_extra_between's order), max_far_factors
+ * entries each -- r6 [X][6], Ja36 / Jb36 [X][36] -- of the current (which = 0) or the trial buffer; an empty entry, and every entry
+ * of an engine that never held a far factor, reads as zeros; an entry with a loss as k_linearize_extra wrote it (r^, J^).  Any
+ * output may be NULL. */
+int vf_engine_read_extra_lin(vf_engine* e, int window, int which, double* r6, double* Ja36, double* Jb36);
 int vf_engine_read_normal(vf_engine* e, int window, int k0, int n, double* Hband, double* g15);
 int vf_engine_read_delta(vf_engine* e, int window, int k0, int n, double* delta15);
 /* Cholesky panels of the last vf_engine_solve: per keyframe 43 rows x 16 doubles (15 used) =
@@ -903,11 +926,18 @@ int vf_add_between(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const doubl
 /* GraphManager::addBetweenFactor with noiseModel::Robust over that Gaussian: loss = VF_LOSS_* with its parameter k ("Robust loss on
  * band between factors" above; vf_engine_set_between_loss behind the record at the solve, on the synchronous and the asynchronous
  * staging path alike).  Validates as vf_add_between does, with the same codes, and VF_ERR_INVALID for an unknown loss or a k that is
- * not finite and > 0; loss = VF_LOSS_NONE is vf_add_between.  Band factors only: a pair the band cannot hold (wider than
- * VF_MAX_BANDWIDTH keyframes, or a second factor ending at cur_key) would be a far factor, which takes no loss -- refused with
- * VF_ERR_INVALID, nothing staged.  Late odometry that a solve gives back keeps its loss. */
+ * not finite and > 0; loss = VF_LOSS_NONE is vf_add_between.  By default band factors only: a pair the band cannot hold (wider than
+ * VF_MAX_BANDWIDTH keyframes, or a second factor ending at cur_key) would be a far factor -- refused with VF_ERR_INVALID, nothing
+ * staged.  After vf_set_robust_far(g, 1) such a pair is staged as a far factor that carries its loss ("Robust loss on far between
+ * factors" above), through every solve, marginalisation of another closure's anchor and late arrival.  Late factors that a solve
+ * gives back keep their loss. */
 int vf_add_between_robust(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q_wxyz[4], const double t[3],
                           const double cov36[36], int loss, double k);
+/* on != 0: vf_add_between_robust accepts a pair the band cannot hold (a loop closure) and stages it as a far factor that carries its
+ * loss (vf_engine_set_extra_between_robust) instead of refusing it; 0, what a new handle does: refuse.  Any time; it decides about
+ * the factors added after it, the ones staged already keep what they have.  (A call, not a field of vf_graph_opts: the struct is
+ * as every caller built against it knows it.)  VF_ERR_INVALID: null handle. */
+int vf_set_robust_far(vf_graph* g, int on);
 /* GraphManager::addFactor(const CombinedImuFactor&) (GraphManager.cpp:90-94): queue a READY-MADE preintegrated factor
  * X(key-1),V(key-1),X(key),V(key),B(key-1),B(key) as its 190-double record (layout at the top of this file; e.g. what
  * vf_get_imu_factor returns) instead of cutting one from the IMU buffer.  key must be the next key (current + 1); the
@@ -949,6 +979,10 @@ int vf_get_degeneracy_scores(vf_graph* g, int source, int metric, unsigned subse
  * through the engine call, vf_engine_read_far_errors; they are part of vf_get_consistency.  VF_ERR_INVALID before the first solve;
  * VF_ERR_BAD_KEY for a key not solved yet or gone from the window.  Takes the state lock: never call it from inside a callback. */
 int vf_get_factor_errors(vf_graph* g, uint64_t key0, int n, double* imu_err, double* btw_err, uint64_t* btw_prev_key);
+/* ... and the nonlinear far factors (loop closures) alive after the last solve, in the order of the engine's list: *n of them, for
+ * each its two keys, its loss (VF_LOSS_*) with its parameter k, and its error (rho(s) under a loss: vf_engine_read_far_errors).  The
+ * arrays hold VF_MAX_FAR_LIMIT entries; any of them may be NULL.  Refusals and lock rule as vf_get_factor_errors. */
+int vf_get_far_factors(vf_graph* g, int* n, uint64_t* prev_key, uint64_t* cur_key, int* loss, double* k, double* err);
 /* graph.error(values) and printErrors with a threshold: the window's summary by factor class (vf_consistency; argmax in keyframe
  * slots of the handle's engine).  chi2_threshold6 as in vf_engine_factor_errors; a call with thresholds computes again (the
  * errors are the same bits), one without reads what the last call since the solve left, its flags included.  Refusals and lock rule as vf_get_factor_errors. */

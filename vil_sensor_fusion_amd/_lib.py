@@ -113,11 +113,11 @@ SYMBOLS = [
     "vf_engine_create", "vf_engine_create_tuned", "vf_engine_destroy",
     "vf_engine_set_range", "vf_engine_set_states", "vf_engine_get_states", "vf_engine_set_imu",
     "vf_engine_set_between", "vf_engine_clear_between", "vf_engine_set_extra_between", "vf_engine_get_extra_between", "vf_engine_get_linear_far", "vf_engine_set_prior",
-    "vf_engine_set_between_loss", "vf_engine_get_between_loss",
+    "vf_engine_set_between_loss", "vf_engine_get_between_loss", "vf_engine_set_extra_between_robust", "vf_engine_get_extra_between_loss",
     "vf_engine_linearize", "vf_engine_assemble", "vf_engine_solve", "vf_engine_retract",
     "vf_engine_decide", "vf_engine_iterate", "vf_engine_slide", "vf_engine_predict",
     "vf_engine_sync", "vf_engine_graph_info", "vf_engine_solve_form",
-    "vf_engine_read_imu_lin", "vf_engine_read_between_lin", "vf_engine_read_normal",
+    "vf_engine_read_imu_lin", "vf_engine_read_between_lin", "vf_engine_read_extra_lin", "vf_engine_read_normal",
     "vf_engine_read_delta", "vf_engine_read_panels", "vf_engine_read_lm", "vf_engine_marginals", "vf_engine_marginals_ex", "vf_engine_read_marginals",
     "vf_engine_read_pose_marginals", "vf_engine_marginal_scores", "vf_engine_read_marginal_scores",
     "vf_engine_factor_errors", "vf_engine_read_factor_errors", "vf_engine_read_far_errors", "vf_engine_read_consistency", "vf_engine_read_health",
@@ -134,8 +134,8 @@ SYMBOLS = [
     "vf_engine_isam_step", "vf_engine_predict_from_estimate", "vf_engine_get_estimate", "vf_engine_incremental_info", "vf_engine_set_async", "vf_engine_read_result", "vf_engine_marginalize_ahead",
     "vf_graph_default_opts", "vf_graph_default_opts_sized", "vf_create", "vf_destroy", "vf_add_imu", "vf_reserve_node",
     "vf_add_between", "vf_solve", "vf_get_state", "vf_get_bias", "vf_most_recent_pose_time",
-    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_predict_state", "vf_gate_between", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
-    "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged", "vf_graph_get_staged_loss", "vf_add_between_robust",
+    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_get_far_factors", "vf_predict_state", "vf_gate_between", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
+    "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged", "vf_graph_get_staged_loss", "vf_add_between_robust", "vf_set_robust_far",
     "vf_degeneracy_batch", "vf_degeneracy_spectrum_batch", "vf_degeneracy_scores_batch", "vf_dopt_filter_f32", "vf_degeneracy_remap_batch",
 ]
 

@@ -69,3 +69,51 @@ int vf_engine_get_between_loss(vf_engine* e, int window, int k0, int n, int32_t*
     HIPCHK(hipStreamSynchronize(e->stream));
     return VF_OK;
 }
+
+// ---- robust losses of the far between factors: an attribute of the list ENTRY (vf_engine::h_xloss, h_xk; on the device behind the
+// records of View::x_in, vf::far_loss).  The list is replaced as a whole, so the losses come with it (set_far_list, engine_staging.inc).
+int vf_engine_set_extra_between_robust(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec28,
+                                       const int32_t* loss, const double* k) {
+    // (the arguments first, the engine after them: a refused call has touched nothing)
+    if (n > 0 && (!loss || !k)) return fail(VF_ERR_INVALID, "null argument");
+    for (int i = 0; i < n; i++) {
+        if (loss[i] < VF_LOSS_NONE || loss[i] > VF_LOSS_GEMAN_MCCLURE) return fail(VF_ERR_INVALID, "far between loss %d: unknown loss id %d", i, loss[i]);
+        if (loss[i] != VF_LOSS_NONE && !(k[i] > 0.0 && std::isfinite(k[i]))) return fail(VF_ERR_INVALID, "far between loss %d: the parameter k must be finite and > 0 (got %g)", i, k[i]);
+    }
+    if (!e) return fail(VF_ERR_INVALID, "engine is null");
+    if (e->v.sh_G > 1) return fail(VF_ERR_INVALID, "vf_engine_set_extra_between_robust: losses on time-sharded engines are not built (shard %d of %d)", e->v.sh_r, e->v.sh_G);
+    return set_far_list(e, window, n, a, b, rec28, loss, k);
+}
+
+int vf_engine_get_extra_between_loss(vf_engine* e, int window, int32_t* loss, double* k) {
+    int rc = check_window(e, window);
+    if (rc) return rc;
+    const int cnt = e->v.x_max ? e->h_xn[window] : 0;
+    for (int i = 0; i < e->x_cap; i++) {
+        if (loss) loss[i] = i < cnt ? e->h_xloss[window][i] : VF_LOSS_NONE;
+        if (k) k[i] = i < cnt ? e->h_xk[window][i] : 0.0;
+    }
+    return VF_OK;
+}
+
+int vf_engine_read_extra_lin(vf_engine* e, int window, int which, double* r6, double* Ja, double* Jb) {
+    Entry entry_(e, Entry::reads);
+    int rc = check_window(e, window);
+    if (rc) return rc;
+    const int X = e->x_cap;
+    std::vector<double> h((size_t)X * vf::BTW_OUT, 0.0);
+    if (e->v.x_max > 0) {
+        int sel = 0;
+        if ((rc = read_sel(e, window, &sel))) return rc;
+        const int b = sel ^ (which ? 1 : 0);
+        HIPCHK(hipMemcpyAsync(h.data(), e->v.x_out + ((size_t)b * e->v.B + window) * X * vf::BTW_OUT, h.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    for (int i = 0; i < X; i++) {
+        const double* p = h.data() + (size_t)i * vf::BTW_OUT;
+        if (r6) memcpy(r6 + (size_t)i * 6, p, 6 * sizeof(double));
+        if (Ja) memcpy(Ja + (size_t)i * 36, p + 6, 36 * sizeof(double));
+        if (Jb) memcpy(Jb + (size_t)i * 36, p + 42, 36 * sizeof(double));
+    }
+    return VF_OK;
+}

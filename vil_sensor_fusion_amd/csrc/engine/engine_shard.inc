@@ -45,6 +45,7 @@ int vf_engine_set_shard(vf_engine* e, int rank, int world) {
         return fail(VF_ERR_INVALID, "time sharding needs an explicit chunk count (vf_engine_opts.chunks >= 2)");
     if (world > 1 && e->v.P % world != 0) return fail(VF_ERR_INVALID, "chunks (%d) must be a multiple of the world size (%d)", e->v.P, world);
     if (world > 1 && e->v.btw_loss) return fail(VF_ERR_INVALID, "this engine holds robust losses (vf_engine_set_between_loss): losses on time-sharded engines are not built");
+    if (world > 1 && e->v.x_loss) return fail(VF_ERR_INVALID, "this engine holds robust losses of far factors (vf_engine_set_extra_between_robust): losses on time-sharded engines are not built");
     HIPCHK(hipStreamSynchronize(e->stream));
     e->v.sh_r = rank;
     e->v.sh_G = world;

@@ -189,7 +189,10 @@ int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, con
     return VF_OK;
 }
 
-int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec) {
+// A window's far list, replaced as a whole: the entries and, with them, their robust losses (loss / k null: every entry Gaussian,
+// vf_engine_set_extra_between; the arguments of vf_engine_set_extra_between_robust have been checked by it).  Every place that
+// rebuilds a list -- transport_far, vf_engine_compact, vf_engine_grow -- comes through here with the losses of the entries it keeps.
+static int set_far_list(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec, const int32_t* loss, const double* k) {
     Entry entry_(e, Entry::rewrites);
     int rc = check_window(e, window);
     if (rc) return rc;
@@ -204,10 +207,17 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
         if (!(rec[(size_t)i * vf::BTW_IN + 7] > 0.0)) return fail(VF_ERR_NOT_SPD, "far between factor %d: singular square-root information", i);
     }
     if (e->v.x_max == 0 && n == 0) return VF_OK;
+    // the losses as the engine keeps them: one id and one parameter per entry, 0 and 0.0 for an entry without a loss
+    std::vector<int> hl(n, VF_LOSS_NONE);
+    std::vector<double> hk(n, 0.0);
+    bool any_loss = false;
+    for (int i = 0; i < n && loss; i++)
+        if (loss[i] != VF_LOSS_NONE) { hl[i] = loss[i]; hk[i] = k[i]; any_loss = true; }
     // the list the device holds already (the GraphManager re-sends its far factors at every solve; a slide that converts none
     // re-sends the survivors): nothing to do -- no copies, no synchronisation, the captured launch sequence stays valid
     if (e->v.x_max > 0 && !e->h_xdirty[window] && n == e->h_xn[window] && (n == 0 || (!memcmp(a, e->h_xa[window].data(), n * sizeof(int)) &&
-        !memcmp(b, e->h_xb[window].data(), n * sizeof(int)) && !memcmp(rec, e->h_xrec[window].data(), (size_t)n * vf::BTW_IN * sizeof(double))))) {
+        !memcmp(b, e->h_xb[window].data(), n * sizeof(int)) && !memcmp(rec, e->h_xrec[window].data(), (size_t)n * vf::BTW_IN * sizeof(double)) &&
+        !memcmp(hl.data(), e->h_xloss[window].data(), n * sizeof(int)) && !memcmp(hk.data(), e->h_xk[window].data(), n * sizeof(double))))) {
         const int before = e->x_used;
         e->recount_far();                                // (the linear far ends are counted too, and those come and go without this list changing)
         if (e->x_used != before) e->epoch++;
@@ -222,6 +232,7 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
         if ((rc = e->ensure_far(need))) return rc;
     }
     e->attach_far();
+    if (any_loss && (rc = e->ensure_far_loss())) return rc;      // (the first list that carries a loss makes the arrays)
     lap("ensure_far");
     // the column engine holds a copy of the window's H per Woodbury column: sized by the far factors alive (6 columns each), grown
     // by doubling -- one loop closure costs 6 windows (0.14 GB, 2 ms to make at 1 200 slots), not the 48 of VF_MAX_EXTRA (1.3 GB, 13 ms)
@@ -251,6 +262,8 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
     e->h_xa[window].assign(a, a + n);
     e->h_xb[window].assign(b, b + n);
     e->h_xrec[window].assign(rec, rec + (size_t)n * vf::BTW_IN);
+    e->h_xloss[window] = hl;
+    e->h_xk[window] = hk;
     std::vector<int> ha(X, -1), hb(X, -1);
     std::vector<double> hr((size_t)X * vf::BTW_IN, 0.0);
     for (int i = 0; i < n; i++) { ha[i] = a[i]; hb[i] = b[i]; }
@@ -258,6 +271,12 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
     HIPCHK(hipMemcpyAsync(e->v.x_a + (size_t)window * X, ha.data(), X * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->v.x_b + (size_t)window * X, hb.data(), X * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->v.x_in + (size_t)window * X * vf::BTW_IN, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    if (e->v.x_loss) {              // (a list without losses on an engine that holds the arrays: NONE everywhere, which is what clears them)
+        hl.resize(X, VF_LOSS_NONE);
+        hk.resize(X, 0.0);
+        HIPCHK(hipMemcpyAsync(e->x_loss_id(window), hl.data(), X * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->x_loss_k(window), hk.data(), X * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    }
     // both linearisation buffers of the window start from zeros (an empty slot must read as "no factor")
     for (int bf = 0; bf < 2; bf++)
         HIPCHK(hipMemsetAsync(e->v.x_out + ((size_t)bf * B + window) * X * vf::BTW_OUT, 0, (size_t)X * vf::BTW_OUT * sizeof(double), e->stream));
@@ -268,6 +287,10 @@ int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* 
     e->recount_far();
     e->epoch++;        // (the number of band solves per trial is baked into a captured launch sequence)
     return VF_OK;
+}
+
+int vf_engine_set_extra_between(vf_engine* e, int window, int n, const int32_t* a, const int32_t* b, const double* rec) {
+    return set_far_list(e, window, n, a, b, rec, nullptr, nullptr);
 }
 
 int vf_engine_clear_between(vf_engine* e, int window, int k0, int n) {

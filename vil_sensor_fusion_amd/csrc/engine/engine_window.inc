@@ -104,8 +104,8 @@ static int transport_far(vf_engine* e, bool marginalised) {
         // (2) the nonlinear ones anchored at lo
         double st[32], R0[9], qD[4], tD[3], RD[9], qDc[4];
         bool have_D = false;
-        std::vector<int> a, b;
-        std::vector<double> rec;
+        std::vector<int> a, b, loss;        // (an entry that stays, re-anchored or not, keeps its loss; one that leaves takes it along)
+        std::vector<double> rec, lk;
         for (int i = 0; i < e->h_xn[w]; i++) {
             double r[vf::BTW_IN];
             memcpy(r, e->h_xrec[w].data() + (size_t)i * vf::BTW_IN, sizeof(r));
@@ -141,10 +141,12 @@ static int transport_far(vf_engine* e, bool marginalised) {
             a.push_back(ai);
             b.push_back(kb);
             rec.insert(rec.end(), r, r + vf::BTW_IN);
+            loss.push_back(e->h_xloss[w][i]);
+            lk.push_back(e->h_xk[w][i]);
         }
         e->h_lb[w] = lb;
         if (had_linear && !marginalised) HIPCHK(hipMemsetAsync(e->v.xl_n + w, 0, sizeof(int), e->stream));
-        if (int rc = vf_engine_set_extra_between(e, w, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+        if (int rc = set_far_list(e, w, (int)a.size(), a.data(), b.data(), rec.data(), loss.data(), lk.data())) return rc;
     }
     return VF_OK;
 }
@@ -336,15 +338,17 @@ int vf_engine_compact(vf_engine* e, int shift) {
     // far between factors: slots move down with the keyframes; one whose older keyframe was reclaimed is gone
     for (int w = 0; w < v.B && v.x_max > 0; w++) {
         if (e->h_xn[w] == 0) continue;
-        std::vector<int> a, b;
-        std::vector<double> r;
+        std::vector<int> a, b, loss;
+        std::vector<double> r, lk;
         for (int i = 0; i < e->h_xn[w]; i++) {
             if (e->h_xa[w][i] < shift) continue;
             a.push_back(e->h_xa[w][i] - shift);
             b.push_back(e->h_xb[w][i] - shift);
             r.insert(r.end(), e->h_xrec[w].begin() + (size_t)i * vf::BTW_IN, e->h_xrec[w].begin() + (size_t)(i + 1) * vf::BTW_IN);
+            loss.push_back(e->h_xloss[w][i]);
+            lk.push_back(e->h_xk[w][i]);
         }
-        if (int rc = vf_engine_set_extra_between(e, w, (int)a.size(), a.data(), b.data(), r.data())) return rc;
+        if (int rc = set_far_list(e, w, (int)a.size(), a.data(), b.data(), r.data(), loss.data(), lk.data())) return rc;
     }
     for (int w = 0; w < v.B && v.x_max > 0; w++) {          // ... and so do the far ends of the linear ones (always inside the window)
         if (e->h_lb[w].empty()) continue;
@@ -425,7 +429,7 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
             n->h_lb = e->h_lb;
         }
         for (int w = 0; w < e->v.B; w++)
-            if (e->h_xn[w] > 0 && (rc = vf_engine_set_extra_between(n, w, e->h_xn[w], e->h_xa[w].data(), e->h_xb[w].data(), e->h_xrec[w].data()))) {
+            if (e->h_xn[w] > 0 && (rc = set_far_list(n, w, e->h_xn[w], e->h_xa[w].data(), e->h_xb[w].data(), e->h_xrec[w].data(), e->h_xloss[w].data(), e->h_xk[w].data()))) {
                 vf_engine_destroy(n);
                 return rc;
             }

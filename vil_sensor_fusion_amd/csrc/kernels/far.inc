@@ -9,7 +9,13 @@
 VF_DI void marg_delta(const View& v, int w, int b, double (&d)[27]);
 #include "../vf_far.hpp"
 // One lane per (window, index): entry `index` of the window's nonlinear list, and far end `index` of its linear far factor
-// (the six rows that belong to it)
+// (the six rows that belong to it).
+// RB: the engine holds losses of far factors (View::x_loss; far_loss).  An entry the loss changes -- not LOSS_NONE, not a Huber inlier,
+// not s = 0 -- is rewritten in its square-root form by the second pass K2 applies to a band factor (robustify_between, over the 78
+// words the lane has just stored); every consumer of x_out reads r^ and J^ and knows nothing of losses.  The RB = false instance
+// reads no new word: the kernel as it was before far factors took losses, chosen on the host (launch.inc).  The linear far factor
+// (xl_*) has no loss: a robust far factor enters it at the weight of the linearisation it is marginalised at.
+template <bool RB>
 __global__ void __launch_bounds__(64) k_linearize_extra(View v, int which) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= v.B * v.x_max) return;
@@ -20,7 +26,13 @@ __global__ void __launch_bounds__(64) k_linearize_extra(View v, int which) {
         const int a = v.x_a[i], kb = v.x_b[i];
         double* out = v.x_out + ((size_t)b * v.B * v.x_max + i) * BTW_OUT;
         if (a < lo || kb >= hi || a >= kb) { for (int f = 0; f < BTW_OUT; f++) out[f] = 0.0; }
-        else between_core<false>(v, b, (long)w * v.M + a, (long)w * v.M + kb, v.x_in + (size_t)i * BTW_IN, 1, out, 1, true);
+        else {
+            between_core<false>(v, b, (long)w * v.M + a, (long)w * v.M + kb, v.x_in + (size_t)i * BTW_IN, 1, out, 1, true);
+            if constexpr (RB) {
+                const FarLoss fl = far_loss(v, i);
+                if (fl.loss != LOSS_NONE) robustify_between<1>(out, fl.loss, fl.k);
+            }
+        }
     }
     double* lout = v.xl_out + ((size_t)b * v.B + w) * 6 * v.x_max + 6 * s;
     const int nl = v.xl_n[w];

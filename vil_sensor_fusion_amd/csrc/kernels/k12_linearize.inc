@@ -312,24 +312,26 @@ __device__ __forceinline__ void between_core(const View& v, const int b, const l
 // way the words of a slot without a loss, and of a Huber inlier (s <= k, s = k included), are those kernels' code and bits, and
 // only a factor the loss changes pays the second pass: r (6), then column by column the 6 + 6 entries of Ja / Jb and their dots
 // r^T Ja[:, c], r^T Jb[:, c] -- read back from the lane's own words (same lane, same addresses: program order).
+// STRIDE: doubles between two of the 78 words -- TILE in btw_out (the band kernels, which name none), 1 in x_out (k_linearize_extra).
+template <int STRIDE = TILE>
 __device__ __forceinline__ void robustify_between(double* out, const int loss, const double k) {
     asm volatile("" ::: "memory");            // (the words are read back, not kept in 78 registers across between_core)
     double rr[6];
     double s2 = 0.0;
 #pragma unroll
-    for (int i = 0; i < 6; i++) { rr[i] = out[(size_t)i * TILE]; s2 = fma(rr[i], rr[i], s2); }
+    for (int i = 0; i < 6; i++) { rr[i] = out[(size_t)i * STRIDE]; s2 = fma(rr[i], rr[i], s2); }
     const double s = sqrt(s2);
     if (loss == LOSS_HUBER && s <= k) return;       // (a NaN norm is no inlier: alpha is NaN and so is every word below)
     const double alpha = robust_alpha(loss, s, k), gamma = robust_gamma(loss, s, k);
 #pragma unroll
-    for (int i = 0; i < 6; i++) __builtin_nontemporal_store(alpha * rr[i], out + (size_t)i * TILE);
+    for (int i = 0; i < 6; i++) __builtin_nontemporal_store(alpha * rr[i], out + (size_t)i * STRIDE);
 #pragma unroll
     for (int c = 0; c < 6; c++) {
         double pa[6], pb[6], da = 0.0, db = 0.0;
 #pragma unroll
         for (int i = 0; i < 6; i++) {
-            pa[i] = out[(size_t)(6 + i * 6 + c) * TILE];
-            pb[i] = out[(size_t)(42 + i * 6 + c) * TILE];
+            pa[i] = out[(size_t)(6 + i * 6 + c) * STRIDE];
+            pb[i] = out[(size_t)(42 + i * 6 + c) * STRIDE];
             da = fma(rr[i], pa[i], da);
             db = fma(rr[i], pb[i], db);
         }
@@ -337,8 +339,8 @@ __device__ __forceinline__ void robustify_between(double* out, const int loss, c
         db *= gamma;
 #pragma unroll
         for (int i = 0; i < 6; i++) {
-            __builtin_nontemporal_store(fma(da, rr[i], alpha * pa[i]), out + (size_t)(6 + i * 6 + c) * TILE);
-            __builtin_nontemporal_store(fma(db, rr[i], alpha * pb[i]), out + (size_t)(42 + i * 6 + c) * TILE);
+            __builtin_nontemporal_store(fma(da, rr[i], alpha * pa[i]), out + (size_t)(6 + i * 6 + c) * STRIDE);
+            __builtin_nontemporal_store(fma(db, rr[i], alpha * pb[i]), out + (size_t)(42 + i * 6 + c) * STRIDE);
         }
     }
 }

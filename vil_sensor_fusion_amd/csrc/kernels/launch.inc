@@ -15,7 +15,10 @@ void launch_ingest_tail(const View& v, const int* off, const double* steps, cons
                        tail_btw, prm, status);
 }
 void launch_linearize_extra(const View& v, int which, hipStream_t s) {
-    if (v.x_max > 0) hipLaunchKernelGGL(k_linearize_extra, dim3(nblk((long)v.B * v.x_max, 64)), dim3(64), 0, s, v, which);
+    if (v.x_max <= 0) return;
+    // (an engine that holds far losses, View::x_loss, launches the instance that reads them: chosen here, as K2's is below)
+    if (v.x_loss) hipLaunchKernelGGL(k_linearize_extra<true>, dim3(nblk((long)v.B * v.x_max, 64)), dim3(64), 0, s, v, which);
+    else hipLaunchKernelGGL(k_linearize_extra<false>, dim3(nblk((long)v.B * v.x_max, 64)), dim3(64), 0, s, v, which);
 }
 void launch_extra_gradient(const View& v, hipStream_t s) {
     if (v.x_max > 0) hipLaunchKernelGGL(k_extra_gradient, dim3(v.B), dim3(64), 0, s, v);

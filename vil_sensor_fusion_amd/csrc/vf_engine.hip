@@ -226,6 +226,29 @@ struct vf_engine : EngineHandle {
     std::vector<char> h_xdirty;                        // the device's copy of a window's list may differ from the host's (k_marginalize has
                                                        // struck out entries the host has not yet): vf_engine_set_extra_between must re-send
     std::vector<std::vector<double>> h_xrec;
+    // ... and the robust loss of every entry (vf_engine_set_extra_between_robust): an attribute of the list ENTRY, so it goes wherever the
+    // list goes -- these mirrors are carried by every place that rebuilds a list (transport_far, vf_engine_compact, vf_engine_grow).
+    // On the device the two arrays are late: the first list that carries a loss other than VF_LOSS_NONE moves the records of x_in into
+    // an allocation with room for them behind the records (vf::far_loss_words) and sets View::x_loss, from where on k_linearize_extra
+    // is the instance that reads them -- another launch sequence, so a captured one is void.  An engine that never saw a far loss
+    // allocates, copies and launches what it always has.
+    std::vector<std::vector<int>> h_xloss;
+    std::vector<std::vector<double>> h_xk;
+    vf::DeviceBuf<double> x_li_loss;
+    double* x_loss_k(int window) const { return v.x_in + vf::far_loss_k_at((size_t)v.B * x_cap) + (size_t)window * x_cap; }
+    int* x_loss_id(int window) const { return (int*)(v.x_in + vf::far_loss_id_at((size_t)v.B * x_cap)) + (size_t)window * x_cap; }
+    int ensure_far_loss() {          // after attach_far
+        if (v.x_loss) return VF_OK;
+        const size_t n = (size_t)v.B * x_cap, rec_bytes = n * vf::BTW_IN * sizeof(double), all = vf::far_loss_words(n) * sizeof(double);
+        HIPCHK(x_li_loss.ensure(all));
+        HIPCHK(hipMemcpyAsync(x_li_loss, x_li, rec_bytes, hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipMemsetAsync((char*)x_li_loss.get() + rec_bytes, 0, all - rec_bytes, stream));
+        x_li = x_li_loss;            // (the records' first home stays in the engine's arena, unused)
+        v.x_in = x_li;
+        v.x_loss = 1;
+        epoch++;
+        return VF_OK;
+    }
     vf::DeviceBuf<double> x_gtmp;
     vf::DeviceBuf<double> x_Z;   // 6 columns of x_zstride for every slot in use; grown on demand, never beyond x_cap slots
     size_t x_zstride = 0;
@@ -255,6 +278,8 @@ struct vf_engine : EngineHandle {
         h_xa.assign(v.B, {});
         h_xb.assign(v.B, {});
         h_xrec.assign(v.B, {});
+        h_xloss.assign(v.B, {});
+        h_xk.assign(v.B, {});
         h_lb.assign(v.B, {});
     }
     void recount_far() {

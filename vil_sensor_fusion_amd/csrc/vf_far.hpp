@@ -18,6 +18,15 @@ VF_DI FarRef far_ref(const View& v, int w, int s) {
     }
     return f;
 }
+// The robust loss of entry i = w * x_max + index of the nonlinear lists (engines with View::x_loss only; DESIGN.md "4i"): the arrays
+// sit in the allocation of x_in behind its [B][x_max] records -- the parameters k, [B][x_max] doubles, then the ids, [B][x_max]
+// ints (far_loss_k_at, far_loss_id_at: vf_kernels.hpp, where the host that makes and fills them finds the same offsets) -- and this
+// is the one device-side reader.
+struct FarLoss { int loss; double k; };
+VF_DI FarLoss far_loss(const View& v, int i) {
+    const size_t n = (size_t)v.B * v.x_max;
+    return {reinterpret_cast<const int*>(v.x_in + far_loss_id_at(n))[i], v.x_in[far_loss_k_at(n) + i]};
+}
 VF_DI int far_cols(const FarRef& f) { return f.kind == 1 ? 27 + 6 * f.nl : 12; }
 // column c of a slot's six rows -> (window-local keyframe, dof of its 15)
 VF_DI void far_col(const View& v, int w, const FarRef& f, int c, int& k, int& d) {

@@ -42,6 +42,8 @@ struct SolveTake {
     bool fars_changed = false;              // `fars` is no longer what the handle's list holds
     bool requeue = false;                   // the solve failed before the optimisation: everything goes back
     vf_between_loss_setter set_loss = nullptr;   // the handle's set_between_loss as it stood at the take (read under graph_mutex, where it is written)
+    vf_far_robust_setter set_far_robust = nullptr;   // ... and its two calls for the losses of far factors, likewise
+    vf_far_loss_getter get_far_loss = nullptr;
 };
 
 struct Lap {   // VF_SOLVE_TIMING: "[vf_solve] <label> <us>" on stderr behind every step of a solve (tools/gm_lap_summary.py reads the labels)
@@ -382,7 +384,7 @@ int vf_add_between(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], 
 }
 // ... with a robust loss (vf_add_between_robust, vf_graph_robust.cpp, which has checked loss and loss_k)
 int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36], int loss, double loss_k,
-                    vf_between_loss_setter setter) {
+                    const vf_robust_calls* calls) {
     if (!g || !q || !t || !cov) return gerr(VF_ERR_INVALID, "null argument");
     PendingBetween b;
     b.a = prev;
@@ -395,10 +397,10 @@ int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4],
     bool band = cur - prev <= VF_MAX_BANDWIDTH && !g->has_band_end(cur);
     for (const auto& s : g->staged_between)
         if (s.b == cur) band = false;
-    if (!band && loss != VF_LOSS_NONE)
-        return gerr(VF_ERR_INVALID, "between factor (%llu, %llu) spans %llu keyframes or shares its end key: it would be a far factor, and far factors take no robust loss",
-                    (unsigned long long)prev, (unsigned long long)cur, (unsigned long long)(cur - prev));
-    if (setter) g->set_between_loss = setter;
+    if (!band && loss != VF_LOSS_NONE && !g->robust_far)
+        return gerr(VF_ERR_INVALID, "between factor (%llu, %llu) spans %llu keyframes or shares its end key: it would be a far factor, and far factors take no robust loss "
+                    "on this handle (vf_set_robust_far is off)",(unsigned long long)prev, (unsigned long long)cur, (unsigned long long)(cur - prev));
+    if (calls) { g->set_between_loss = calls->set_between_loss; g->set_far_robust = calls->set_far_robust; g->get_far_loss = calls->get_far_loss; }
     if (band) {
         g->staged_between.push_back(b);
     } else {
@@ -525,6 +527,8 @@ static void take(vf_graph* g, SolveTake& t) {
     t.imus.swap(g->imu_queue);
     t.betweens.swap(g->staged_between);
     t.set_loss = g->set_between_loss;
+    t.set_far_robust = g->set_far_robust;
+    t.get_far_loss = g->get_far_loss;
     for (const auto& bt : t.betweens) g->set_band_end(bt.b, 1);   // these keys now carry their band factor (a second one goes to the far list)
     // (keys below the window can never be named again by a factor that is accepted: their marks are let go)
     while (!g->band_end.empty() && g->band_base < oldest_key(g)) { g->band_end.pop_front(); g->band_base++; }
@@ -692,12 +696,18 @@ static int adopt_engine_far_list(vf_graph* g, SolveTake& t) {
     int32_t ea[VF_MAX_FAR_LIMIT], eb[VF_MAX_FAR_LIMIT];
     double erec[VF_MAX_FAR_LIMIT * VF_BTW_RECORD];
     if ((rc = vf_engine_get_extra_between(g->eng, 0, &cnt, ea, eb, erec, nullptr, nullptr, nullptr))) return rc;
+    // ... and the loss of every entry with it (an attribute of the list entry: the engine's list has kept each on its own through the
+    // marginalisation).  A handle that was never given a robust factor has no call to make and no loss to lose
+    int32_t eloss[VF_MAX_FAR_LIMIT] = {0};
+    double ek[VF_MAX_FAR_LIMIT] = {0};
+    if (t.get_far_loss && (rc = t.get_far_loss(g->eng, 0, eloss, ek))) return rc;
     std::vector<PendingBetween> moved;
     for (int i = 0; i < cnt; i++) {
         PendingBetween f;
         f.a = (uint64_t)ea[i] + g->key_base, f.b = (uint64_t)eb[i] + g->key_base;
         memcpy(f.rec, erec + (size_t)i * VF_BTW_RECORD, sizeof(f.rec));
         f.on_device = true;
+        f.loss = eloss[i], f.loss_k = ek[i];
         moved.push_back(f);
     }
     for (const auto& f : t.fars)
@@ -712,15 +722,22 @@ static int adopt_engine_far_list(vf_graph* g, SolveTake& t) {
 // `lo`; the list is re-sent at every solve, so compaction and growth need no bookkeeping here)
 static int stage_far_list(vf_graph* g, SolveTake& t, Lap& lap) {
     if (t.fars.empty() && !g->far_on_device) return VF_OK;
-    std::vector<int32_t> a, b;
-    std::vector<double> rec;
+    std::vector<int32_t> a, b, loss;
+    std::vector<double> rec, k;
+    bool robust = false;
     for (const auto& f : t.fars) {
         if (!in_window(g, f, t.last_key)) continue;
         a.push_back(slot_of(g, f.a));
         b.push_back(slot_of(g, f.b));
         rec.insert(rec.end(), f.rec, f.rec + VF_BTW_RECORD);
+        loss.push_back(f.loss);
+        k.push_back(f.loss_k);
+        robust = robust || f.loss != VF_LOSS_NONE;
     }
-    if (int rc = vf_engine_set_extra_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+    // (the losses travel with the list; a list without one is the plain call, which also clears what an earlier list carried)
+    if (robust && !t.set_far_robust) return gerr(VF_ERR_INVALID, "a far factor carries a loss and the handle has no call to send it with");
+    if (int rc = robust ? t.set_far_robust(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data(), loss.data(), k.data())
+                        : vf_engine_set_extra_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
     g->far_on_device = !a.empty();
     for (auto& f : t.fars)
         if (in_window(g, f, t.last_key)) { t.fars_changed = t.fars_changed || !f.on_device; f.on_device = true; }

@@ -52,6 +52,27 @@ int vf_get_factor_errors(vf_graph* g, uint64_t key0, int n, double* imu_err, dou
     return VF_OK;
 }
 
+int vf_get_far_factors(vf_graph* g, int* n, uint64_t* prev_key, uint64_t* cur_key, int* loss, double* k, double* err) {
+    if (!g || !n) return eerr(VF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(g->state_mutex);
+    if (int rc = ensure_errors(g, nullptr)) return rc;
+    int cnt = 0;
+    int32_t a[VF_MAX_FAR_LIMIT], b[VF_MAX_FAR_LIMIT], li[VF_MAX_FAR_LIMIT];
+    double kk[VF_MAX_FAR_LIMIT], fe[VF_MAX_FAR_LIMIT], fl[VF_MAX_FAR_LIMIT];
+    if (int rc = vf_engine_get_extra_between(g->eng, 0, &cnt, a, b, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (int rc = vf_engine_get_extra_between_loss(g->eng, 0, li, kk)) return rc;
+    if (int rc = vf_engine_read_far_errors(g->eng, 0, fe, fl)) return rc;
+    *n = cnt;
+    for (int i = 0; i < cnt; i++) {
+        if (prev_key) prev_key[i] = g->key_base + (uint64_t)a[i];
+        if (cur_key) cur_key[i] = g->key_base + (uint64_t)b[i];
+        if (loss) loss[i] = li[i];
+        if (k) k[i] = kk[i];
+        if (err) err[i] = fe[i];
+    }
+    return VF_OK;
+}
+
 int vf_get_consistency(vf_graph* g, const double* chi2_threshold6, vf_consistency* out) {
     if (!g || !out) return eerr(VF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->state_mutex);

@@ -26,6 +26,10 @@ struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device
 // a between factor as the caller handed it in: what GraphManager::graph() shows until the next solve (vf_graph_get_staged, vf_graph_get_staged_loss)
 struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; int loss = VF_LOSS_NONE; double loss_k = 0.0; };
 typedef int (*vf_between_loss_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*);   // vf_engine_set_between_loss
+// ... and the two calls a far factor's loss needs: vf_engine_set_extra_between_robust, vf_engine_get_extra_between_loss
+typedef int (*vf_far_robust_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*, const int32_t*, const double*);
+typedef int (*vf_far_loss_getter)(vf_engine*, int, int32_t*, double*);
+struct vf_robust_calls { vf_between_loss_setter set_between_loss; vf_far_robust_setter set_far_robust; vf_far_loss_getter get_far_loss; };
 
 struct vf_graph {
     vf_engine* eng = nullptr;
@@ -41,6 +45,11 @@ struct vf_graph {
     // factor is added (vf_graph_robust.cpp hands it to vf_add_between_, which writes it under graph_mutex; a solve reads it under graph_mutex too,
     // in its take, with the factors; vf_graph.cpp never names the engine call), and nothing is called
     vf_between_loss_setter set_between_loss = nullptr;
+    // ... and how it sends a far list whose entries carry losses, and reads the losses back with the list after a marginalisation
+    // (robust_far below): set with set_between_loss, by the same hand, under the same rules
+    vf_far_robust_setter set_far_robust = nullptr;
+    vf_far_loss_getter get_far_loss = nullptr;
+    bool robust_far = false;       // vf_set_robust_far: a pair the band cannot hold may carry a loss (guarded by graph_mutex)
     // Between factors the band cannot hold -- wider than VF_MAX_BANDWIDTH keyframes, or a second one ending at a key (loop
     // closures; iSAM2 takes any pair of keys, GraphManager.cpp:83-88): handed to the engine as "far" factors
     // (vf_engine_set_extra_between) at every solve.  When the older key of one leaves the fixed-lag window the engine
@@ -81,9 +90,10 @@ struct vf_graph {
     bool err_valid = false;     // the engine holds the per-factor errors of the window as the last solve left it (vf_graph_errors.cpp)
 };
 
-// vf_add_between with a loss (vf_graph.cpp): VF_LOSS_NONE is vf_add_between itself; any other loss is for band factors only
+// vf_add_between with a loss (vf_graph.cpp): VF_LOSS_NONE is vf_add_between itself; any other loss is for band factors only unless
+// vf_set_robust_far has switched far losses on.  calls: the engine calls a loss needs (null with VF_LOSS_NONE), kept in the handle
 extern "C" int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36], int loss, double loss_k,
-                               vf_between_loss_setter setter);
+                               const vf_robust_calls* calls);
 extern "C" int vf_between_record_(const double q[4], const double t[3], const double cov[36], double rec[VF_BTW_RECORD]);   // vf_graph.cpp
 
 // key -> keyframe slot of the handle's one window, and the oldest key still in it

@@ -250,6 +250,9 @@ struct View {
     // they were (the wildfire threshold of iSAM2; 0 = to the bit).
     int inc_on;         // 0: off.  != 0: K1 / K2 / K3 work from inc_k[w] on (0 elsewhere in the library)
     int inc_prior;      // != 0: the priors are linearised whatever inc_k says (the marginal prior has just changed: a slide)
+    int x_loss;         // != 0: this engine holds losses of far between factors -- two arrays behind the records of x_in (far_loss,
+                        // vf_far.hpp), made by the first list that carries one; the launcher of k_linearize_extra chooses by it.  (The
+                        // word was padding in front of inc_k: the argument block keeps its 712 bytes)
     int* inc_k;         // [B] first keyframe slot changed since the factorisation in Lp / ck was made (INT_MAX: none)
     int* inc_stop;      // [B] slot at which the last back substitution stopped: increments below it are as they were
     int* inc_from;      // [B] slot at which the last forward sweep started (diagnostics: vf_engine_incremental_info)
@@ -260,6 +263,12 @@ struct View {
 // this size; btw_loss / btw_loss_k sit in what were two padding words, which is why nm_W and x_max stand where they do)
 static_assert(sizeof(View) == 712, "View: the kernel argument block");
 __host__ __device__ inline int xl_ld(const View& v) { return 27 + 6 * v.x_max; }   // row stride of View::xl_U
+// Losses of the far between factors (View::x_loss): with n = B x_max entries, the allocation of x_in holds behind its n records the
+// parameters k (n doubles, from far_loss_k_at) and the loss ids (n ints, from far_loss_id_at, counted in doubles); far_loss_words: all
+// of it, in doubles.  An engine without far losses has the records alone.
+__host__ __device__ inline size_t far_loss_k_at(size_t n) { return n * BTW_IN; }
+__host__ __device__ inline size_t far_loss_id_at(size_t n) { return n * (BTW_IN + 1); }
+__host__ __device__ inline size_t far_loss_words(size_t n) { return n * (BTW_IN + 1) + (n + 1) / 2; }
 // Do the dense far systems (the Woodbury combine, the marginals' C, the joint marginalisation) take their device-memory form?  The
 // form follows the slots IN USE, not the engine's capacity: an engine made for 32 far factors that holds eight or fewer takes the
 // LDS forms -- the lists are compact, so what is there sits in the first slots -- and gets the same bits either way.

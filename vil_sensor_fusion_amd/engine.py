@@ -163,13 +163,32 @@ class Engine:
         assert a.size == b.size == r.shape[0]
         check(self._l.vf_engine_set_between(self._h, window, a.size, _i(a), _i(b), _d(r)))
 
-    def set_extra_between(self, window, a, b, rec):
-        """far between factors of a window (any pair of keyframes; vf_engine_set_extra_between): REPLACES the window's list"""
+    def set_extra_between(self, window, a, b, rec, loss=None, k=None):
+        """far between factors of a window (any pair of keyframes; vf_engine_set_extra_between): REPLACES the window's list.
+        loss: a robust loss for the entries (vf_engine_set_extra_between_robust), by name or id (robust.py), one for all or one
+        each; k likewise (None: robust.DEFAULT_K).  The losses belong to the list: a call without them clears them."""
         a = np.ascontiguousarray(a, dtype=np.int32)
         b = np.ascontiguousarray(b, dtype=np.int32)
         r = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, BTW_RECORD)
         assert a.size == b.size == r.shape[0]
-        check(self._l.vf_engine_set_extra_between(self._h, window, a.size, _i(a), _i(b), _d(r)))
+        if loss is None:
+            check(self._l.vf_engine_set_extra_between(self._h, window, a.size, _i(a), _i(b), _d(r)))
+            return
+        from . import robust
+        ids = [robust.loss_id(x) for x in (loss if isinstance(loss, (list, tuple, np.ndarray)) else [loss] * a.size)]
+        ks = [robust.DEFAULT_K.get(i, 0.0) for i in ids] if k is None else np.broadcast_to(np.asarray(k, dtype=np.float64), (a.size,))
+        li = np.ascontiguousarray(ids, dtype=np.int32)
+        kk = np.ascontiguousarray(ks, dtype=np.float64)
+        assert li.size == a.size == kk.size
+        check(self._l.vf_engine_set_extra_between_robust(self._h, window, a.size, _i(a), _i(b), _d(r), _i(li), _d(kk)))
+
+    def get_extra_between_loss(self, window):
+        """(loss ids, k), max_far_factors entries each, in the order of get_extra_between; none and 0 behind the list's end and
+        on an engine that was never given a far loss"""
+        cap = self.opts.max_far_factors or MAX_FAR
+        li, kk = np.zeros(cap, dtype=np.int32), np.zeros(cap)
+        check(self._l.vf_engine_get_extra_between_loss(self._h, window, _i(li), _d(kk)))
+        return li, kk
 
     def get_extra_between(self, window):
         """(a, b, records, made linear by a marginalisation or re-anchored by a slide without one so far, dropped without a
@@ -455,6 +474,14 @@ class Engine:
     def read_between_lin(self, window, k0, n, which=0):
         r, Ja, Jb = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
         check(self._l.vf_engine_read_between_lin(self._h, window, which, k0, n, _d(r), _d(Ja), _d(Jb)))
+        return r, Ja, Jb
+
+    def read_extra_lin(self, window, which=0):
+        """(r (X, 6), Ja (X, 6, 6), Jb (X, 6, 6)) of the window's far list, X = max_far_factors entries in the order of
+        get_extra_between; zeros where the list holds none; an entry with a loss in its square-root form"""
+        cap = self.opts.max_far_factors or MAX_FAR
+        r, Ja, Jb = np.zeros((cap, 6)), np.zeros((cap, 6, 6)), np.zeros((cap, 6, 6))
+        check(self._l.vf_engine_read_extra_lin(self._h, window, which, _d(r), _d(Ja), _d(Jb)))
         return r, Ja, Jb
 
     def read_normal(self, window, k0, n):

@@ -31,7 +31,7 @@ class GraphManager:
     def __init__(self, imu_params=CARLA_IMU, capacity=4096, lag=0, iterations=5, device=0,
                  prior_sigma=None, rel_tol=None, abs_tol=None, reference_compat=False, relin_threshold=None,
                  cold_start=False, fixed_capacity=False, incremental=False, wildfire=None, min_model_fidelity=None,
-                 synchronous_staging=False, max_far_factors=None, far_covariance=False):
+                 synchronous_staging=False, max_far_factors=None, far_covariance=False, robust_far=False):
         """iterations: LM trials per solve at most; a solve stops earlier once a trial changes the cost by <= abs_tol or
         <= rel_tol * cost (defaults 1e-5 / 1e-5, gtsam::LevenbergMarquardtParams; 0 / 0: always `iterations` trials)."""
         self._l = _lib.lib()
@@ -65,9 +65,13 @@ class GraphManager:
         # far_covariance: marginalCovariance and the covariance callbacks take loop closures alive into account (a low-rank
         # downdate) instead of refusing while one is alive
         o.far_covariance = int(bool(far_covariance))
+        # robust_far: addBetweenFactor(..., robust=...) is accepted on a pair the band cannot hold (a loop closure), which then
+        # carries its loss as a far factor; without it such a pair is refused (vf_set_robust_far, once the handle exists)
         self._h = C.c_void_p()
         self._robust = {}          # end key -> (loss id, k) of the robust band factors added (between_weights)
         check(self._l.vf_create(C.byref(p), C.byref(o), C.byref(self._h)))
+        if robust_far:
+            check(self._l.vf_set_robust_far(self._h, 1))
         self._cbs = []
 
     def close(self):
@@ -105,7 +109,8 @@ class GraphManager:
 
     def addBetweenFactor(self, previousKey, currentKey, betweenPose, noiseCovariance, robust=None):
         """robust: None (noiseModel::Gaussian::Covariance, as the reference's sensor managers build it), or a loss over that
-        Gaussian (noiseModel::Robust) as ("huber", 1.345) / ("cauchy", k) / ("geman_mcclure", k) -- band factors only
+        Gaussian (noiseModel::Robust) as ("huber", 1.345) / ("cauchy", k) / ("geman_mcclure", k) -- band factors only, unless the
+        manager was made with robust_far=True, which takes it on loop closures too
         (vf_add_between_robust; robust.py has the names and the losses' arithmetic)"""
         q = np.ascontiguousarray(betweenPose[0], dtype=np.float64)
         t = np.ascontiguousarray(betweenPose[1], dtype=np.float64)
@@ -131,6 +136,22 @@ class GraphManager:
             if eb[i] >= 0.0:
                 loss, k = self._robust.get(key0 + i, (robust_losses.NONE, 0.0))
                 out[i] = robust_losses.weight_from_error(loss, k, eb[i])
+        return out
+
+    def far_weights(self):
+        """per nonlinear far factor (loop closure) alive after the last solve: (previousKey, currentKey, loss name, k, weight) --
+        the weight rho'/s as between_weights gives it for band factors, from the factor's error alone (vf_get_far_factors:
+        vf_engine_read_far_errors through robust.weight_from_error); 1 for a Gaussian closure and for an inlier"""
+        n = C.c_int()
+        cap = 32        # VF_MAX_FAR_LIMIT
+        a, b = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+        li, kk, err = np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(cap)
+        check(self._l.vf_get_far_factors(self._h, C.byref(n), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                         li.ctypes.data_as(C.c_void_p), _d(kk), _d(err)))
+        out = []
+        for i in range(n.value):
+            w = robust_losses.weight_from_error(int(li[i]), float(kk[i]), err[i]) if err[i] >= 0.0 else float("nan")
+            out.append((int(a[i]), int(b[i]), robust_losses.NAMES[int(li[i])], float(kk[i]), w))
         return out
 
     def addFactor(self, key, record190):

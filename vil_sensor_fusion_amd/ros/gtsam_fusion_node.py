@@ -22,6 +22,8 @@ sensor_manager.SensorManager.innovation_gate).
 sensors/<name>/robust_loss and robust_k (absent by default: Gaussian factors, as the reference; "huber" / "cauchy" / "geman_mcclure" and
 the loss's parameter in standard deviations of the whitened residual, default robust.DEFAULT_K -- noiseModel::Robust over the
 sensor's Gaussian, sensor_manager.SensorManager.robust; with innovation_gate_chi2 the gate decides first).
+solver/robust_far (default false: a factor the band cannot hold -- a loop closure -- takes no loss and is added as a Gaussian factor;
+true: it carries the sensor's loss as a far factor, GraphManager(robust_far=True)).
 sensors/<name>/odom_covariance_order ("reference" by default: the message's twist covariance is copied as the reference copies
 it; "ros": it is read as (x, y, z, rx, ry, rz) and permuted to the factor's [rot, trans] -- what a covariance
 remapped by the odometry filter's ~filter/mode = deweight needs to mean what it says; use_odom_covariance only).
@@ -73,7 +75,10 @@ class FusionNode:
                                                    # loop closures / wide between factors alive at once (32, the library's default and its limit, unless set lower)
                                                    max_far_factors=(int(P("solver/max_far_factors", 0)) or None),
                                                    # covariances with loop closures alive (~publish_covariance; default false: none then)
-                                                   far_covariance=bool(P("solver/far_covariance", False)))
+                                                   far_covariance=bool(P("solver/far_covariance", False)),
+                                                   # a sensor's robust_loss also on factors the band cannot hold (loop closures; default
+                                                   # false: those are refused and the sensor manager adds them as Gaussian factors)
+                                                   robust_far=bool(P("solver/robust_far", False)))
         x0 = rospy.get_param("~solver/initial_state", [])
         if graph_manager is None and len(x0) == 16:
             self.graph.setInitialState(x0)
