@@ -405,7 +405,8 @@ int vf_engine_propagate_status(vf_engine* e, float* h2d_ms, float* kernel_ms);
  *   - S = I + Ja Sigma_aa Ja^T + Ja C^T Jb^T + Jb C Ja^T + Jb Sigma_jj Jb^T; nis = r^T S^-1 r (chi-square, 6 degrees of freedom
  *     when the measurement is consistent); nis_measurement = r^T r, twice the factor's error at the predicted state.
  * REACH: a = i or a = i-1.  An older keyframe would need the covariance of an earlier pose against a later full state, which the
- * selected inversion does not keep: such a window gets VF_GATE_OUT_OF_REACH, not an error.
+ * selected inversion does not keep: such a window gets VF_GATE_OUT_OF_REACH, not an error (two solved keyframes any distance apart:
+ * vf_engine_gate_closures below).
  * chi2_threshold: rejected is set when nis exceeds it and it is finite and positive (else nothing is rejected).  The 6-dof quantiles
  * a caller is likely to pass: 16.81 at 99 %, 22.46 at 99.9 %.
  * VF_GATE_FROM_ESTIMATE: as VF_PROPAGATE_FROM_ESTIMATE.
@@ -438,6 +439,61 @@ int vf_engine_read_gate(vf_engine* e, int window, vf_gate_result* out);
 int vf_engine_read_gate_all(vf_engine* e, int32_t* status, double* nis);
 /* ... and the last call's copy / kernel times from HIP events (synchronises on the kernel's event) */
 int vf_engine_gate_status(vf_engine* e, float* h2d_ms, float* kernel_ms);
+/* Loop-closure gate: the same test for a between factor on ANY two solved keyframes of a window, before it is added (no reference
+ * code; GTSAM users build it on Marginals::jointMarginalCovariance of the two keys).  n candidates, at most VF_CLOSURE_GATE_MAX on
+ * one window: candidate i is a BetweenFactor<Pose3> from slot a[i] to slot b[i] of window window[i], lo <= a < b < hi, with the
+ * record rec28[i] that vf_engine_set_between takes (a[i] = -1: none).
+ *   - r, Ja, Jb: the factor's whitened residual and Jacobians at T_a and T_b of the current buffer; xi = Log(Z^-1 T_a^-1 T_b);
+ *   - Sigma_J: the 12 x 12 joint covariance of the two poses (tangent order of vf_engine_read_marginals, a first), of
+ *     Sigma = (J^T J + L)^-1 at lambda = 0 of EVERYTHING the window holds: the band, the marginal prior, the far factors alive at the
+ *     weights their losses give them at this linearisation, the linear far factor -- far factors are always taken in (a loop-closure
+ *     gate that ignores the closures already made has no meaning): there is no flag like VF_MARGINALS_FAR to ask for it;
+ *   - S = I + [Ja Jb] Sigma_J [Ja Jb]^T, nis = r^T S^-1 r, nis_measurement = r^T r, rejected as vf_engine_gate_tail sets it.
+ * Sigma_J comes from columns of the inverse, not from the selected inversion: the call makes the undamped factorisation at the
+ * current states itself (the one vf_engine_marginals_ex makes) and solves the six unit columns of every distinct candidate
+ * keyframe on its panels, from the window's smallest such keyframe to its end; with far factors alive the blocks take the low-rank
+ * downdate of VF_MARGINALS_FAR.  No vf_engine_marginals_ex is needed before it, and the covariances that call left are neither read
+ * nor written, nor is their validity changed.  A candidate's record and Sigma_J do not depend on what else the call holds.
+ * Side effects, those of vf_engine_marginals_ex without its results: the current buffer's linearisation is rewritten (same bits), H,
+ * g and the panels are overwritten, the engine is left cold; states, the LM state, the result block, factor errors, the propagation
+ * and vf_engine_gate_tail's result are untouched.  Enqueues; scratch and result buffers of the call's own, made by the first call
+ * and grown on demand (an engine that never calls it holds none).
+ * Statuses (VF_GATE_*): OK; NONE (a = -1); OUT_OF_REACH (a >= b, or an end outside [lo, hi)); NO_COVARIANCE (the window's
+ * factorisation or its far system failed, or S has a non-positive pivot: nis is NaN, xi and nis_measurement are valid).
+ * VF_ERR_CAPACITY: more than VF_CLOSURE_GATE_MAX candidates on one window (nothing is touched: the last result stays readable);
+ * VF_ERR_INVALID: a null pointer, n < 0, a time-sharded engine; VF_ERR_BAD_KEY: a window that does not exist. */
+#define VF_CLOSURE_GATE_MAX 4
+/* One candidate's result: nis, nis_measurement and xi are NaN unless the status says otherwise.  A plain output struct as
+ * vf_gate_result: the caller fills struct_size, the library writes no byte beyond it.  Grows at the end only. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t status;            /* VF_GATE_* */
+    int32_t rejected;          /* 1: status is VF_GATE_OK and nis > chi2_threshold */
+    int32_t window;
+    int32_t a, b;              /* as given */
+    double nis;
+    double nis_measurement;
+    double xi[6];
+} vf_closure_gate_result;
+int vf_engine_gate_closures(vf_engine* e, int n, const int32_t* window, const int32_t* a, const int32_t* b, const double* rec28,
+                            double chi2_threshold);
+/* ... with flags.  VF_GATE_FROM_ESTIMATE: T_a and T_b, hence r, Ja, Jb and xi, are those of the trial buffer -- the ESTIMATE of a
+ * reference-compat engine, whose current buffer is the linearisation point theta -- as vf_engine_gate_tail takes its newer end from
+ * it; Sigma_J is of the linearisation at the current buffer either way, as every covariance of such an engine is.  flags = 0 is
+ * vf_engine_gate_closures.  Unknown flags: VF_ERR_INVALID.  When no candidate of the call can be tested (every one NONE or
+ * OUT_OF_REACH) nothing is factored and the engine is left as warm as it was: only the records are written. */
+int vf_engine_gate_closures_ex(vf_engine* e, int n, const int32_t* window, const int32_t* a, const int32_t* b, const double* rec28,
+                               double chi2_threshold, unsigned flags);
+/* ... read back candidate `index` of the last call (synchronises); joint_cov144: Sigma_J row-major, or NULL (NaN unless the status is
+ * VF_GATE_OK or S was not positive definite).  VF_ERR_INVALID: no vf_engine_gate_closures since the engine was made, compacted or
+ * grown; VF_ERR_BAD_KEY: index at or beyond the number of candidates of that call. */
+int vf_engine_read_closure_gate(vf_engine* e, int index, vf_closure_gate_result* out, double* joint_cov144);
+/* ... every candidate's status and nis, n entries each, in one synchronisation; either pointer may be NULL */
+int vf_engine_read_closure_gate_all(vf_engine* e, int32_t* status, double* nis);
+/* ... the last call's copy / kernel times from HIP events (synchronises on the last kernel's event; the kernel time holds the
+ * factorisation too), and the bytes of device memory the gate holds: its scratch and its results (0 and 0 on an engine that never
+ * called it).  Any pointer may be NULL */
+int vf_engine_closure_gate_status(vf_engine* e, float* h2d_ms, float* kernel_ms, uint64_t* scratch_bytes, uint64_t* result_bytes);
 
 /* ---- hot-path stages (asynchronous on the engine's HIP stream) ---- */
 /* K1+K2+priors: residual + whitened Jacobian of every factor, at the current (which=0) or
@@ -1002,7 +1058,7 @@ int vf_predict_state(vf_graph* g, double time, double q[4], double t[3], double 
  * cur_key: a reserved key in [solved key, current key]; the IMU steps are those of the queued, not yet solved factors up to
  * cur_key, concatenated as vf_predict_state does, nothing is cut from the IMU buffer; cur_key = the solved key means no steps.
  * prev_key: the last solved key or the one before it, still in the window -- anything else returns VF_OK with status
- * VF_GATE_OUT_OF_REACH.  If the last solve has no covariances yet they are computed first: VF_MARGINALS_TAIL while no far factor is
+ * VF_GATE_OUT_OF_REACH (two solved keys any distance apart: vf_gate_closure below).  If the last solve has no covariances yet they are computed first: VF_MARGINALS_TAIL while no far factor is
  * alive (vf_get_marginal_covariance, the scores and the covariance callbacks compute the full ones when they are asked), otherwise
  * as vf_predict_state does, vf_graph_opts.far_covariance honoured and its refusals applied.  reference_compat handles gate from
  * the estimate.  Nothing is consumed or staged: vf_add_between + vf_solve after a gate give the bits of a handle that never gated.
@@ -1010,6 +1066,19 @@ int vf_predict_state(vf_graph* g, double time, double q[4], double t[3], double 
  * vf_predict_state (never from inside a callback); VF_ERR_BAD_KEY also for keys not reserved in order or a cur_key solved already. */
 int vf_gate_between(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q[4], const double t[3], const double cov36[36],
                     double chi2_threshold, vf_gate_result* out);
+/* The same test of a LOOP CLOSURE before vf_add_between takes it: a between factor on two solved keys of the window, any distance
+ * apart (vf_engine_gate_closures on the handle's window; its comment has the quantity).  q, t, cov36: what vf_add_between would be
+ * given -- the record is built and validated by the same routine, with the same error codes.  Both keys must be solved and still in
+ * the window: anything else returns VF_OK with status VF_GATE_OUT_OF_REACH (an end that is reserved but not solved yet is
+ * vf_gate_between's to test).  Far factors alive -- the closures already made -- are ALWAYS part of the covariance, whatever
+ * vf_graph_opts.far_covariance says: a loop-closure gate that ignores the closures already made has no meaning.  The covariances
+ * the handle keeps (vf_get_marginal_covariance, vf_gate_between) are neither used nor voided.  reference_compat handles gate from
+ * the estimate (VF_GATE_FROM_ESTIMATE: both ends are solved keys, so both poses are the estimate's).  Nothing is consumed or staged: vf_add_between + vf_solve
+ * after a gate give the bits of a handle that never gated.  out->a, out->b: the keys' slots in the window.  joint_cov144: the 12 x 12
+ * joint covariance of the two poses (prev_key first), or NULL.  Locks and refusals as vf_gate_between: never call it from inside a
+ * callback. */
+int vf_gate_closure(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q[4], const double t[3], const double cov36[36],
+                    double chi2_threshold, vf_closure_gate_result* out, double* joint_cov144);
 /* the callback of vf_set_callback plus the marginal covariance of the solved keyframe */
 typedef void (*vf_cov_callback)(void* user, double time, const double q[4], const double t[3], const double v[3],
                                 const double bias[6], const double cov225[225]);

@@ -78,6 +78,12 @@ class GateResultC(C.Structure):
                 ("nis", C.c_double), ("nis_measurement", C.c_double), ("xi", C.c_double * 6), ("state16", C.c_double * 16)]
 
 
+class ClosureGateResultC(C.Structure):
+    """one candidate's loop-closure test (include/vilfusion.h vf_closure_gate_result); the caller fills struct_size"""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("rejected", C.c_int32), ("window", C.c_int32),
+                ("a", C.c_int32), ("b", C.c_int32), ("nis", C.c_double), ("nis_measurement", C.c_double), ("xi", C.c_double * 6)]
+
+
 CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                        C.POINTER(C.c_double), C.POINTER(C.c_double))
 
@@ -97,6 +103,7 @@ PROPAGATE_FROM_ESTIMATE = 2  # ... start from the trial buffer's state, the esti
 GATE_FROM_ESTIMATE = 2       # vf_engine_gate_tail: as PROPAGATE_FROM_ESTIMATE (VF_GATE_FROM_ESTIMATE)
 GATE_OK, GATE_NONE, GATE_OUT_OF_REACH, GATE_DEGENERATE, GATE_NO_COVARIANCE = 0, 1, 2, 3, 4     # vf_gate_result.status (VF_GATE_*)
 GATE_STATUS = ("ok", "none", "out_of_reach", "degenerate", "no_covariance")
+CLOSURE_GATE_MAX = 4         # candidates vf_engine_gate_closures takes on one window (VF_CLOSURE_GATE_MAX)
 # quantiles of the chi-square distribution with 6 degrees of freedom: thresholds on the gate's nis (scipy.stats.chi2.ppf(q, 6))
 CHI2_6_99, CHI2_6_999 = 16.81, 22.46
 SCORE_COVARIANCE, SCORE_INFORMATION = 0, 1     # vf_engine_marginal_scores / vf_get_degeneracy_scores: which of the two is scored
@@ -125,6 +132,7 @@ SYMBOLS = [
     "vf_engine_preintegrate", "vf_engine_get_imu", "vf_engine_ingest_tail", "vf_engine_ingest_status",
     "vf_engine_propagate_tail", "vf_engine_read_propagated", "vf_engine_propagate_status",
     "vf_engine_gate_tail", "vf_engine_read_gate", "vf_engine_read_gate_all", "vf_engine_gate_status",
+    "vf_engine_gate_closures", "vf_engine_gate_closures_ex", "vf_engine_read_closure_gate", "vf_engine_read_closure_gate_all", "vf_engine_closure_gate_status",
     "vf_engine_marginalize", "vf_engine_drop_oldest", "vf_engine_read_marginal", "vf_engine_compact", "vf_engine_grow",
     "vf_engine_set_stream", "vf_engine_set_shard", "vf_engine_shard_info", "vf_engine_solve_local",
     "vf_engine_solve_global", "vf_engine_reset_lambda",
@@ -134,7 +142,7 @@ SYMBOLS = [
     "vf_engine_isam_step", "vf_engine_predict_from_estimate", "vf_engine_get_estimate", "vf_engine_incremental_info", "vf_engine_set_async", "vf_engine_read_result", "vf_engine_marginalize_ahead",
     "vf_graph_default_opts", "vf_graph_default_opts_sized", "vf_create", "vf_destroy", "vf_add_imu", "vf_reserve_node",
     "vf_add_between", "vf_solve", "vf_get_state", "vf_get_bias", "vf_most_recent_pose_time",
-    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_get_far_factors", "vf_predict_state", "vf_gate_between", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
+    "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_get_far_factors", "vf_predict_state", "vf_gate_between", "vf_gate_closure", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
     "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged", "vf_graph_get_staged_loss", "vf_add_between_robust", "vf_set_robust_far",
     "vf_degeneracy_batch", "vf_degeneracy_spectrum_batch", "vf_degeneracy_scores_batch", "vf_dopt_filter_f32", "vf_degeneracy_remap_batch",
 ]
@@ -163,6 +171,9 @@ def lib():
         l.vf_engine_gate_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint]
         l.vf_predict_state.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.vf_gate_between.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        l.vf_engine_gate_closures.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+        l.vf_engine_gate_closures_ex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint]
+        l.vf_gate_closure.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         l.vf_get_degeneracy_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.c_int, C.c_void_p]
         l.vf_engine_factor_errors.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
         l.vf_get_factor_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

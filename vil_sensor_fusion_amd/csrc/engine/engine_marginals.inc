@@ -19,6 +19,29 @@ constexpr size_t FARCOV_BUDGET = (size_t)1 << 30;
 // VF_MARGINALS_TAIL: the selected inversion stops after the last two keyframes of every window -- what the innovation gate reads
 // (engine/engine_gate.inc).  sig_lo says so, and every reader's range check refuses what was not computed.
 constexpr int MARGINALS_TAIL_DEPTH = 2;
+// The front half of vf_engine_marginals_ex, which vf_engine_gate_closures (engine/engine_closure.inc) shares: the linearisation at
+// the current states, the far factors' too where any is alive (e->x_used, recounted by the caller), and the undamped sweep of
+// every window whole; `a` is the view it ran on.  zero / failed / ones: [B] each -- a zero lambda, the failure flags (cleared
+// here, set by the sweep) and all-ones `fresh` flags, the caller's own.
+static int factor_undamped(vf_engine* e, double* zero, int* failed, int* ones, vf::View* out) {
+    e->mem.rewritten();
+    // undamped, every window assembled and swept whole -- whether or not the termination rule has finished it, whatever form the
+    // engine's solves take (they may be partitioned)
+    const vf::View a = vf::undamped_whole(e->v, zero, failed, ones);
+    HIPCHK(hipMemsetAsync(failed, 0, (size_t)e->v.B * sizeof(int), e->stream));
+    // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
+    vf::launch_linearize(a, 0, e->stream);
+    if (e->x_used > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
+    // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3.  The plan
+    // is the one the same engine without far factors would have: far factors veto the assembling sweep for the SOLVE (its Woodbury
+    // columns read H and g), but they never enter the band and the downdate reads only the panels -- so a window without far
+    // factors gets the bits it gets from an engine that has none, on batch engines that assemble as well
+    const vf::SolvePlan plan = vf::solve_plan(solve_inputs(e, false));
+    if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
+    vf::launch_band_factor(a, plan, e->stream);
+    *out = a;
+    return VF_OK;
+}
 int vf_engine_marginals(vf_engine* e) { return vf_engine_marginals_ex(e, 0); }
 int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     if (!e) return fail(VF_ERR_INVALID, "engine is null");
@@ -56,21 +79,8 @@ int vf_engine_marginals_ex(vf_engine* e, unsigned flags) {
     }
     // allocated on first use as sig is (G x 624 B): only engines that ask for the nav_msgs records hold them
     if (pose) HIPCHK(e->pm_cov.ensure(G * (36 + 36 + 6) * sizeof(double) + 2 * B * sizeof(int) + 256));
-    e->mem.rewritten();
-    // undamped, every window assembled and swept whole -- whether or not the termination rule has finished it, whatever form the
-    // engine's solves take (they may be partitioned)
-    const vf::View a = vf::undamped_whole(e->v, e->sig_zero(), e->sig_fail(), e->sig_ones());
-    HIPCHK(hipMemsetAsync(e->sig_fail(), 0, B * sizeof(int), e->stream));
-    // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
-    vf::launch_linearize(a, 0, e->stream);
-    if (m > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
-    // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3.  The plan
-    // is the one the same engine without far factors would have: far factors veto the assembling sweep for the SOLVE (its Woodbury
-    // columns read H and g), but they never enter the band and the downdate reads only the panels -- so a window without far
-    // factors gets the bits it gets from an engine that has none, on batch engines that assemble as well
-    const vf::SolvePlan plan = vf::solve_plan(solve_inputs(e, false));
-    if (plan.factor == vf::Sweep::split) vf::launch_assemble(a, e->stream);
-    vf::launch_band_factor(a, plan, e->stream);
+    vf::View a{};
+    if (int rc = factor_undamped(e, e->sig_zero(), e->sig_fail(), e->sig_ones(), &a)) return rc;
     vf::launch_selinv(a, e->sig_fail(), e->sig, tail ? MARGINALS_TAIL_DEPTH : 0, e->stream);
     for (int w0 = 0; w0 < e->v.B && m > 0; w0 += group) {
         vf::FarCov fc{};

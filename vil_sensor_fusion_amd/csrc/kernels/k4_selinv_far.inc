@@ -264,13 +264,17 @@ __global__ void __launch_bounds__(64) k_farcov_downdate(View v, FarCov fc, doubl
         out[e] -= s;
     }
 }
-void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStream_t s) {
+// Z = A^-1 U and R of the windows' far systems, without the downdate of sig (the loop-closure gate, kclosure.inc, reads Z and R itself)
+void launch_farcov_system(const View& v, const FarCov& fc, int nw, hipStream_t s) {
     const unsigned cb = (unsigned)((fc.m + 63) / 64);
     hipLaunchKernelGGL(k_farcov_rhs, dim3((unsigned)nw), dim3(64 * cb), 0, s, v, fc);
     hipLaunchKernelGGL(k_farcov_forward, dim3((unsigned)nw, cb), dim3(64), 0, s, v, fc);
     hipLaunchKernelGGL(k_farcov_back, dim3((unsigned)nw, cb), dim3(64), 0, s, v, fc);
     if (far_big_form(v, fc.slots)) hipLaunchKernelGGL(k_farcov_chol<true>, dim3((unsigned)nw), dim3(256), 0, s, v, fc);
     else hipLaunchKernelGGL(k_farcov_chol<false>, dim3((unsigned)nw), dim3(256), 0, s, v, fc);
+}
+void launch_farcov(const View& v, const FarCov& fc, int nw, double* sig, hipStream_t s) {
+    launch_farcov_system(v, fc, nw, s);
     hipLaunchKernelGGL(k_farcov_downdate, dim3((unsigned)v.M, (unsigned)nw), dim3(64), (size_t)FC_YROWS * (fc.m + 1) * sizeof(double), s,
                        v, fc, sig);
 }

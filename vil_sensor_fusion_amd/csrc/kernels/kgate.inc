@@ -35,6 +35,61 @@ struct GateSink {
     VF_DI void jb(int e, double x) { J[(e / 6) * 12 + 6 + e % 6] = x; }
 };
 
+// (e) of k_gate_between, shared with k_gate_closure (kclosure.inc): S = I + [Ja Jb] Sigma_J [Ja Jb]^T, symmetrised, from sJ (6 x 12) and
+// sJoint (12 x 12) in LDS; then on thread 0 S = L L^T, y = L^-1 r, nis = y^T y and m = r^T r.  The whole workgroup calls it (72 threads
+// at least; it synchronises, and sJ, sR, sJoint are complete when it is entered); nis, m and the value returned are thread 0's.
+// false: a pivot was not positive.
+VF_DI bool gate_nis(int tid, const double* sJ, const double* sR, const double* sJoint, double* sU, double* sSm, double& nis, double& m) {
+    if (tid < 72) {
+        const int r = tid / 12, c = tid - r * 12;
+        double x = 0.0;
+        for (int l = 0; l < 12; l++) x = fma(sJ[r * 12 + l], sJoint[l * 12 + c], x);
+        sU[tid] = x;
+    }
+    __syncthreads();
+    if (tid < 36) {
+        const int r = tid / 6, c = tid - r * 6;
+        double x = 0.0, y = 0.0;
+        for (int l = 0; l < 12; l++) {
+            x = fma(sU[r * 12 + l], sJ[c * 12 + l], x);
+            y = fma(sU[c * 12 + l], sJ[r * 12 + l], y);
+        }
+        sSm[tid] = (r == c ? 1.0 : 0.0) + 0.5 * (x + y);
+    }
+    __syncthreads();
+    bool spd = true;
+    nis = 0.0, m = 0.0;
+    if (tid == 0) {
+        double S[36], L[36], r6[6], y[6];
+#pragma unroll
+        for (int e = 0; e < 36; e++) S[e] = sSm[e];
+#pragma unroll
+        for (int e = 0; e < 6; e++) r6[e] = sR[e];
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            double d = S[c * 6 + c];
+#pragma unroll
+            for (int k = 0; k < c; k++) d = fma(-L[c * 6 + k], L[c * 6 + k], d);
+            if (!(d > 0.0)) spd = false;
+            const double lcc = sqrt(d), inv = 1.0 / lcc;
+#pragma unroll
+            for (int r = c + 1; r < 6; r++) {
+                double x = S[r * 6 + c];
+#pragma unroll
+                for (int k = 0; k < c; k++) x = fma(-L[r * 6 + k], L[c * 6 + k], x);
+                L[r * 6 + c] = x * inv;
+            }
+            double x = r6[c];
+#pragma unroll
+            for (int k = 0; k < c; k++) x = fma(-L[c * 6 + k], y[k], x);
+            y[c] = x * inv;
+            nis = fma(y[c], y[c], nis);
+            m = fma(r6[c], r6[c], m);
+        }
+    }
+    return spd;
+}
+
 __global__ void __launch_bounds__(256) k_gate_between(View v, const int* __restrict__ off, const double* __restrict__ steps, ImuCov prm,
                                                      const int* __restrict__ btw_a, const int* __restrict__ reach_lo,
                                                      const double* __restrict__ btw_rec, double threshold, int from_estimate,
@@ -151,53 +206,9 @@ __global__ void __launch_bounds__(256) k_gate_between(View v, const int* __restr
     }
     __syncthreads();
     // (e)
-    if (tid < 72) {
-        const int r = tid / 12, c = tid - r * 12;
-        double x = 0.0;
-        for (int l = 0; l < 12; l++) x = fma(sJ[r * 12 + l], sJoint[l * 12 + c], x);
-        sU[tid] = x;
-    }
-    __syncthreads();
-    if (tid < 36) {
-        const int r = tid / 6, c = tid - r * 6;
-        double x = 0.0, y = 0.0;
-        for (int l = 0; l < 12; l++) {
-            x = fma(sU[r * 12 + l], sJ[c * 12 + l], x);
-            y = fma(sU[c * 12 + l], sJ[r * 12 + l], y);
-        }
-        sSm[tid] = (r == c ? 1.0 : 0.0) + 0.5 * (x + y);
-    }
-    __syncthreads();
+    double nis, m;
+    const bool spd = gate_nis(tid, sJ, sR, sJoint, sU, sSm, nis, m);
     if (tid == 0) {
-        // S = L L^T, y = L^-1 r, nis = y^T y
-        double S[36], L[36], r6[6], y[6];
-#pragma unroll
-        for (int e = 0; e < 36; e++) S[e] = sSm[e];
-#pragma unroll
-        for (int e = 0; e < 6; e++) r6[e] = sR[e];
-        bool spd = true;
-        double nis = 0.0, m = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            double d = S[c * 6 + c];
-#pragma unroll
-            for (int k = 0; k < c; k++) d = fma(-L[c * 6 + k], L[c * 6 + k], d);
-            if (!(d > 0.0)) spd = false;
-            const double lcc = sqrt(d), inv = 1.0 / lcc;
-#pragma unroll
-            for (int r = c + 1; r < 6; r++) {
-                double x = S[r * 6 + c];
-#pragma unroll
-                for (int k = 0; k < c; k++) x = fma(-L[r * 6 + k], L[c * 6 + k], x);
-                L[r * 6 + c] = x * inv;
-            }
-            double x = r6[c];
-#pragma unroll
-            for (int k = 0; k < c; k++) x = fma(-L[c * 6 + k], y[k], x);
-            y[c] = x * inv;
-            nis = fma(y[c], y[c], nis);
-            m = fma(r6[c], r6[c], m);
-        }
         if (!spd) nis = qnan;
         o->xi[0] = xi.w.x; o->xi[1] = xi.w.y; o->xi[2] = xi.w.z; o->xi[3] = xi.u.x; o->xi[4] = xi.u.y; o->xi[5] = xi.u.z;
         o->struct_size = 0;

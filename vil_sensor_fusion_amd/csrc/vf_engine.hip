@@ -212,6 +212,17 @@ struct vf_engine : EngineHandle {
     vf::DeviceBuf<int> in_status;
     vf::DeviceBuf<double> prop_out;
     vf::DeviceBuf<char> gate_out;
+    // vf_engine_gate_closures (engine/engine_closure.inc): its argument block's channel; what its kernels write (records, then the
+    // joint covariances); the scratch of a group of windows (unit columns, and Z and C of the far systems); the zero lambda, failure
+    // flags and all-ones `fresh` flags of its undamped factorisation (the marginals' own live in sig, which this call never makes).
+    // All made by the first call: an engine that never gates closures holds none.  How many records there are to read is
+    // SolveMemory's to say (closure_gate_count)
+    vf::UploadChannel closure;
+    vf::DeviceBuf<char> cg_out;
+    vf::DeviceBuf<double> cg_scratch, cg_aux;
+    double* cg_zero() const { return cg_aux; }
+    int* cg_fail() const { return (int*)(cg_aux + v.B); }
+    int* cg_ones() const { return cg_fail() + v.B; }
     int ensure_ingest() {
         if (in_status) return VF_OK;
         HIPCHK(in_status.ensure(sizeof(int)));
@@ -445,6 +456,7 @@ extern "C" {
 #include "engine/engine_marginals.inc"
 #include "engine/engine_propagate.inc"
 #include "engine/engine_gate.inc"
+#include "engine/engine_closure.inc"
 #include "engine/engine_errors.inc"
 #include "engine/engine_robust.inc"
 }  // extern "C"

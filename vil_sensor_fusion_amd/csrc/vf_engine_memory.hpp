@@ -8,7 +8,8 @@
 // propagation (vf_engine_propagate_tail), which only a grown engine loses.  A seventh is a fact about the residuals rather than a
 // saving: whether the current buffer's whitened residuals are those of the current states, so that vf_engine_factor_errors may read
 // them as they lie (residuals_vouched), with the per-factor errors that call left (errors_valid).  An eighth is the innovation gate's result
-// (vf_engine_gate_tail: gate_valid), which a compacted or grown engine loses.  Every entry point of the engine
+// (vf_engine_gate_tail: gate_valid), which a compacted or grown engine loses; a ninth the loop-closure gate's (vf_engine_gate_closures:
+// closure_gate_count), lost the same way.  Every entry point of the engine
 // says what it did through one of the EVENTS below -- they are the only writers -- and asks through the QUERIES.
 #pragma once
 
@@ -87,9 +88,9 @@ class SolveMemory {
         warm_ = ahead_valid_ = res_current_ = false;
     }
     // the window was compacted: the covariance blocks stay in the slots they were computed for
-    void compacted() { rewritten(), covariances_started(), err_valid_ = gate_valid_ = false; }
+    void compacted() { rewritten(), covariances_started(), err_valid_ = gate_valid_ = false, closure_n_ = 0; }
     // the engine was grown: new arrays, nothing linearised in them yet, no covariances
-    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = err_valid_ = gate_valid_ = false; }
+    void grown() { rewritten(), covariances_started(), slid_ = redo_ = 0, prop_valid_ = prop_cov_ = err_valid_ = gate_valid_ = false, closure_n_ = 0; }
     // the marginal prior of the keyframe at `lo` was computed ahead of time / ... was put in place
     void stashed(int lo) { ahead_valid_ = true, ahead_lo_ = lo; }
     void stash_committed() { ahead_valid_ = false; }
@@ -121,6 +122,9 @@ class SolveMemory {
     // vf_engine_gate_tail left a result for every window in its own buffer.  It is of the call that wrote it: later solves leave
     // it, a compacted or grown engine loses it
     void gated() { gate_valid_ = true; }
+    // vf_engine_gate_closures left n records (and joint covariances) in its own buffer.  They are of the call that wrote them, as
+    // the tail gate's: later solves leave them, a compacted or grown engine loses them
+    void closure_gated(int n) { closure_n_ = n; }
 
     // ---- queries
     // keyframes at the window's end the next solve linearises again, 0: a cold solve (everything).  The launch sequence of
@@ -144,6 +148,8 @@ class SolveMemory {
     // the covariances are valid, but of every window's tail only (its last two keyframes)
     bool covariances_tail_only() const { return sig_valid_ && sig_tail_; }
     bool gate_valid() const { return gate_valid_; }
+    // records the last vf_engine_gate_closures left to be read (0: none)
+    int closure_gate_count() const { return closure_n_; }
 
   private:
     // what rewritten() does to the savings, for the events that are rewrites inside but say themselves what becomes of the residuals
@@ -162,6 +168,7 @@ class SolveMemory {
     bool prop_valid_ = false, prop_cov_ = false;
     bool res_current_ = false, err_valid_ = false;
     bool sig_tail_ = false, gate_valid_ = false;
+    int closure_n_ = 0;
 };
 
 }  // namespace vf

@@ -1,8 +1,8 @@
-// vf_graph_gate.cpp -- vf_gate_between: the innovation test of an odometry increment before vf_add_between takes it
-// (include/vilfusion.h).
+// vf_graph_gate.cpp -- vf_gate_between: the innovation test of an odometry increment before vf_add_between takes it; vf_gate_closure:
+// the same test of a loop closure between two solved keys (include/vilfusion.h).
 //
-// A translation unit of its own, beside vf_graph_predict.cpp and for its reason: it calls vf_engine_gate_tail / vf_engine_read_gate,
-// which the stand-in engine the host tests link vf_graph.cpp against does not have.  It reaches the handle through
+// A translation unit of its own, beside vf_graph_predict.cpp and for its reason: it calls vf_engine_gate_tail / vf_engine_read_gate
+// and vf_engine_gate_closures / vf_engine_read_closure_gate, which the stand-in engine the host tests link vf_graph.cpp against does not have.  It reaches the handle through
 // vf_graph_handle.hpp.
 #include <cstdarg>
 #include <cstdio>
@@ -79,6 +79,32 @@ int vf_gate_between(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const doub
     const int32_t off[2] = {0, (int32_t)(steps.size() / 7)};
     if (int rc = vf_engine_gate_tail(g->eng, off, steps.data(), &g->imu, &a, rec, chi2_threshold, flags)) return rc;
     return vf_engine_read_gate(g->eng, 0, out);
+}
+
+// Locks and refusals as vf_gate_between.  Nothing is consumed or staged, and no covariance the handle keeps is touched: the engine
+// call factors the window itself and writes buffers of its own (vf_engine_gate_closures), leaving the next solve the bits it would
+// have had.  Far factors alive are part of the covariance whatever vf_graph_opts.far_covariance says.
+int vf_gate_closure(vf_graph* g, uint64_t prev_key, uint64_t cur_key, const double q[4], const double t[3], const double cov36[36],
+                    double chi2_threshold, vf_closure_gate_result* out, double* joint_cov144) {
+    if (!g || !q || !t || !cov36 || !out) return gate_err(VF_ERR_INVALID, "null argument");
+    double rec[VF_BTW_RECORD];
+    if (int rc = vf_between_record_(q, t, cov36, rec)) return rc;
+    std::lock_guard<std::mutex> lk(g->graph_mutex);
+    if (g->current_key < 1) return gate_err(VF_ERR_INVALID, "vf_gate_closure: no solve yet: there is no window to test against");
+    if (prev_key >= cur_key || cur_key > g->current_key)
+        return gate_err(VF_ERR_BAD_KEY, "between factor keys (%llu, %llu) not reserved in order", (unsigned long long)prev_key, (unsigned long long)cur_key);
+    const uint64_t queued = g->imu_queue.size(), last_key = g->current_key;
+    std::lock_guard<std::mutex> sl(g->state_mutex);
+    if (!g->solved_once) return gate_err(VF_ERR_INVALID, "vf_gate_closure: no solve yet: there is no window to test against");
+    if (g->solved_key + queued != last_key)
+        return gate_err(VF_ERR_INVALID, "vf_gate_closure: the last solve failed and its factors are being queued again: solve first");
+    // both keys solved and still in the window; anything else is a status, which the engine gives for slots outside [lo, hi)
+    const int32_t w = 0;
+    const bool reach = cur_key <= g->solved_key && prev_key >= oldest_key(g);
+    const int32_t a = reach ? slot_of(g, prev_key) : -2, b = reach ? slot_of(g, cur_key) : -3;
+    const unsigned flags = (g->opts.reference_compat && g->solved_key > 0) ? VF_GATE_FROM_ESTIMATE : 0u;      // (as vf_gate_between)
+    if (int rc = vf_engine_gate_closures_ex(g->eng, 1, &w, &a, &b, rec, chi2_threshold, flags)) return rc;
+    return vf_engine_read_closure_gate(g->eng, 0, out, joint_cov144);
 }
 
 }  // extern "C"

@@ -21,6 +21,10 @@
 //   k_gate_between          the innovation test of a between factor before it enters the graph: chi-square of an odometry increment
 //                           against the solved window and the IMU since (no reference code: the estimation-theoretic counterpart
 //                           of the reference's degerate_odometry_filter)
+//   k_closure_rhs, k_closure_forward, k_closure_back, k_gate_closure
+//                           the same test of a loop closure: a between factor on any two solved keyframes of a window, against their
+//                           joint pose covariance from columns of the inverse (no reference code: Marginals::jointMarginalCovariance
+//                           of GTSAM and the chi-square test a caller builds on it)
 //   k_factor_errors, k_batch_health
 //                           every factor's chi-square error from the residuals the solve left, a summary per window, the
 //                           batch's health (no reference code: factor->error, graph.error, printErrors of GTSAM)
@@ -148,5 +152,6 @@ VF_DI void white9(const double (&R)[45], const double (&u)[9], double (&o)[9]) {
 #include "kernels/kpose.inc"
 #include "kernels/kprop.inc"
 #include "kernels/kgate.inc"
+#include "kernels/kclosure.inc"
 #include "kernels/kerr.inc"
 }  // namespace vf

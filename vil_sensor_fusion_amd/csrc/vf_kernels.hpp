@@ -370,6 +370,32 @@ constexpr size_t GATE_RECORD = 208;
 void launch_gate_between(const View& v, const int* off, const double* steps, const ImuCov& prm, const int* btw_a, const int* reach_lo,
                          const double* btw_rec, double threshold, int from_estimate, const double* sig, const int* sig_failed,
                          void* out, hipStream_t s);
+// Loop-closure gate (kernels/kclosure.inc; vf_engine_gate_closures): n candidates, at most CLOSURE_MAX on a window, each a between
+// factor from slot a[i] to slot b[i] of window window[i]; for the windows [w0, w0 + nw) of a group, whose column scratch X holds.
+// Written: out ([n] records of CLOSURE_RECORD bytes, vf_closure_gate_result's layout) and joint ([n][144]).  fc: the far systems of the
+// same windows (m = 0: no far factor alive anywhere), whose downdate of sig never runs.
+constexpr int CLOSURE_MAX = 4, CLOSURE_KEYS = 2 * CLOSURE_MAX;      // (= VF_CLOSURE_GATE_MAX; the distinct keyframes it makes at most)
+constexpr size_t CLOSURE_RECORD = 88;
+struct ClosureGate {
+    double* X;           // [nw][M][15][nc]   the unit columns: column q of window w0 + i at X + i xwin, entry (slot k, dof d) at (15 k + d) nc + q
+    const int* keys;     // [B][CLOSURE_KEYS] a window's distinct candidate keyframes, ascending; column 6 j + p: pose dof p of keys[j]
+    const int* nkeys;    // [B]
+    const int* cnt;      // [B]               candidates on the window
+    const int* idx;      // [B][CLOSURE_MAX]  ... and which of the call's they are
+    const int* a;        // [n]
+    const int* b;        // [n]
+    const int* status;   // [n]               GATE_OK: to be tested; else the status the host found (NONE, OUT_OF_REACH)
+    const double* rec;   // [n][BTW_IN]
+    int* failed;         // [B]               the call's failure flags: the window's sweep, or its far system C
+    char* out;
+    double* joint;
+    double threshold;
+    size_t xwin;
+    int w0, nc;
+    int from_estimate;   // T_a, T_b of the trial buffer (VF_GATE_FROM_ESTIMATE) instead of the current one; Sigma is of the current buffer either way
+};
+void launch_farcov_system(const View& v, const FarCov& fc, int nw, hipStream_t s);      // launch_farcov without the downdate
+void launch_closure_gate(const View& v, const ClosureGate& cg, const FarCov& fc, int nw, hipStream_t s);
 // Per-factor chi-square errors (kernels/kerr.inc; vf_engine_factor_errors): e = 0.5 |whitened residual|^2 of every factor of the
 // current buffer, -1 where a slot holds none, a summary per window and one block for the batch.  ErrSummary and BatchHealth are
 // the device twins of vf_consistency and vf_batch_health (include/vilfusion.h), byte for byte: the word of struct_size is unused.

@@ -311,6 +311,60 @@ class Engine:
         """waits for the last gate_tail, returns (h2d_ms, kernel_ms) of that call"""
         return self._status(self._l.vf_engine_gate_status)
 
+    def gate_closures(self, windows, a, b, records, threshold=None, from_estimate=False):
+        """Loop-closure gate (vf_engine_gate_closures): the chi-square (6 dof) of candidate between factors from slot a[i] to slot b[i]
+        of window windows[i] -- any two solved keyframes, lo <= a < b < hi; at most _lib.CLOSURE_GATE_MAX candidates on one window --
+        against their joint pose covariance in everything the window holds, far factors alive included.  Needs no marginals(): the
+        call factors the windows itself, and leaves the engine cold; states, the LM state and earlier marginals are untouched.
+        from_estimate (VF_GATE_FROM_ESTIMATE): the two poses are the trial buffer's, the estimate of a reference-compat engine.
+        Returns a list of dicts, one per candidate: status (a name of _lib.GATE_STATUS), rejected, window, a, b, nis,
+        nis_measurement, xi (6,) -- read back candidate by candidate, a synchronisation each (read_closure_gate_all: statuses and
+        nis of all in one); read_closure_joint(i) gives a candidate's 12 x 12 joint covariance."""
+        w = np.ascontiguousarray(windows, dtype=np.int32).ravel()
+        ka, kb = np.ascontiguousarray(a, dtype=np.int32).ravel(), np.ascontiguousarray(b, dtype=np.int32).ravel()
+        r = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, BTW_RECORD)
+        assert w.size == ka.size == kb.size == r.shape[0]
+        self._closure_n = 0
+        check(self._l.vf_engine_gate_closures_ex(self._h, int(w.size), _i(w), _i(ka), _i(kb), _d(r), 0.0 if threshold is None else float(threshold),
+                                                 _lib.GATE_FROM_ESTIMATE if from_estimate else 0))
+        self._closure_n = int(w.size)
+        return [self.read_closure_gate(i) for i in range(w.size)]
+
+    def read_closure_gate(self, index, joint=False):
+        """candidate `index` of the last gate_closures as a dict; joint=True adds joint_covariance (12, 12).  Synchronises."""
+        g = _lib.ClosureGateResultC()
+        g.struct_size = C.sizeof(g)
+        cov = np.zeros((12, 12)) if joint else None
+        check(self._l.vf_engine_read_closure_gate(self._h, index, C.byref(g), _d(cov) if joint else None))
+        out = dict(status=_lib.GATE_STATUS[g.status], rejected=bool(g.rejected), window=g.window, a=g.a, b=g.b, nis=g.nis,
+                   nis_measurement=g.nis_measurement, xi=np.array(g.xi[:]))
+        if joint:
+            out["joint_covariance"] = cov
+        return out
+
+    def read_closure_joint(self, index):
+        """the joint pose covariance (12, 12) of candidate `index` of the last gate_closures: [[S_aa, S_ab], [S_ba, S_bb]], pose dofs in
+        the tangent order of read_marginals; NaN unless the candidate was tested"""
+        return self.read_closure_gate(index, joint=True)["joint_covariance"]
+
+    def read_closure_gate_all(self, n=None):
+        """(status (n,) int32 of _lib.GATE_*, nis (n,)) of the last gate_closures of this object, which held n candidates (the count
+        is this object's own: the library writes that many entries, so another n is refused here); one synchronisation"""
+        held = getattr(self, "_closure_n", 0)
+        if n is not None and n != held:
+            raise ValueError(f"the last gate_closures held {held} candidates, not {n}")
+        n = held
+        s, v = np.zeros(max(n, 1), dtype=np.int32)[:n], np.zeros(max(n, 1))[:n]
+        check(self._l.vf_engine_read_closure_gate_all(self._h, _i(s), _d(v)))
+        return s, v
+
+    def closure_gate_status(self):
+        """waits for the last gate_closures; (h2d_ms, kernel_ms, scratch_bytes, result_bytes): its copy and kernel times (the
+        factorisation included) and the device memory the gate holds -- 0 and 0 on an engine that never called it"""
+        h, k, sb, rb = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        check(self._l.vf_engine_closure_gate_status(self._h, C.byref(h), C.byref(k), C.byref(sb), C.byref(rb)))
+        return h.value, k.value, sb.value, rb.value
+
     def get_imu(self, window, k0, n):
         r = np.zeros((n, IMU_RECORD))
         check(self._l.vf_engine_get_imu(self._h, window, k0, n, _d(r)))

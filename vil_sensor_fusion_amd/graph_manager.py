@@ -221,6 +221,24 @@ class GraphManager:
         return dict(status=_lib.GATE_STATUS[g.status], rejected=bool(g.rejected), nis=g.nis, nis_measurement=g.nis_measurement,
                     xi=np.array(g.xi[:]), state=np.array(g.state16[:]))
 
+    def gate_closure(self, previousKey, currentKey, betweenPose, noiseCovariance, threshold=None):
+        """The same test of a LOOP CLOSURE before addBetweenFactor takes it (vf_gate_closure): a between factor on two solved keys
+        of the window, any distance apart, against their joint pose covariance in everything the window holds -- closures already
+        made included, whatever far_covariance says.  Arguments as addBetweenFactor's; a key not solved yet or gone from the window
+        gives status "out_of_reach".  Returns what gate_between returns without the predicted state (both ends are solved
+        keyframes), plus joint_covariance (12, 12): [[S_aa, S_ab], [S_ba, S_bb]] of the two poses, previousKey first, tangent
+        order [rot, trans].  Consumes and stages nothing.  Not from inside a callback."""
+        q = np.ascontiguousarray(betweenPose[0], dtype=np.float64)
+        t = np.ascontiguousarray(betweenPose[1], dtype=np.float64)
+        cov = np.ascontiguousarray(noiseCovariance, dtype=np.float64).reshape(6, 6)
+        g = _lib.ClosureGateResultC()
+        g.struct_size = C.sizeof(g)
+        joint = np.zeros((12, 12))
+        check(self._l.vf_gate_closure(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q), _d(t), _d(cov),
+                                      0.0 if threshold is None else float(threshold), C.byref(g), _d(joint)))
+        return dict(status=_lib.GATE_STATUS[g.status], rejected=bool(g.rejected), nis=g.nis, nis_measurement=g.nis_measurement,
+                    xi=np.array(g.xi[:]), joint_covariance=joint)
+
     def degeneracy_scores(self, metric, subsets=("all", "trans", "rot"), information=False, key0=None, n=None):
         """One degeneracy metric (a name of degeneracy.ALL_METRICS) on `subsets` of the nav_msgs pose covariance (or,
         information=True, its inverse) of the solved keys key0 .. key0+n-1, computed on the device from the covariances of the
