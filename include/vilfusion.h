@@ -343,6 +343,43 @@ int vf_engine_set_extra_between_robust(vf_engine* e, int window, int n, const in
 /* ... read back: max_far_factors entries each (VF_MAX_EXTRA by default), in the order of vf_engine_get_extra_between; VF_LOSS_NONE
  * and k = 0 behind the list's end and on an engine without the arrays.  Either output may be NULL. */
 int vf_engine_get_extra_between_loss(vf_engine* e, int window, int32_t* loss, double* k);
+/* Absolute pose and position factors on keyframes (no reference code of its own: GraphManager::addBetweenFactor builds the sensor's
+ * absolute pose and discards it; a GTSAM user adds PriorFactor<Pose3>(X(b), Z, model) or GPSFactor(X(b), z, model)).  A factor on
+ * keyframe b ALONE, held in b's own between slot as a between factor from b - 1 whose first Jacobian is 36 exact zeros: J^T J gets
+ * J_u^T J_u on block (b, b) and exact zeros on the blocks of b - 1, J^T r gets J_u^T r_u on b, the cost 0.5 |r_u|^2 -- a unary
+ * factor's contribution, and everything behind K2 (assembly, every solve form, the LM decision, the refined and the incremental
+ * solve, the marginals, vf_engine_factor_errors, the marginalisation, both gates) reads the slot as it reads any other.
+ *   VF_ABSOLUTE_POSE      r = R Log(Z^-1 T_b), J_u = R J_r^-1(Log(Z^-1 T_b)): PriorFactor<Pose3>.  rec28 as for vf_engine_set_between:
+ *                         Z = [q wxyz, t] in the world frame of the states, then the 21 words of the upper-triangular square-root
+ *                         information R (R^T R = cov^-1), tangent order [rot, trans].
+ *   VF_ABSOLUTE_POSITION  e = t_b - z in the world frame, r = R3 e, J_u = R3 [0 | R_b] (the retraction moves t by R_b dp): GPSFactor.
+ *                         rec28 = [1, 0, 0, 0, z, R] with only the translation block of R's 21 words in use (R3, 3 x 3 upper
+ *                         triangular, R3^T R3 = cov^-1; vf_absolute_position_record builds it).  The factor fills rows 3..5 of the
+ *                         slot (r, Jb), the translation rows of a pose factor; rows 0..2 are exact zeros, and so is vf_engine_read_between_lin's
+ *                         Ja of either kind.
+ * The price is one factor per slot: keyframe b carries EITHER the band between factor that ends at it OR an absolute factor, and
+ * b - 1 must be inside the window when the factor is linearised (the oldest keyframe of a window cannot take one).  When keyframe
+ * b - 1 is marginalised the factor is absorbed into the marginal prior, at its linearisation of that moment -- one update earlier
+ * than a unary factor strictly must be; a slide that drops instead of marginalising drops it there.  Lever arms and the alignment
+ * of the sensor's datum with the world frame are the caller's.  vf_engine_factor_errors counts the factor in class
+ * VF_FACTOR_BETWEEN (its `a` reads b - 1): a position factor's 3 rows are judged against the 6-row threshold.
+ * The kind is an attribute of the SLOT, like the loss: vf_engine_set_absolute writes record, source b - 1, kind, and loss
+ * VF_LOSS_NONE (vf_engine_set_between_loss AFTER it gives the factor a robust loss: (alpha I + gamma r r^T) 0 = 0, so a Huber or
+ * Cauchy fix composes); vf_engine_set_between, vf_engine_ingest_tail and vf_engine_clear_between reset the slots they write to
+ * VF_ABSOLUTE_NONE; vf_engine_compact moves it with its slot, vf_engine_grow carries it, a slide leaves it with its slot.  The first
+ * call makes the per-slot array (and the loss arrays); an engine that never saw an absolute factor launches what it always has.
+ * A mutating call like vf_engine_set_between (on an asynchronous engine, n <= 4 enqueues and returns).  Refused with nothing
+ * touched: VF_ERR_INVALID for a kind other than the two, a null pointer, a time-sharded engine; VF_ERR_BAD_KEY for b - 1 < 0 or
+ * b >= capacity. */
+#define VF_ABSOLUTE_NONE 0
+#define VF_ABSOLUTE_POSE 1
+#define VF_ABSOLUTE_POSITION 2
+int vf_engine_set_absolute(vf_engine* e, int window, int n, const int32_t* b, const int32_t* kind, const double* rec28);
+/* ... of slots k0 .. k0+n-1 (synchronises); VF_ABSOLUTE_NONE everywhere on an engine without the array */
+int vf_engine_get_absolute(vf_engine* e, int window, int k0, int n, int32_t* kind);
+/* the record of a VF_ABSOLUTE_POSITION factor from the fix p and its 3 x 3 covariance (row-major; symmetrised).  Host only.
+ * VF_ERR_NOT_SPD: the covariance is not symmetric positive definite; VF_ERR_INVALID: a null pointer, p not finite. */
+int vf_absolute_position_record(const double p[3], const double cov9[9], double rec28[28]);
 
 /* K0: IMU preintegration on the device.  Factor i (keyframe k0+i) integrates
  * steps[step_off[i] .. step_off[i+1]) (7 doubles each: dt, acc xyz, gyro xyz) with bias estimate
@@ -994,6 +1031,29 @@ int vf_add_between_robust(vf_graph* g, uint64_t prev_key, uint64_t cur_key, cons
  * the factors added after it, the ones staged already keep what they have.  (A call, not a field of vf_graph_opts: the struct is
  * as every caller built against it knows it.)  VF_ERR_INVALID: null handle. */
 int vf_set_robust_far(vf_graph* g, int on);
+/* Absolute factors on the handle ("Absolute pose and position factors on keyframes" above): what a GTSAM user adds through the graph
+ * as PriorFactor<Pose3>(X(key), Z, Gaussian::Covariance(cov36)) / GPSFactor(X(key), p, Gaussian::Covariance(cov9)), with
+ * noiseModel::Robust over it when loss != VF_LOSS_NONE -- the absolute pose GraphManager::addBetweenFactor takes as poseEstimate and
+ * discards.  Z = (q_wxyz, t) and p live in the graph's WORLD frame (the frame of vf_set_initial_state): lever arms and the alignment of
+ * the sensor's datum with it are the caller's.  cov36 in tangent order [rot, trans]; cov9 row-major.
+ * The factor is staged like a between factor and applied at vf_solve; a fix for a key already solved and still resident is written
+ * at the next solve, as late band odometry is.  It takes the key's band slot (one factor per slot): the key must carry no band between
+ * factor, staged or resident, else VF_ERR_CAPACITY with nothing staged -- reserve a node of its own for a fix (vf_reserve_node at its
+ * stamp), as every sensor measurement of the reference does; such a key has an IMU factor and no odometry ending at it.  A later
+ * vf_add_between ending at the key becomes a far factor by the rule that holds for a second factor on a key.  key - 1 must still be in
+ * the window (VF_ERR_BAD_KEY; the oldest keyframe and key 0 cannot take one), also at the solve that applies it (dropped as late
+ * odometry is, and reported by that vf_solve).
+ * The factor is absorbed into the marginal prior when keyframe key - 1 is marginalised -- one update earlier than a unary factor
+ * strictly must be -- at its linearisation of that moment; a handle that drops instead of marginalising drops it at that moment.
+ * vf_graph_get_staged reports it as kind 4 (pose) or 5 (position) with key1 = key2 = key (a position's covariance in the translation
+ * block of cov36), vf_graph_get_staged_loss its loss; vf_get_factor_errors returns btw_prev_key = key for its slot: a factor on ONE
+ * key.  vf_get_consistency counts it in class VF_FACTOR_BETWEEN, so a position fix's 3 rows are judged against the 6-row threshold.
+ * VF_ERR_INVALID: a loss id outside 0..3, k not finite or <= 0, a null pointer, a rotation that is no quaternion; VF_ERR_NOT_SPD:
+ * the covariance. */
+int vf_add_absolute_pose(vf_graph* g, uint64_t key, const double q_wxyz[4], const double t[3], const double cov36[36], int loss, double k);
+int vf_add_absolute_position(vf_graph* g, uint64_t key, const double p[3], const double cov9[9], int loss, double k);
+/* the kinds (VF_ABSOLUTE_*) of the factors in the band slots of the solved keys key0 .. key0+n-1, as the last vf_solve left them */
+int vf_get_absolute_factors(vf_graph* g, uint64_t key0, int n, int32_t* kind);
 /* GraphManager::addFactor(const CombinedImuFactor&) (GraphManager.cpp:90-94): queue a READY-MADE preintegrated factor
  * X(key-1),V(key-1),X(key),V(key),B(key-1),B(key) as its 190-double record (layout at the top of this file; e.g. what
  * vf_get_imu_factor returns) instead of cutting one from the IMU buffer.  key must be the next key (current + 1); the

@@ -106,6 +106,7 @@ GATE_STATUS = ("ok", "none", "out_of_reach", "degenerate", "no_covariance")
 CLOSURE_GATE_MAX = 4         # candidates vf_engine_gate_closures takes on one window (VF_CLOSURE_GATE_MAX)
 # quantiles of the chi-square distribution with 6 degrees of freedom: thresholds on the gate's nis (scipy.stats.chi2.ppf(q, 6))
 CHI2_6_99, CHI2_6_999 = 16.81, 22.46
+ABSOLUTE_NONE, ABSOLUTE_POSE, ABSOLUTE_POSITION = 0, 1, 2     # vf_engine_set_absolute: the kind of the factor in a between slot (VF_ABSOLUTE_*)
 SCORE_COVARIANCE, SCORE_INFORMATION = 0, 1     # vf_engine_marginal_scores / vf_get_degeneracy_scores: which of the two is scored
 
 COV_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -121,6 +122,7 @@ SYMBOLS = [
     "vf_engine_set_range", "vf_engine_set_states", "vf_engine_get_states", "vf_engine_set_imu",
     "vf_engine_set_between", "vf_engine_clear_between", "vf_engine_set_extra_between", "vf_engine_get_extra_between", "vf_engine_get_linear_far", "vf_engine_set_prior",
     "vf_engine_set_between_loss", "vf_engine_get_between_loss", "vf_engine_set_extra_between_robust", "vf_engine_get_extra_between_loss",
+    "vf_engine_set_absolute", "vf_engine_get_absolute", "vf_absolute_position_record",
     "vf_engine_linearize", "vf_engine_assemble", "vf_engine_solve", "vf_engine_retract",
     "vf_engine_decide", "vf_engine_iterate", "vf_engine_slide", "vf_engine_predict",
     "vf_engine_sync", "vf_engine_graph_info", "vf_engine_solve_form",
@@ -143,7 +145,7 @@ SYMBOLS = [
     "vf_graph_default_opts", "vf_graph_default_opts_sized", "vf_create", "vf_destroy", "vf_add_imu", "vf_reserve_node",
     "vf_add_between", "vf_solve", "vf_get_state", "vf_get_bias", "vf_most_recent_pose_time",
     "vf_set_callback", "vf_get_marginal_covariance", "vf_get_degeneracy_scores", "vf_get_factor_errors", "vf_get_consistency", "vf_get_far_factors", "vf_predict_state", "vf_gate_between", "vf_gate_closure", "vf_set_covariance_callback", "vf_graph_staged", "vf_get_trajectory", "vf_get_imu_factor",
-    "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged", "vf_graph_get_staged_loss", "vf_add_between_robust", "vf_set_robust_far",
+    "vf_add_imu_factor", "vf_get_most_recent_estimate", "vf_graph_lm_stats", "vf_graph_solver_info", "vf_set_initial_state", "vf_graph_incremental_info", "vf_graph_get_staged", "vf_graph_get_staged_loss", "vf_add_between_robust", "vf_set_robust_far", "vf_add_absolute_pose", "vf_add_absolute_position", "vf_get_absolute_factors",
     "vf_degeneracy_batch", "vf_degeneracy_spectrum_batch", "vf_degeneracy_scores_batch", "vf_dopt_filter_f32", "vf_degeneracy_remap_batch",
 ]
 

@@ -40,7 +40,7 @@ static int isam_step_incremental(vf_engine* e, double relin_threshold) {
     const vf::View a = vf::incremental(e->v, invalid || e->mem.inc_slid());     // (the priors too where the marginal prior has changed)
     vf::launch_inc_begin(a, relin_threshold, appended, invalid, e->stream);
     HIPCHK(hipMemsetAsync(e->v.lambda, 0, e->v.B * sizeof(double), e->stream));     // Gauss-Newton: no damping
-    vf::launch_linearize(a, 0, e->stream);
+    vf::launch_linearize(a, e->btw_kind, 0, e->stream);
     vf::launch_assemble(a, e->stream);
     vf::launch_inc_solve(a, e->stream);
     vf::launch_inc_retract(a, e->stream);

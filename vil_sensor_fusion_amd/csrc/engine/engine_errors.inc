@@ -25,7 +25,7 @@ int vf_engine_factor_errors(vf_engine* e, unsigned flags, const double* chi2_thr
     if ((flags & VF_ERRORS_RELINEARIZE) || !e->mem.residuals_vouched()) {
         e->mem.rewritten();
         const vf::View a = vf::every_window(e->v);
-        vf::launch_linearize(a, 0, e->stream);      // (which = 0: the estimate, or theta of a reference-compat engine)
+        vf::launch_linearize(a, e->btw_kind, 0, e->stream);      // (which = 0: the estimate, or theta of a reference-compat engine)
         if (e->x_used > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
         e->mem.residuals_current();
     }

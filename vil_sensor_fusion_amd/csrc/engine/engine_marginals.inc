@@ -30,7 +30,7 @@ static int factor_undamped(vf_engine* e, double* zero, int* failed, int* ones, v
     const vf::View a = vf::undamped_whole(e->v, zero, failed, ones);
     HIPCHK(hipMemsetAsync(failed, 0, (size_t)e->v.B * sizeof(int), e->stream));
     // linearisation at the current states (which = 0): the estimate, or theta of a reference-compat engine
-    vf::launch_linearize(a, 0, e->stream);
+    vf::launch_linearize(a, e->btw_kind, 0, e->stream);
     if (e->x_used > 0) vf::launch_linearize_extra(a, 0, e->stream);     // (launch_linearize leaves the far factors to the caller)
     // the forward sweep of the engine's own solves when they assemble H themselves (form 2), else k_band_forward after K3.  The plan
     // is the one the same engine without far factors would have: far factors veto the assembling sweep for the SOLVE (its Woodbury

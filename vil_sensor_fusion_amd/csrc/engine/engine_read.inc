@@ -164,7 +164,7 @@ int vf_engine_time_stage(vf_engine* e, int stage, int reps, float* avg_ms) {
     auto run = [&]() {
         switch (stage) {
             case VF_STAGE_LINEARIZE_IMU: vf::launch_linearize_imu(tv, 0, e->stream); break;
-            case VF_STAGE_LINEARIZE_BTW: vf::launch_linearize_between(tv, 0, e->stream); break;
+            case VF_STAGE_LINEARIZE_BTW: vf::launch_linearize_between(tv, e->btw_kind, 0, e->stream); break;
             case VF_STAGE_ASSEMBLE: vf::launch_assemble(tv, e->stream); break;
             case VF_STAGE_SOLVE: vf::launch_band_solve(tv, tv, plan, e->stream); break;
             case VF_STAGE_RETRACT: vf::launch_retract(tv, e->stream); break;

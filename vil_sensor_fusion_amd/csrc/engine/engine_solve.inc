@@ -15,7 +15,7 @@ static int linearize(vf_engine* e, int which) {
         HIPCHK(hipMemsetAsync(e->v.fresh, 0x01, e->v.B * sizeof(int), e->stream));
         HIPCHK(hipMemsetAsync(e->v.done, 0, e->v.B * sizeof(int), e->stream));
     }
-    vf::launch_linearize(e->v, which, e->stream);
+    vf::launch_linearize(e->v, e->btw_kind, which, e->stream);
     if (e->x_used > 0) vf::launch_linearize_extra(e->v, which, e->stream);
     HIPCHK(hipGetLastError());
     return VF_OK;
@@ -189,7 +189,7 @@ static int retract(vf_engine* e) {
 // non-monotone LM: a failed excursion has put the point it started from back into the current buffer; its factors are
 // linearised again (the kernels skip every window whose flag is clear)
 static int relinearize_restored(vf_engine* e) {
-    vf::launch_linearize(vf::restored_only(e->v), 0, e->stream);
+    vf::launch_linearize(vf::restored_only(e->v), e->btw_kind, 0, e->stream);
     HIPCHK(hipMemsetAsync(e->v.relin, 0, e->v.B * sizeof(int), e->stream));
     return VF_OK;
 }
@@ -240,7 +240,7 @@ static int iterate_sequence(vf_engine* e, int iterations) {
     if (slid) {
         // nothing but slides since the last solve: only the appended keyframes' factors and the priors need linearising
         // (no window is converged yet: the flags were cleared with the damping)
-        vf::launch_linearize_tail(e->v, slid, e->stream);
+        vf::launch_linearize_tail(e->v, e->btw_kind, slid, e->stream);
         HIPCHK(hipGetLastError());
     } else if ((rc = linearize(e, 0))) return rc;
     if ((rc = decide(e, 1))) return rc;

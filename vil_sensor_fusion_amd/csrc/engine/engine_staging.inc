@@ -165,6 +165,12 @@ int vf_engine_set_between(vf_engine* e, int window, int n, const int32_t* a, con
             for (int i = 0; i < n; i++) la.g[i] = (long)window * M + b[i];
             vf::launch_put_between_loss(e->v, la, e->stream);
         }
+        if (e->btw_kind && n > 0) {                // (... and a between factor, whatever the slot held)
+            vf::BtwKindArg ka{};
+            ka.n = n;
+            for (int i = 0; i < n; i++) ka.g[i] = (long)window * M + b[i];
+            vf::launch_put_between_kind(e->btw_kind, ka, e->stream);
+        }
         HIPCHK(hipGetLastError());
         return VF_OK;
     }
@@ -408,7 +414,7 @@ int vf_engine_ingest_tail(vf_engine* e, const int32_t* step_off, const double* s
     const char* d = e->ingest.device();
     vf::launch_ingest_tail(e->v, (const int*)(d + off_at), (const double*)(d + st_at), (const int*)(d + a_at),
                            (const double*)(d + rec_at), imu_cov(p), e->in_status, e->stream);
-    if (e->v.btw_loss) vf::launch_reset_tail_loss(e->v, e->stream);     // (the slot a record has just been written to)
+    if (e->v.btw_loss) vf::launch_reset_tail_loss(e->v, e->btw_kind, e->stream);     // (the slot a record has just been written to)
     HIPCHK(hipGetLastError());
     HIPCHK(e->ingest.launched(e->stream));
     // Nothing inside any window changed (the records sit in slot hi, beyond every window's end): a warm engine stays warm,

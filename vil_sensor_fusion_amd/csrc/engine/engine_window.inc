@@ -321,6 +321,11 @@ int vf_engine_compact(vf_engine* e, int shift) {
         HIPCHK(hipMemcpyAsync(e->stage, lk + shift, keepk * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
         HIPCHK(hipMemcpyAsync(lk, e->stage, keepk * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
         HIPCHK(hipMemsetAsync(lk + keepk, 0, (size_t)shift * sizeof(double), e->stream));
+        if (!e->btw_kind) continue;               // ... and their kinds (absolute factors, engine_absolute.inc)
+        int* ki = e->btw_kind + (size_t)w * v.M;
+        HIPCHK(hipMemcpyAsync(e->stage, ki + shift, keepk * sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(ki, e->stage, keepk * sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(ki + keepk, 0, (size_t)shift * sizeof(int), e->stream));
     }
     // window ranges and prior keys
     std::vector<int> lo(v.B), hi(v.B), pk(v.B);
@@ -439,6 +444,11 @@ int vf_engine_grow(vf_engine* e, int new_capacity) {
         if ((rc = n->ensure_loss())) { vf_engine_destroy(n); return rc; }
         cp2(n->v.btw_loss, e->v.btw_loss, sizeof(int));
         cp2(n->v.btw_loss_k, e->v.btw_loss_k, sizeof(double));
+        if ((rc = copied())) return rc;
+    }
+    if (e->btw_kind) {            // ... and their kinds (absolute factors)
+        if ((rc = n->ensure_kind())) { vf_engine_destroy(n); return rc; }
+        cp2(n->btw_kind, e->btw_kind, sizeof(int));
         if ((rc = copied())) return rc;
     }
     // what the solver remembers from solve to solve: the non-monotone rule's damping / excursion state (a whole-history handle

@@ -345,18 +345,95 @@ __device__ __forceinline__ void robustify_between(double* out, const int loss, c
     }
 }
 
+// Absolute factors in the between slot (vf_engine_set_absolute; DESIGN.md "4k"): a factor on keyframe gk ALONE, written into gk's
+// own slot as a between factor from gk - 1 whose first Jacobian is 36 exact zeros -- J^T J then has J_u^T J_u on block (gk, gk) and
+// exact zeros on the blocks of gk - 1, J^T r has J_u^T r_u on gk, the cost 0.5 |r_u|^2: a unary factor's, and nothing that reads
+// btw_out knows the difference.  The slot's kind (ABS_*) is an array of the engine's, an ARGUMENT of the kernels that read it.
+//
+// ABS_NONE and ABS_POSE: the between factor, and GTSAM's PriorFactor<Pose3> -- r = R Log(Z^-1 T_b), J_u = R J_r^-1(Log(Z^-1 T_b)),
+// which is between_values with (qa, ta) = (identity, 0): Ra = I, qh = qb and th = tb come out exactly, and its jb is this Hlocal.
+// ONE call serves both, so that a wave that holds both kinds runs it once: `unary` picks the first pose, and the sink's ja
+// stores 0.0 whatever it is handed.
+__device__ __forceinline__ void between_or_pose_core(const View& v, const int b, const long ga, const long gk, const bool unary,
+                                                     const double* __restrict__ in, double* __restrict__ out) {
+    struct Rec {
+        const double* __restrict__ in;
+        VF_DI double operator()(int f) const { return in[(size_t)f * TILE]; }
+    };
+    struct Sink {
+        double* __restrict__ out;
+        bool unary;
+        VF_DI void r(int f, double x) { __builtin_nontemporal_store(x, out + (size_t)f * TILE); }
+        VF_DI void ja(int e, double x) { __builtin_nontemporal_store(unary ? 0.0 : x, out + (size_t)(6 + e) * TILE); }
+        VF_DI void jb(int e, double x) { __builtin_nontemporal_store(x, out + (size_t)(42 + e) * TILE); }
+    };
+    // (slot ga = gk - 1 of a unary factor is inside the window: its state is loaded like any other and not used)
+    const Q4 qs = q4(XS(b, 0, ga), XS(b, 1, ga), XS(b, 2, ga), XS(b, 3, ga));
+    const V3 ts = v3(XS(b, 4, ga), XS(b, 5, ga), XS(b, 6, ga));
+    const Q4 qa = unary ? q4(1.0, 0.0, 0.0, 0.0) : qs;
+    const V3 ta = unary ? v3(0.0, 0.0, 0.0) : ts;
+    const Q4 qb = q4(XS(b, 0, gk), XS(b, 1, gk), XS(b, 2, gk), XS(b, 3, gk));
+    const V3 tb = v3(XS(b, 4, gk), XS(b, 5, gk), XS(b, 6, gk));
+    Sink sink{out, unary};
+    between_values(qa, ta, qb, tb, Rec{in}, sink);
+}
+
+// ABS_POSITION: GTSAM's GPSFactor.  e = t_b - z in the world frame, r = R3 e, J_u = R3 [0 | R_b] (k_retract moves t by R_b dp, and
+// the rotation has no first-order effect on t).  The record is [1, 0, 0, 0, z, R] with only the translation block of R's 21 words
+// in use: R3 is rows 3..5 of the upper triangle, and rows 3..5 of the slot carry the factor, as the translation rows of a pose do
+// (ABS_POSITION_ROW0); rows 0..2 of r, Ja and Jb, all of Ja and the rotation columns of Jb are exact zeros.
+__device__ __forceinline__ void absolute_position_core(const View& v, const int b, const long gk, const double* __restrict__ in,
+                                                       double* __restrict__ out) {
+    const Q4 qb = q4(XS(b, 0, gk), XS(b, 1, gk), XS(b, 2, gk), XS(b, 3, gk));
+    const V3 e = v3(XS(b, 4, gk), XS(b, 5, gk), XS(b, 6, gk)) - v3(in[4 * TILE], in[5 * TILE], in[6 * TILE]);
+    M3 R3;      // (upper triangular: the three words below the diagonal stay zero)
+    R3.a[0] = in[(size_t)(7 + off6(3)) * TILE]; R3.a[1] = in[(size_t)(7 + off6(3) + 1) * TILE]; R3.a[2] = in[(size_t)(7 + off6(3) + 2) * TILE];
+    R3.a[3] = 0.0;                              R3.a[4] = in[(size_t)(7 + off6(4)) * TILE];     R3.a[5] = in[(size_t)(7 + off6(4) + 1) * TILE];
+    R3.a[6] = 0.0;                              R3.a[7] = 0.0;                                  R3.a[8] = in[(size_t)(7 + off6(5)) * TILE];
+    const M3 Rb = qrot(qb);
+    const double ev[3] = {e.x, e.y, e.z};
+    static_assert(ABS_POSITION_ROW0 == 3, "rows 3..5 of the slot");
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = i; c < 3; c++) s = fma(R3.a[i * 3 + c], ev[c], s);
+        __builtin_nontemporal_store(0.0, out + (size_t)i * TILE);
+        __builtin_nontemporal_store(s, out + (size_t)(ABS_POSITION_ROW0 + i) * TILE);
+    }
+#pragma unroll
+    for (int e36 = 0; e36 < 36; e36++) __builtin_nontemporal_store(0.0, out + (size_t)(6 + e36) * TILE);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            double s = 0.0;
+            if (c >= 3) {
+#pragma unroll
+                for (int l = i; l < 3; l++) s = fma(R3.a[i * 3 + l], Rb.a[l * 3 + c - 3], s);
+            }
+            __builtin_nontemporal_store(0.0, out + (size_t)(42 + i * 6 + c) * TILE);
+            __builtin_nontemporal_store(s, out + (size_t)(42 + (ABS_POSITION_ROW0 + i) * 6 + c) * TILE);
+        }
+}
+
 // RB: the engine holds losses (View::btw_loss is not null; never on a time-sharded engine).  The kernels without them are the
 // RB = false instances, which read neither array: what they were before losses existed.
-template <bool SH, bool RB = false>
-__device__ __forceinline__ void linearize_between_factor(const View& v, int which, const long gk) {
+// AB: the engine holds absolute factors too (btw_kind, the slots' kinds: made behind the loss arrays, so AB implies RB).  The
+// instances without them read no kind and are what they were before absolute factors existed.
+template <bool SH, bool RB = false, bool AB = false>
+__device__ __forceinline__ void linearize_between_factor(const View& v, int which, const long gk, const int* __restrict__ btw_kind = nullptr) {
     static_assert(!(SH && RB), "losses on time-sharded windows are not built");
+    static_assert(!AB || RB, "the kinds come behind the loss arrays");
     if (gk >= v.G) return;
     const int w = (int)(gk / v.M), k = (int)(gk - (long)w * v.M);
     const int lo = v.lo[w], w_hi = v.hi[w], w_sel = v.sel[w], w_done = v.stop_on ? v.done[w] : 0;
     const int a = v.btw_a[gk];                 // (all five requested together: one round trip)
     int loss = LOSS_NONE;
     double loss_k = 0.0;
+    int kind = ABS_NONE;
     if (RB) { loss = v.btw_loss[gk]; loss_k = v.btw_loss_k[gk]; }
+    if (AB) kind = btw_kind[gk];               // (... and the kind with them)
     if (k <= lo || k >= w_hi || w_done) return;
     if (v.relin_only && !v.relin[w]) return;
     if (v.inc_on && k < v.inc_k[w]) return;
@@ -365,6 +442,9 @@ __device__ __forceinline__ void linearize_between_factor(const View& v, int whic
     const int b = w_sel ^ which;
     const double* __restrict__ in = v.btw_in + (size_t)(gk >> 6) * BTW_IN * TILE + (gk & 63);
     double* __restrict__ out = v.btw_out + ((size_t)b * (size_t)(v.G >> 6) + (size_t)(gk >> 6)) * BTW_OUT * TILE + (gk & 63);
-    between_core<SH>(v, b, (long)w * v.M + a, gk, in, TILE, out, TILE, jac);
+    if (AB) {
+        if (kind == ABS_POSITION) absolute_position_core(v, b, gk, in, out);
+        else between_or_pose_core(v, b, (long)w * v.M + a, gk, kind == ABS_POSE, in, out);
+    } else between_core<SH>(v, b, (long)w * v.M + a, gk, in, TILE, out, TILE, jac);
     if (RB && loss != LOSS_NONE) robustify_between(out, loss, loss_k);
 }

@@ -115,6 +115,23 @@ __global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_all_robust(Vie
     else if (bx < nb_imu + nb_btw) linearize_between_factor<false, true>(v, which, (long)(bx - nb_imu) * K1_BLOCK + threadIdx.x);
     else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * K1_BLOCK + (int)threadIdx.x);
 }
+// ... and of an engine that holds absolute factors (vf_engine_set_absolute; linearize_between_factor<.., true, true>, which reads the
+// slots' kinds from btw_kind): kernels of their own again, so that the ones above stay what they were
+__global__ void __launch_bounds__(256) k_linearize_between_abs(View v, int which, const int* btw_kind) {
+    linearize_between_factor<false, true, true>(v, which, (long)blockIdx.x * 256 + threadIdx.x, btw_kind);
+}
+__global__ void __launch_bounds__(256) k_linearize_between_prior_abs(View v, int which, int nb_pri, const int* btw_kind) {
+    const int bx = blockIdx.x;
+    if (bx < nb_pri) {
+        if (threadIdx.x < 64) linearize_prior_window(v, which, bx * 64 + (int)threadIdx.x);
+    } else linearize_between_factor<false, true, true>(v, which, (long)(bx - nb_pri) * 256 + threadIdx.x, btw_kind);
+}
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_all_abs(View v, int which, int nb_imu, int nb_btw, const int* btw_kind) {
+    const int bx = blockIdx.x;
+    if (bx < nb_imu) linearize_imu_factor<false>(v, which, (long)bx * K1_BLOCK + threadIdx.x);
+    else if (bx < nb_imu + nb_btw) linearize_between_factor<false, true, true>(v, which, (long)(bx - nb_imu) * K1_BLOCK + threadIdx.x, btw_kind);
+    else linearize_prior_window(v, which, (bx - nb_imu - nb_btw) * K1_BLOCK + (int)threadIdx.x);
+}
 
 // Warm start of a fixed-lag update (vf_engine_slide directly after a solve): the linearisation of every factor that was
 // in the window is still the one of the current states (an accepted trial's records became current with its states, a
@@ -143,6 +160,21 @@ __global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_tail_robust(Vi
     } else if (bx < 2 * v.B) {
         const int w = bx - v.B;
         if (t < nslid) linearize_between_factor<false, true>(v, 0, (long)w * v.M + v.hi[w] - 1 - t);
+    } else {
+        const int w = (bx - 2 * v.B) * 64 + t;
+        if (t < 64) {
+            if (w < v.B) v.fresh[w] = v.fresh[w] ? 1 : 1 + nslid;
+            linearize_prior_window(v, 0, w);
+        }
+    }
+}
+__global__ void __launch_bounds__(K1_BLOCK, K1_WAVES) k_linearize_tail_abs(View v, int nslid, const int* btw_kind) {
+    const int bx = blockIdx.x, t = threadIdx.x;
+    if (bx < v.B) {
+        if (t < nslid) linearize_imu_factor<false>(v, 0, (long)bx * v.M + v.hi[bx] - 1 - t);
+    } else if (bx < 2 * v.B) {
+        const int w = bx - v.B;
+        if (t < nslid) linearize_between_factor<false, true, true>(v, 0, (long)w * v.M + v.hi[w] - 1 - t, btw_kind);
     } else {
         const int w = (bx - 2 * v.B) * 64 + t;
         if (t < 64) {

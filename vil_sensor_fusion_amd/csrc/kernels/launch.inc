@@ -36,33 +36,39 @@ void launch_extra_combine(const View& v, const double* Zm, size_t zstride, int s
         hipLaunchKernelGGL(k_extra_apply<false>, dim3(nblk((long)v.M * 15, 256), (unsigned)v.B), dim3(256), 0, s, v, Zm, zstride, slots);
     }
 }
-static void launch_linearize_all(const View& v, int which, hipStream_t s) {
+static void launch_linearize_all(const View& v, const int* btw_kind, int which, hipStream_t s) {
     const int nb_imu = (int)nblk(v.G, K1_BLOCK), nb_btw = nb_imu, nb_pri = (int)nblk(v.B, K1_BLOCK);
-    if (v.btw_loss) hipLaunchKernelGGL(k_linearize_all_robust, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
+    // (an engine that holds absolute factors launches the instances that read the slots' kinds, one that holds losses the ones
+    // that read those, any other what it always has: chosen here, on the host)
+    if (btw_kind) hipLaunchKernelGGL(k_linearize_all_abs, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw, btw_kind);
+    else if (v.btw_loss) hipLaunchKernelGGL(k_linearize_all_robust, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
     else if (v.sh_G > 1) hipLaunchKernelGGL(k_linearize_all<true>, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
     else hipLaunchKernelGGL(k_linearize_all<false>, dim3(nb_imu + nb_btw + nb_pri), dim3(K1_BLOCK), 0, s, v, which, nb_imu, nb_btw);
 }
 void launch_linearize_imu(const View& v, int which, hipStream_t s) {
     hipLaunchKernelGGL(k_linearize_imu, dim3(nblk(v.G, K1_BLOCK)), dim3(K1_BLOCK), 0, s, v, which);
 }
-void launch_linearize_between(const View& v, int which, hipStream_t s) {
-    if (v.btw_loss) hipLaunchKernelGGL(k_linearize_between_robust, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which);
+void launch_linearize_between(const View& v, const int* btw_kind, int which, hipStream_t s) {
+    if (btw_kind) hipLaunchKernelGGL(k_linearize_between_abs, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which, btw_kind);
+    else if (v.btw_loss) hipLaunchKernelGGL(k_linearize_between_robust, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which);
     else hipLaunchKernelGGL(k_linearize_between, dim3(nblk(v.G, 256)), dim3(256), 0, s, v, which);
 }
-static void launch_linearize_between_prior(const View& v, int which, hipStream_t s) {     // K2 + K2b in one launch
+static void launch_linearize_between_prior(const View& v, const int* btw_kind, int which, hipStream_t s) {     // K2 + K2b in one launch
     const int nb_pri = (int)nblk(v.B, 64);
-    if (v.btw_loss) hipLaunchKernelGGL(k_linearize_between_prior_robust, dim3(nblk(v.G, 256) + nb_pri), dim3(256), 0, s, v, which, nb_pri);
+    if (btw_kind) hipLaunchKernelGGL(k_linearize_between_prior_abs, dim3(nblk(v.G, 256) + nb_pri), dim3(256), 0, s, v, which, nb_pri, btw_kind);
+    else if (v.btw_loss) hipLaunchKernelGGL(k_linearize_between_prior_robust, dim3(nblk(v.G, 256) + nb_pri), dim3(256), 0, s, v, which, nb_pri);
     else hipLaunchKernelGGL(k_linearize_between_prior, dim3(nblk(v.G, 256) + nb_pri), dim3(256), 0, s, v, which, nb_pri);
 }
-void launch_linearize(const View& v, int which, hipStream_t s) {
-    if (v.B <= 128 || v.sh_G > 1) launch_linearize_all(v, which, s);
+void launch_linearize(const View& v, const int* btw_kind, int which, hipStream_t s) {
+    if (v.B <= 128 || v.sh_G > 1) launch_linearize_all(v, btw_kind, which, s);
     else {
         launch_linearize_imu(v, which, s);
-        launch_linearize_between_prior(v, which, s);
+        launch_linearize_between_prior(v, btw_kind, which, s);
     }
 }
-void launch_linearize_tail(const View& v, int nslid, hipStream_t s) {
-    if (v.btw_loss) hipLaunchKernelGGL(k_linearize_tail_robust, dim3(2 * v.B + nblk(v.B, 64)), dim3(K1_BLOCK), 0, s, v, nslid);
+void launch_linearize_tail(const View& v, const int* btw_kind, int nslid, hipStream_t s) {
+    if (btw_kind) hipLaunchKernelGGL(k_linearize_tail_abs, dim3(2 * v.B + nblk(v.B, 64)), dim3(K1_BLOCK), 0, s, v, nslid, btw_kind);
+    else if (v.btw_loss) hipLaunchKernelGGL(k_linearize_tail_robust, dim3(2 * v.B + nblk(v.B, 64)), dim3(K1_BLOCK), 0, s, v, nslid);
     else hipLaunchKernelGGL(k_linearize_tail, dim3(2 * v.B + nblk(v.B, 64)), dim3(K1_BLOCK), 0, s, v, nslid);
 }
 // K3 for the partitioned half of a hybrid solve whose sweep half assembles its own rows (see k_assemble)
@@ -217,12 +223,19 @@ __global__ void __launch_bounds__(64) k_put_between_loss(View v, BtwLossArg a) {
     if (i < a.n) { v.btw_loss[a.g[i]] = a.loss[i]; v.btw_loss_k[a.g[i]] = a.k[i]; }
 }
 // ... and NONE for the slot behind every window's end: the record vf_engine_ingest_tail has just written there is a new factor
-__global__ void __launch_bounds__(64) k_reset_tail_loss(View v) {
+// (... and its kind on an engine that holds kinds: btw_kind, null elsewhere)
+__global__ void __launch_bounds__(64) k_reset_tail_loss(View v, int* btw_kind) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= v.B || v.hi[w] >= v.M) return;
     const long g = (long)w * v.M + v.hi[w];
     v.btw_loss[g] = LOSS_NONE;
     v.btw_loss_k[g] = 0.0;
+    if (btw_kind) btw_kind[g] = ABS_NONE;
+}
+// the kind of up to four slots of one window (vf_engine_set_absolute and vf_engine_set_between on an asynchronous engine)
+__global__ void __launch_bounds__(64) k_put_between_kind(int* btw_kind, BtwKindArg a) {
+    const int i = threadIdx.x;
+    if (i < a.n) btw_kind[a.g[i]] = a.kind[i];
 }
 __global__ void __launch_bounds__(64) k_read_result(View v, int window, int slot, int which, int* sticky, SolveResult* out) {
     const int t = threadIdx.x;
@@ -244,8 +257,11 @@ void launch_put_between(const View& v, long g, int a, const BtwArg& rec, hipStre
 void launch_put_between_loss(const View& v, const BtwLossArg& a, hipStream_t s) {
     hipLaunchKernelGGL(k_put_between_loss, dim3(1), dim3(64), 0, s, v, a);
 }
-void launch_reset_tail_loss(const View& v, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset_tail_loss, dim3(nblk(v.B, 64)), dim3(64), 0, s, v);
+void launch_reset_tail_loss(const View& v, int* btw_kind, hipStream_t s) {
+    hipLaunchKernelGGL(k_reset_tail_loss, dim3(nblk(v.B, 64)), dim3(64), 0, s, v, btw_kind);
+}
+void launch_put_between_kind(int* btw_kind, const BtwKindArg& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_put_between_kind, dim3(1), dim3(64), 0, s, btw_kind, a);
 }
 void launch_read_result(const View& v, int window, int slot, int which, int* sticky, SolveResult* out, hipStream_t s) {
     hipLaunchKernelGGL(k_read_result, dim3(1), dim3(64), 0, s, v, window, slot, which, sticky, out);

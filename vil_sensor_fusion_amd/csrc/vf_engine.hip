@@ -422,11 +422,28 @@ struct vf_engine : EngineHandle {
         epoch++;
         return VF_OK;
     }
-    // NONE for the slots [g0, g0 + n) whose record a staging call has just written or cleared (nothing on an engine without losses)
+    // absolute factors in the between slot (engine/engine_absolute.inc): [G] kinds, VF_ABSOLUTE_*, made by the first
+    // vf_engine_set_absolute behind the loss arrays (the kernels that read kinds read losses).  Not a member of View, whose 712
+    // bytes have no word left: btw_kind is handed to the launchers, which choose the K2 kernels by it -- another launch sequence
+    // from then on, so a captured one is void
+    vf::DeviceBuf<int> kind_id;
+    int* btw_kind = nullptr;
+    int ensure_kind() {
+        if (btw_kind) return VF_OK;
+        if (int rc = ensure_loss()) return rc;
+        HIPCHK(kind_id.ensure((size_t)v.G * sizeof(int)));
+        HIPCHK(hipMemsetAsync(kind_id, 0, (size_t)v.G * sizeof(int), stream));
+        btw_kind = kind_id;
+        epoch++;
+        return VF_OK;
+    }
+    // NONE for the slots [g0, g0 + n) whose record a staging call has just written or cleared: their loss and their kind (nothing on
+    // an engine without the arrays)
     int reset_loss(long g0, long n) {
         if (!v.btw_loss || n <= 0) return VF_OK;
         HIPCHK(hipMemsetAsync(v.btw_loss + g0, 0, (size_t)n * sizeof(int), stream));
         HIPCHK(hipMemsetAsync(v.btw_loss_k + g0, 0, (size_t)n * sizeof(double), stream));
+        if (btw_kind) HIPCHK(hipMemsetAsync(btw_kind + g0, 0, (size_t)n * sizeof(int), stream));
         return VF_OK;
     }
     // vf_engine_grow: the arrays of `o` come behind this handle (and this one's go behind o's, to be destroyed with it)
@@ -459,4 +476,5 @@ extern "C" {
 #include "engine/engine_closure.inc"
 #include "engine/engine_errors.inc"
 #include "engine/engine_robust.inc"
+#include "engine/engine_absolute.inc"
 }  // extern "C"

@@ -44,6 +44,7 @@ struct SolveTake {
     vf_between_loss_setter set_loss = nullptr;   // the handle's set_between_loss as it stood at the take (read under graph_mutex, where it is written)
     vf_far_robust_setter set_far_robust = nullptr;   // ... and its two calls for the losses of far factors, likewise
     vf_far_loss_getter get_far_loss = nullptr;
+    vf_absolute_setter set_absolute = nullptr;   // ... and the one for absolute factors
 };
 
 struct Lap {   // VF_SOLVE_TIMING: "[vf_solve] <label> <us>" on stderr behind every step of a solve (tools/gm_lap_summary.py reads the labels)
@@ -425,6 +426,42 @@ int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4],
     return VF_OK;
 }
 
+// An absolute factor on `key` (vf_add_absolute_pose / vf_add_absolute_position, vf_graph_absolute.cpp): staged like a band factor from
+// key - 1 -- it takes key's band slot, marks band_end at the take, and a later vf_add_between ending at key goes to the far list by
+// the rule above.  A fix for a key already solved is written at the next solve, as late band odometry is; one whose key - 1 has left
+// the window by then is dropped as late (refuse_late).
+int vf_add_absolute_(vf_graph* g, uint64_t key, int kind, const double rec[VF_BTW_RECORD], const StagedFactor* shown, int loss, double loss_k,
+                     vf_absolute_setter setter, const vf_robust_calls* calls) {
+    if (!g || !rec || !shown || !setter) return gerr(VF_ERR_INVALID, "null argument");
+    PendingBetween b;
+    b.a = key - 1;
+    b.b = key;
+    b.kind = kind;
+    b.loss = loss;
+    b.loss_k = loss == VF_LOSS_NONE ? 0.0 : loss_k;
+    memcpy(b.rec, rec, sizeof(b.rec));
+    std::lock_guard<std::mutex> lk(g->graph_mutex);
+    if (key == 0 || key > g->current_key) return gerr(VF_ERR_BAD_KEY, "absolute factor on key %llu: not a reserved key other than the first", (unsigned long long)key);
+    if (key - 1 < oldest_key(g))
+        return gerr(VF_ERR_BAD_KEY, "absolute factor on key %llu: key %llu has left the window (oldest key %llu); the oldest keyframe cannot take one",
+                    (unsigned long long)key, (unsigned long long)(key - 1), (unsigned long long)oldest_key(g));
+    bool taken = g->has_band_end(key);
+    for (const auto& s : g->staged_between) taken = taken || s.b == key;
+    if (taken) return gerr(VF_ERR_CAPACITY, "absolute factor on key %llu: the key's band slot holds a factor already (one factor per slot)", (unsigned long long)key);
+    g->set_absolute = setter;
+    if (calls) { g->set_between_loss = calls->set_between_loss; g->set_far_robust = calls->set_far_robust; g->get_far_loss = calls->get_far_loss; }
+    g->staged_between.push_back(b);
+    g->staged_count++;
+    StagedFactor sf = *shown;
+    sf.a = key - 1;             // (as drop_late finds it; vf_graph_get_staged shows the key twice)
+    sf.b = key;
+    sf.kind = kind;
+    sf.loss = b.loss;
+    sf.loss_k = b.loss_k;
+    g->staged_log.push_back(sf);
+    return VF_OK;
+}
+
 int vf_set_callback(vf_graph* g, vf_callback cb, void* user) {
     if (!g || !cb) return gerr(VF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->state_mutex);
@@ -473,8 +510,8 @@ int vf_graph_get_staged(vf_graph* g, int index, int* kind, uint64_t* key1, uint6
         return VF_OK;
     }
     const StagedFactor& f = g->staged_log[(size_t)(index - np)];
-    if (kind) *kind = 3;
-    if (key1) *key1 = f.a;
+    if (kind) *kind = 3 + f.kind;          // (3: a between factor; 4, 5: an absolute pose / position factor, on one key)
+    if (key1) *key1 = f.kind == VF_ABSOLUTE_NONE ? f.a : f.b;
     if (key2) *key2 = f.b;
     if (q) memcpy(q, f.q, sizeof(f.q));
     if (t) memcpy(t, f.t, sizeof(f.t));
@@ -529,6 +566,7 @@ static void take(vf_graph* g, SolveTake& t) {
     t.set_loss = g->set_between_loss;
     t.set_far_robust = g->set_far_robust;
     t.get_far_loss = g->get_far_loss;
+    t.set_absolute = g->set_absolute;
     for (const auto& bt : t.betweens) g->set_band_end(bt.b, 1);   // these keys now carry their band factor (a second one goes to the far list)
     // (keys below the window can never be named again by a factor that is accepted: their marks are let go)
     while (!g->band_end.empty() && g->band_base < oldest_key(g)) { g->band_end.pop_front(); g->band_base++; }
@@ -674,7 +712,27 @@ static int stage_band(vf_graph* g, SolveTake& t, Lap& lap) {
         b[i] = slot_of(g, betweens[order[i]].b);
         memcpy(&rec[i * VF_BTW_RECORD], betweens[order[i]].rec, sizeof(double) * VF_BTW_RECORD);
     }
-    if (int rc = vf_engine_set_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+    // (absolute factors among them go through their own call, the others through vf_engine_set_between: two sorted subsequences)
+    std::vector<int32_t> ua, ub, uk;
+    std::vector<double> urec;
+    bool unary = false;
+    for (const auto& f : betweens) unary = unary || f.kind != VF_ABSOLUTE_NONE;
+    if (!unary) {
+        if (int rc = vf_engine_set_between(g->eng, 0, (int)a.size(), a.data(), b.data(), rec.data())) return rc;
+    } else {
+        if (!t.set_absolute) return gerr(VF_ERR_INVALID, "an absolute factor is staged and the handle has no call to send it with");
+        std::vector<int32_t> pa, pb;
+        std::vector<double> prec;
+        for (size_t i = 0; i < order.size(); i++) {
+            const PendingBetween& f = betweens[order[i]];
+            const double* r = &rec[i * VF_BTW_RECORD];
+            if (f.kind == VF_ABSOLUTE_NONE) { pa.push_back(a[i]); pb.push_back(b[i]); prec.insert(prec.end(), r, r + VF_BTW_RECORD); }
+            else { ub.push_back(b[i]); uk.push_back(f.kind); urec.insert(urec.end(), r, r + VF_BTW_RECORD); }
+        }
+        if (!pa.empty())
+            if (int rc = vf_engine_set_between(g->eng, 0, (int)pa.size(), pa.data(), pb.data(), prec.data())) return rc;
+        if (int rc = t.set_absolute(g->eng, 0, (int)ub.size(), ub.data(), uk.data(), urec.data())) return rc;
+    }
     lap("set_between");
     // the losses behind the records (the engine resets the slots it writes): only when one of these factors has a loss
     bool robust = false;

@@ -48,7 +48,12 @@ int vf_get_factor_errors(vf_graph* g, uint64_t key0, int n, double* imu_err, dou
     if (int rc = ensure_errors(g, nullptr)) return rc;
     std::vector<int32_t> a(btw_prev_key ? (size_t)n : 0);
     if (int rc = vf_engine_read_factor_errors(g->eng, 0, slot_of(g, key0), n, imu_err, btw_err, btw_prev_key ? a.data() : nullptr)) return rc;
-    for (size_t i = 0; i < a.size(); i++) btw_prev_key[i] = a[i] < 0 ? UINT64_MAX : g->key_base + (uint64_t)a[i];
+    // (an absolute factor sits in its key's slot as one from the key before: it is reported as a factor on ONE key, prev == key)
+    std::vector<int32_t> kind(a.size());
+    if (!a.empty())
+        if (int rc = vf_engine_get_absolute(g->eng, 0, slot_of(g, key0), n, kind.data())) return rc;
+    for (size_t i = 0; i < a.size(); i++)
+        btw_prev_key[i] = a[i] < 0 ? UINT64_MAX : kind[i] != VF_ABSOLUTE_NONE ? key0 + (uint64_t)i : g->key_base + (uint64_t)a[i];
     return VF_OK;
 }
 

@@ -22,13 +22,17 @@ struct PendingImu {            // one queued CombinedImuFactor (GraphManager::_i
     bool staged = false;        // preintegrated on the device already, at reserveNode time (where the reference preintegrates: GraphManager.cpp:59-66)
 };
 // (loss, loss_k: the robust loss of a band factor, vf_add_between_robust; a Gaussian factor by default)
-struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device = false; int loss = VF_LOSS_NONE; double loss_k = 0.0; };
+// (kind: VF_ABSOLUTE_NONE for a between factor; an absolute factor on key b, vf_add_absolute_pose / _position, is staged like a band
+// factor from b - 1 -- it takes b's band slot -- and goes to the engine through vf_engine_set_absolute)
+struct PendingBetween { uint64_t a, b; double rec[VF_BTW_RECORD]; bool on_device = false; int loss = VF_LOSS_NONE; double loss_k = 0.0; int kind = VF_ABSOLUTE_NONE; };
 // a between factor as the caller handed it in: what GraphManager::graph() shows until the next solve (vf_graph_get_staged, vf_graph_get_staged_loss)
-struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; int loss = VF_LOSS_NONE; double loss_k = 0.0; };
+// (kind: as PendingBetween's; an absolute factor shows a = b = its key, a position fix its 3 x 3 covariance in the translation block of cov)
+struct StagedFactor { uint64_t a, b; double q[4], t[3], cov[36]; int loss = VF_LOSS_NONE; double loss_k = 0.0; int kind = VF_ABSOLUTE_NONE; };
 typedef int (*vf_between_loss_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*);   // vf_engine_set_between_loss
 // ... and the two calls a far factor's loss needs: vf_engine_set_extra_between_robust, vf_engine_get_extra_between_loss
 typedef int (*vf_far_robust_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*, const int32_t*, const double*);
 typedef int (*vf_far_loss_getter)(vf_engine*, int, int32_t*, double*);
+typedef int (*vf_absolute_setter)(vf_engine*, int, int, const int32_t*, const int32_t*, const double*);       // vf_engine_set_absolute
 struct vf_robust_calls { vf_between_loss_setter set_between_loss; vf_far_robust_setter set_far_robust; vf_far_loss_getter get_far_loss; };
 
 struct vf_graph {
@@ -49,6 +53,8 @@ struct vf_graph {
     // (robust_far below): set with set_between_loss, by the same hand, under the same rules
     vf_far_robust_setter set_far_robust = nullptr;
     vf_far_loss_getter get_far_loss = nullptr;
+    // ... and how it hands absolute factors to the engine (vf_graph_absolute.cpp sets it with the first one, as above)
+    vf_absolute_setter set_absolute = nullptr;
     bool robust_far = false;       // vf_set_robust_far: a pair the band cannot hold may carry a loss (guarded by graph_mutex)
     // Between factors the band cannot hold -- wider than VF_MAX_BANDWIDTH keyframes, or a second one ending at a key (loop
     // closures; iSAM2 takes any pair of keys, GraphManager.cpp:83-88): handed to the engine as "far" factors
@@ -94,6 +100,9 @@ struct vf_graph {
 // vf_set_robust_far has switched far losses on.  calls: the engine calls a loss needs (null with VF_LOSS_NONE), kept in the handle
 extern "C" int vf_add_between_(vf_graph* g, uint64_t prev, uint64_t cur, const double q[4], const double t[3], const double cov[36], int loss, double loss_k,
                                const vf_robust_calls* calls);
+// an absolute factor on `key` (vf_graph.cpp; vf_graph_absolute.cpp has built and checked the record, the loss and what graph() shows)
+extern "C" int vf_add_absolute_(vf_graph* g, uint64_t key, int kind, const double rec[VF_BTW_RECORD], const StagedFactor* shown, int loss, double loss_k,
+                                vf_absolute_setter setter, const vf_robust_calls* calls);
 extern "C" int vf_between_record_(const double q[4], const double t[3], const double cov[36], double rec[VF_BTW_RECORD]);   // vf_graph.cpp
 
 // key -> keyframe slot of the handle's one window, and the oldest key still in it

@@ -263,6 +263,13 @@ struct View {
 // this size; btw_loss / btw_loss_k sit in what were two padding words, which is why nm_W and x_max stand where they do)
 static_assert(sizeof(View) == 712, "View: the kernel argument block");
 __host__ __device__ inline int xl_ld(const View& v) { return 27 + 6 * v.x_max; }   // row stride of View::xl_U
+// Absolute factors in the between slot (vf_engine_set_absolute; DESIGN.md "4k"): the kind of the factor in each slot, VF_ABSOLUTE_*.
+// The array ([G] ints, vf_engine::btw_kind) is NOT a member of View -- the argument block has no padding word left and keeps its
+// 712 bytes -- but an argument of the kernels that read or write it; null on an engine that never saw an absolute factor, whose K2
+// launches are the ones they were (the launchers choose by it, launch.inc).  A position factor fills rows ABS_POSITION_ROW0 .. + 2
+// of its slot (r and Jb), the translation rows of a pose factor; the three rows in front of them are exact zeros.
+constexpr int ABS_NONE = 0, ABS_POSE = 1, ABS_POSITION = 2;
+constexpr int ABS_POSITION_ROW0 = 3;
 // Losses of the far between factors (View::x_loss): with n = B x_max entries, the allocation of x_in holds behind its n records the
 // parameters k (n doubles, from far_loss_k_at) and the loss ids (n ints, from far_loss_id_at, counted in doubles); far_loss_words: all
 // of it, in doubles.  An engine without far losses has the records alone.
@@ -325,10 +332,11 @@ void launch_cols_prepare(const View& v, const View& c, int ncols, hipStream_t s)
 void launch_cols_fail(const View& v, const View& c, int ncols, hipStream_t s);
 void launch_partitioned_solve(const View& v, hipStream_t s);
 // K1, K2 and K2b: one launch up to 128 windows and on time-sharded engines (latency), K1 and K2 + K2b as two above (throughput)
-void launch_linearize(const View& v, int which, hipStream_t s);
+// (btw_kind: the kinds of the slots' factors, see ABS_NONE; null on an engine without absolute factors)
+void launch_linearize(const View& v, const int* btw_kind, int which, hipStream_t s);
 void launch_linearize_imu(const View& v, int which, hipStream_t s);
-void launch_linearize_between(const View& v, int which, hipStream_t s);
-void launch_linearize_tail(const View& v, int nslid, hipStream_t s);   // warm start: factors of the appended keyframes + priors
+void launch_linearize_between(const View& v, const int* btw_kind, int which, hipStream_t s);
+void launch_linearize_tail(const View& v, const int* btw_kind, int nslid, hipStream_t s);   // warm start: factors of the appended keyframes + priors
 void launch_assemble(const View& v, hipStream_t s);
 void launch_assemble_window(const View& v, int window, hipStream_t s);   // H and g of one window, whatever its fresh / done flags say
 void launch_assemble_for_partitioned(const View& v, hipStream_t s);   // hybrid solves with an assembling sweep (K3::partitioned)
@@ -454,7 +462,10 @@ void launch_bump_lo(const View& v, hipStream_t s);
 void launch_put_between(const View& v, long g, int a, const BtwArg& rec, hipStream_t s);
 struct BtwLossArg { long g[4]; double k[4]; int loss[4]; int n; };      // up to four slots' losses by value (View::btw_loss)
 void launch_put_between_loss(const View& v, const BtwLossArg& a, hipStream_t s);
-void launch_reset_tail_loss(const View& v, hipStream_t s);      // NONE for the slot behind every window's end (vf_engine_ingest_tail)
+// NONE for the slot behind every window's end (vf_engine_ingest_tail): its loss, and its kind where the engine holds kinds
+void launch_reset_tail_loss(const View& v, int* btw_kind, hipStream_t s);
+struct BtwKindArg { long g[4]; int kind[4]; int n; };                   // up to four slots' kinds by value (vf_engine::btw_kind)
+void launch_put_between_kind(int* btw_kind, const BtwKindArg& a, hipStream_t s);
 void launch_read_result(const View& v, int window, int slot, int which, int* sticky, SolveResult* out, hipStream_t s);
 void launch_marginalize(const View& v, int far_slots_in_use, int* status, hipStream_t s);
 constexpr int MARG_STASH_DOUBLES = 729 + 27 + 48 + 4;     // per window: what k_marginalize leaves in a stash (information, gradient, linearisation states)

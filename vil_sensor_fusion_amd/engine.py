@@ -225,6 +225,35 @@ class Engine:
         check(self._l.vf_engine_get_between_loss(self._h, window, k0, n, _i(li), _d(kk)))
         return li, kk
 
+    def set_absolute(self, window, b, kind, rec):
+        """absolute factors on the keyframes in slots b (vf_engine_set_absolute): a factor on b alone, held in b's between slot as
+        one from b - 1 with a zero first Jacobian.  kind: "pose" / "position" or _lib.ABSOLUTE_*, one for all or one each; rec:
+        (n, 28) records -- a pose's as for set_between, a position's from position_record()"""
+        from . import _lib
+        names = {"pose": _lib.ABSOLUTE_POSE, "position": _lib.ABSOLUTE_POSITION}
+        b = np.atleast_1d(np.ascontiguousarray(b, dtype=np.int32))
+        kinds = kind if isinstance(kind, (list, tuple, np.ndarray)) else [kind] * b.size
+        ki = np.ascontiguousarray([names.get(x, x) for x in kinds], dtype=np.int32)
+        r = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, BTW_RECORD)
+        assert b.size == ki.size == r.shape[0]
+        check(self._l.vf_engine_set_absolute(self._h, window, b.size, _i(b), _i(ki), _d(r)))
+
+    def get_absolute(self, window, k0, n):
+        """kinds (n,) of the factors in the between slots k0 .. k0+n-1 (_lib.ABSOLUTE_*); none on an engine that never saw one"""
+        ki = np.zeros(n, dtype=np.int32)
+        check(self._l.vf_engine_get_absolute(self._h, window, k0, n, _i(ki)))
+        return ki
+
+    @staticmethod
+    def position_record(position, cov):
+        """the 28-double record of a position factor from the fix and its 3 x 3 covariance (vf_absolute_position_record)"""
+        from ._lib import lib
+        p = np.ascontiguousarray(position, dtype=np.float64).reshape(3)
+        c = np.ascontiguousarray(cov, dtype=np.float64).reshape(9)
+        rec = np.zeros(BTW_RECORD)
+        check(lib().vf_absolute_position_record(_d(p), _d(c), _d(rec)))
+        return rec
+
     def set_prior(self, window, k, rec):
         r = np.ascontiguousarray(rec, dtype=np.float64).reshape(PRIOR_RECORD)
         check(self._l.vf_engine_set_prior(self._h, window, k, _d(r)))

@@ -123,6 +123,35 @@ class GraphManager:
         check(self._l.vf_add_between_robust(self._h, C.c_uint64(previousKey), C.c_uint64(currentKey), _d(q), _d(t), _d(cov), C.c_int(loss), C.c_double(k)))
         self._robust[int(currentKey)] = (loss, k)
 
+    def addPoseFactor(self, key, pose, cov, robust=None):
+        """an absolute pose factor on `key` (PriorFactor<Pose3>; vf_add_absolute_pose): pose = (q_wxyz, t) in the graph's world frame,
+        cov 6 x 6 in tangent order [rot, trans], robust as addBetweenFactor's.  The key must carry no band between factor -- reserve
+        a node of its own for the fix (reserveNode(stamp)) -- and key - 1 must still be in the window."""
+        q = np.ascontiguousarray(pose[0], dtype=np.float64)
+        t = np.ascontiguousarray(pose[1], dtype=np.float64)
+        c = np.ascontiguousarray(cov, dtype=np.float64).reshape(6, 6)
+        loss, k = robust_losses.parse(robust)
+        check(self._l.vf_add_absolute_pose(self._h, C.c_uint64(key), _d(q), _d(t), _d(c), C.c_int(loss), C.c_double(k)))
+        if loss != robust_losses.NONE:
+            self._robust[int(key)] = (loss, k)
+
+    def addPositionFactor(self, key, position, cov, robust=None):
+        """an absolute position factor on `key` (GPSFactor; vf_add_absolute_position): position in the graph's world frame, cov 3 x 3;
+        the rules of addPoseFactor"""
+        p = np.ascontiguousarray(position, dtype=np.float64).reshape(3)
+        c = np.ascontiguousarray(cov, dtype=np.float64).reshape(3, 3)
+        loss, k = robust_losses.parse(robust)
+        check(self._l.vf_add_absolute_position(self._h, C.c_uint64(key), _d(p), _d(c), C.c_int(loss), C.c_double(k)))
+        if loss != robust_losses.NONE:
+            self._robust[int(key)] = (loss, k)
+
+    def absolute_factors(self, key0=None, n=None):
+        """kinds (_lib.ABSOLUTE_*) of the factors in the band slots of keys key0 .. key0+n-1 (defaults: the window, as factor_errors)"""
+        key0, n = self._window_keys(key0, n)
+        kinds = np.zeros(n, dtype=np.int32)
+        check(self._l.vf_get_absolute_factors(self._h, C.c_uint64(key0), n, kinds.ctypes.data_as(C.c_void_p)))
+        return kinds
+
     def between_weights(self, key0=None, n=None):
         """how far the last solve's optimum has down-weighted the band between factor ending at each of the keys key0 .. key0+n-1
         (defaults: the window, as factor_errors): rho'/s, the weight GTSAM's reweighting would have given it -- 1 for a Gaussian
@@ -322,9 +351,9 @@ class GraphManager:
 
     def graph(self):
         """GraphManager::graph() (GraphManager.cpp:46-49): the staged factors as a list of dicts -- kind ("prior_pose" |
-        "prior_velocity" | "prior_bias" | "between"), keys, measured (q_wxyz, t), covariance (6 x 6), robust (None, or (loss name, k): noiseModel::Robust)."""
+        "prior_velocity" | "prior_bias" | "between" | "absolute_pose" | "absolute_position", the last two on one key given twice), keys, measured (q_wxyz, t), covariance (6 x 6), robust (None, or (loss name, k): noiseModel::Robust)."""
         n = self.graphSize()
-        names = ("prior_pose", "prior_velocity", "prior_bias", "between")
+        names = ("prior_pose", "prior_velocity", "prior_bias", "between", "absolute_pose", "absolute_position")
         out = []
         for i in range(n):
             kind, k1, k2 = C.c_int(), C.c_uint64(), C.c_uint64()

@@ -196,3 +196,54 @@ class SensorManager:
         self.last_valid_odom = msg
         self.last_valid_key = found[1]
         return added
+
+
+class AbsoluteSensorManager:
+    """A sensor that measures the platform's ABSOLUTE pose or position in the graph's world frame -- a map or relocalisation result,
+    motion capture, a GPS fix in a local datum -- as the reference's sensor managers treat every measurement: a node of its own at the
+    fix's stamp (reserveNode), then the factor on the key returned (GraphManager.addPoseFactor / addPositionFactor).  Such a key has an
+    IMU factor and no odometry ending at it, so its band slot is free for the fix.  Lever arms and the alignment of the sensor's datum
+    with the world frame are the caller's.
+
+    kind: "pose" or "position".  covariance: used for every fix that brings none (6 x 6 in tangent order [rot, trans], or 3 x 3).
+    covariance_order: SensorManager's option for a 6 x 6 covariance that comes with a fix -- "reference" takes it as it is,
+    "ros" reads it as nav_msgs says, (x, y, z, rx, ry, rz), and permutes its blocks to [rot, trans].  robust: a loss for every fix
+    (("huber", 1.345), ...).  A fix the graph cannot take (VF_ERR_CAPACITY, VF_ERR_BAD_KEY) is dropped with a warning, like a missed
+    odometry message."""
+
+    def __init__(self, graph_manager, kind, covariance=None, robust=None, optimize_after=False, covariance_order="reference"):
+        if kind not in ("pose", "position"):
+            raise ValueError('kind must be "pose" or "position"')
+        if covariance_order not in ("reference", "ros"):
+            raise ValueError('covariance_order must be "reference" or "ros"')
+        from . import robust as robust_losses
+        self.gm, self.kind, self.optimize_after, self.covariance_order = graph_manager, kind, optimize_after, covariance_order
+        self.covariance = None if covariance is None else np.asarray(covariance, dtype=np.float64)
+        self.robust = None if robust_losses.parse(robust)[0] == robust_losses.NONE else robust_losses.parse(robust)
+        self.warnings = deque(maxlen=4096)
+        self.keys_and_times = deque(maxlen=4096)
+
+    def fixCallback(self, stamp, position, orientation_wxyz=None, covariance=None):
+        """one fix: returns its key, or None if the graph could not take it"""
+        from ._lib import VilFusionError
+        cov = self.covariance if covariance is None else np.asarray(covariance, dtype=np.float64)
+        if cov is None:
+            raise ValueError("a fix without a covariance, and the manager has none")
+        key = self.gm.reserveNode(float(stamp))
+        try:
+            if self.kind == "position":
+                self.gm.addPositionFactor(key, position, cov.reshape(3, 3), robust=self.robust)
+            else:
+                cov = cov.reshape(6, 6)
+                if covariance is not None and self.covariance_order == "ros":
+                    cov = cov[np.ix_(_TANGENT_FROM_ROS, _TANGENT_FROM_ROS)].copy()
+                self.gm.addPoseFactor(key, (orientation_wxyz, position), cov, robust=self.robust)
+        except VilFusionError as exc:
+            if exc.code not in (-6, -2):
+                raise
+            self.warnings.append(f"absolute {self.kind} factor on key {key} not added: {exc}")
+            return None
+        self.keys_and_times.append((float(stamp), key))
+        if self.optimize_after:
+            self.gm.solve()
+        return key
